@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the SuperPoint + LightGlue hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either launched by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`
      (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or as the plain command above: the parent then
      starts the N rank processes itself -- before making any GPU call -- and relays rank 0's JSON line)
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, the final gather, the
+outputs of the last timed step if --dump-outputs is given (dump_outputs), one JSON line.  Everything else the
+benchmark measures or checks runs only with --full (the `roofline` and `cpu_baseline` objects and the rest below).
 
 Metric (BASELINE.json): image-pairs/sec, SuperPoint + LightGlue, 1024 keypoints, 640x480.
 One "step" = one pass of the hot path over one batch of synthetic pairs resident in HBM:
@@ -14,12 +18,13 @@ images go through one extractor call of 2*pairs images (--joint-extract 0 = two 
 Every rank processes its own `--pairs` image pairs per step (weak scaling, no data-path
 collective); one RCCL gather of per-pair records closes the job.
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel = the one with the largest share of the step:
-`attention_kernel<2,4>`, 18 launches per step, timed live with HIP events around each launch inside the timed
+With --full, rank 0's ONE JSON line also carries `roofline` (dominant kernel = the one with the largest share of the
+step: `attention_kernel<2,4>`, 18 launches per step, timed live with HIP events around each launch inside the timed
 region; `frac` = ALGORITHMIC attention FLOPs / launch time / fp32-MFMA peak, never above 1; the stem convolution
-and the split by self / cross launch are listed under `roofline.kernels`) and `cpu_baseline` (the CPU oracle, a
+and the split by self / cross launch are listed under `roofline.kernels`), `cpu_baseline` (the CPU oracle, a
 PyTorch-CPU port of the reference path, on a bounded sample; also on the N > 1 line, run by rank 0 after the
-timed region and the gather).
+timed region and the gather), `self_check` and the information-only legs (`batch1`, `c3_regime`, `c4`, `config5`).
+Without --full both objects are null and the per-kernel fields of `config.per_rank` are null.
 """
 import argparse
 import ctypes
@@ -29,6 +34,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 import torch
 
@@ -603,6 +609,44 @@ def spawn_ranks(n: int) -> int:
     return 0
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # all files of --dump-outputs together (below 64 MB)
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as `outdir/<name>.npy`, float32 (float64 stays float64; integer and boolean arrays
+    become float64, exactly).  Arrays are taken smallest first, each up to an equal share of the budget still left: one
+    larger than its share is written as a fixed sample of its rows (last axis whole; rows drawn without replacement by
+    a generator seeded from the name, ascending), their flat row numbers beside it as `<name>_rows.npy`.  Same shapes
+    -> same sample, so two builds' files compare element for element.  Returns {file name: shape}."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    items = []
+    for name, t in arrays.items():
+        dt = t.dtype if t.dtype in (torch.float32, torch.float64) else (
+            torch.float32 if t.is_floating_point() else torch.float64)
+        items.append((t.numel() * (4 if dt == torch.float32 else 8), name, t.detach(), dt))
+    items.sort(key=lambda e: e[:2])
+    left, written = budget, {}
+    for i, (nbytes, name, t, dt) in enumerate(items):
+        share = left // (len(items) - i)
+        if nbytes <= share:
+            files = {name: t.to(dt).cpu().numpy()}
+        else:
+            row = t.shape[-1]
+            rows = t.numel() // row
+            esize = 4 if dt == torch.float32 else 8
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randperm(rows, generator=g)[: max(1, share // (row * esize + 8))].sort().values
+            files = {name: t.reshape(rows, row)[idx.to(t.device)].to(dt).cpu().numpy(),
+                     name + "_rows": idx.to(torch.float64).numpy()}
+        for fname, a in files.items():
+            np.save(os.path.join(outdir, fname + ".npy"), a)
+            left -= a.nbytes
+            written[fname] = list(a.shape)
+    return written
+
+
 def self_check(v0, v1, p0, p1, pred, idxs=(0, 10, 21, 31)):
     """Pairs `idxs` (spread over the batch) of the LAST timed step against the CPU oracle (outside the timed region):
     what was measured is also what is correct.  Same comparison as tests/test_gpu_batch32.py (which checks all 32)."""
@@ -666,8 +710,8 @@ def rehearse_cpu(args):
     per_rank, per_rank_summary = per_rank_table([busy, elapsed_local, 0.5 + 0.01 * rank, 5.0, None, None, 10 + rank], world)
     if rank == 0:
         allrec = torch.cat(gathered)
-        # like main(): rank 0 times the CPU baseline after the gather while the other ranks wait at the last barrier
-        base = None if args.no_cpu_baseline else cpu_baseline(args.cpu_pairs, args.cpu_iters)
+        # like main() --full: rank 0 times the CPU baseline after the gather while the other ranks wait at the last barrier
+        base = cpu_baseline(args.cpu_pairs, args.cpu_iters) if args.full and not args.no_cpu_baseline else None
         print(json.dumps({"metric": METRIC, "value": None, "unit": "image-pairs/sec", "n_gpus": world,
                           "steps": args.steps, "warmup": args.warmup, "rehearsal": True,
                           "pairs_gathered": int(allrec.shape[0]),
@@ -679,6 +723,90 @@ def rehearse_cpu(args):
         torch.distributed.destroy_process_group()
 
 
+def roofline_report(args, b, elapsed, durs, adurs, default_shape, wino):
+    """--full: the `roofline` object from the HIP-event durations of the timed launches (attention: `adurs`, self
+    and cross alternating; stem: `durs`) and the step time `elapsed` of all timed steps."""
+    # ---- dominant kernel: attention (SURVEY.md 8d "attention-MFMA roofline") ------------------------------
+    # one product = Q.K^T or P.V of one problem over its 4 heads: 2 * K * K * 64 * 4 FLOP
+    prod = 2.0 * K * K * 64 * 4
+    self_alg = 2 * b * 2 * prod          # 2b images, QK^T + PV each
+    cross_alg = b * 3 * prod             # b pairs: ONE sim + two PV products (lightglue.py:207-217)
+    cross_exec = b * 4 * prod            # the kernel evaluates the second direction's sim again
+    self_ms, cross_ms = adurs[0::2], adurs[1::2]
+    n_self, n_cross = len(self_ms), len(cross_ms)
+    att_ms = sum(adurs)
+    att_alg = n_self * self_alg + n_cross * cross_alg
+    att_exec = n_self * self_alg + n_cross * cross_exec
+
+    def tflops(flops, ms):
+        return flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+
+    att_kernel = ("attention_kernel<2, 4>" if 2 * b * 4 * ((K + 255) // 256) >= 1024 else "attention_kernel<1, 4>")
+    att_traffic, att_src = pmc_traffic_bytes("attention_kernel<2, 4>") if default_shape else (None, None)
+    ach = tflops(att_alg, att_ms)
+    roof = {"bound": "mfma",
+            "kernel": att_kernel + " (flash-style self / bidirectional cross attention, fp32 MFMA 32x32x2; the "
+                      "kernel with the largest share of the step)",
+            "achieved": round(ach, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(ach / FP32_MFMA_PEAK_TFLOPS, 4),
+            "executed_tflops": round(tflops(att_exec, att_ms), 2),
+            "executed_frac": round(tflops(att_exec, att_ms) / FP32_MFMA_PEAK_TFLOPS, 4),
+            "traffic": att_traffic,
+            "traffic_note": ("HBM bytes/launch (mean of self and cross launches), rocprofv3 --pmc FETCH_SIZE(x2) + "
+                             f"WRITE_SIZE passes of the default command ({att_src}); algorithmic per launch: Q, K, V "
+                             f"read once + O written = {2 * b * K * 256 * 4 * 4 / 1e6:.1f} MB"),
+            "launches_timed": len(adurs),
+            "avg_launch_ms": round(att_ms / max(len(adurs), 1), 4),
+            "flops_per_launch": round(att_alg / max(len(adurs), 1)),
+            "share_of_step": round(att_ms / (elapsed * 1e3), 4),
+            "definition": "achieved = ALGORITHMIC attention FLOPs (QK^T + PV; cross attention counted with ONE "
+                          "shared sim) summed over the timed launches / their summed HIP-event durations; "
+                          "executed_* counts the cross sim twice, as the kernel evaluates it"}
+
+    # ---- the other traced kernels ---------------------------------------------------------------------------
+    kernels = [
+        {"kernel": att_kernel + " [self launches]", "launches_timed": n_self,
+         "avg_launch_ms": round(sum(self_ms) / max(n_self, 1), 4), "flops_per_launch": round(self_alg),
+         "achieved": round(tflops(n_self * self_alg, sum(self_ms)), 2),
+         "frac": round(tflops(n_self * self_alg, sum(self_ms)) / FP32_MFMA_PEAK_TFLOPS, 4)},
+        {"kernel": att_kernel + " [cross launches]", "launches_timed": n_cross,
+         "avg_launch_ms": round(sum(cross_ms) / max(n_cross, 1), 4), "flops_per_launch": round(cross_alg),
+         "achieved": round(tflops(n_cross * cross_alg, sum(cross_ms)), 2),
+         "frac": round(tflops(n_cross * cross_alg, sum(cross_ms)) / FP32_MFMA_PEAK_TFLOPS, 4),
+         "executed_frac": round(tflops(n_cross * cross_exec, sum(cross_ms)) / FP32_MFMA_PEAK_TFLOPS, 4)},
+    ]
+    stem_ms = sum(durs)
+    imgs_per_launch = 2 * b if args.joint_extract else b
+    stem_alg = STEM_FLOPS_PER_IMAGE * imgs_per_launch  # direct-convolution FLOPs of SURVEY.md 8d
+    # Winograd F(2x2,3x3): 16 instead of 36 multiplications per 2x2 output block and input channel, so the matrix
+    # pipe executes 4/9 of conv1b's direct FLOPs (conv1a, cin = 1, runs beside it on the VALU).
+    # F(4x4,3x3) stem (default): 36 per 4x4 block = 1/4 of conv1b's direct FLOPs, plus conv1a on the pipe: per
+    # 32x16-pixel work item 36 positions x 2 cout tiles x 32 k steps + 40 conv1a units x 5 = 2504 MFMAs of 4096 FLOP
+    if stem_is_f43(args.conv_arithmetic):
+        stem_exec = 2504 * 4096 * ((H + 15) // 16) * ((W + 31) // 32) * imgs_per_launch
+    else:
+        stem_exec = (2 * 4 * 64 * 64 * H * W * imgs_per_launch) if wino else stem_alg
+    stem_traffic, stem_src = (pmc_traffic_bytes("stem_wino43_kernel" if stem_is_f43(args.conv_arithmetic)
+                                                else "conv3x3_wino_kernel<true, true")
+                              if default_shape else (None, None))
+    kernels.append(
+        {"kernel": stem_kernel_name(args.conv_arithmetic), "launches_timed": len(durs),
+         "avg_launch_ms": round(stem_ms / max(len(durs), 1), 4),
+         "executed_flops_per_launch": stem_exec,
+         "achieved": round(tflops(len(durs) * stem_exec, stem_ms), 2),
+         "frac": round(tflops(len(durs) * stem_exec, stem_ms) / FP32_MFMA_PEAK_TFLOPS, 4),
+         "algorithmic_equiv_tflops": round(tflops(len(durs) * stem_alg, stem_ms), 2),
+         "share_of_step": round(stem_ms / (elapsed * 1e3), 4),
+         "traffic": stem_traffic,
+         "note": "frac = FLOPs the matrix pipe EXECUTES / peak; algorithmic_equiv_tflops = direct-convolution FLOPs "
+                 "(SURVEY.md 8d) / time: a Winograd kernel may exceed the pipe's peak in that unit, it is not a "
+                 f"roofline fraction; traffic from {stem_src}, algorithmic "
+                 f"{imgs_per_launch * H * W * 4 / 1e6:.1f} MB in + "
+                 f"{imgs_per_launch * (H // 2) * (W // 2) * 64 * 4 / 1e6:.1f} MB out"})
+    roof["kernels"] = kernels
+    return roof
+
+
 def main():
     global H, W, K, STEM_FLOPS_PER_IMAGE, PAIR_FLOPS
     ap = argparse.ArgumentParser()
@@ -686,9 +814,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--pairs", type=int, default=32, help="image pairs per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: HIP-event timings of the "
+                         "dominant kernels (`roofline`), the MFMA probe, the oracle check of the last step, the "
+                         "information-only legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's last timed step computed as DIR/<name>.npy "
+                         "(at most 64 MB; larger arrays as a fixed sample of rows, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-self-check", action="store_true",
-                    help="skip the oracle check of four pairs of the last timed step (after the timed region)")
+                    help="with --full: skip the oracle check of four pairs of the last timed step (after the timed region)")
     ap.add_argument("--cpu-pairs", type=int, default=2)
     ap.add_argument("--cpu-iters", type=int, default=8)
     ap.add_argument("--workload", default="c2", choices=["c2", "c4"],
@@ -699,7 +834,8 @@ def main():
     ap.add_argument("--no-experimental", action="store_true",
                     help="accepted for older scripts (the split-arithmetic leg was retired in round 4)")
     ap.add_argument("--no-batch1", action="store_true",
-                    help="skip the informational legs (`batch1` single-pair latency, `c3_regime`, `c4`, `config5`)")
+                    help="with --full: skip the informational legs (`batch1` single-pair latency, `c3_regime`, `c4`, "
+                         "`config5`)")
     ap.add_argument("--conv-arithmetic", default=None, choices=[None, "fp32", "winograd"],
                     help="3x3 convolutions of the timed path: Winograd F(2x2,3x3) / F(4x4,3x3) stem on fp32 MFMA (default) "
                          "or the direct implicit GEMM on fp32 MFMA")
@@ -707,6 +843,8 @@ def main():
                     help="no GPU work: exercise only the multi-process plumbing (rendezvous, barriers, max-reduce, "
                          "final gather, JSON) on gloo with a dummy step; never a measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: this process becomes the parent of the N ranks (it has made no GPU call and makes none)
@@ -759,13 +897,15 @@ def main():
             torch.distributed.barrier()
 
     calls = 1 if args.joint_extract else 2
+    trace = atrace = None
     with torch.no_grad():
         for _ in range(args.warmup):
             step()
-        trace = nat.KernelTrace(calls * args.steps)                     # stem launches
-        atrace = nat.KernelTrace(2 * mat.conf.n_layers * args.steps)   # attention launches (self, cross per layer)
-        ext._runner.trace = trace
-        mat.trace = atrace
+        if args.full:
+            trace = nat.KernelTrace(calls * args.steps)                     # stem launches
+            atrace = nat.KernelTrace(2 * mat.conf.n_layers * args.steps)   # attention launches (self, cross per layer)
+            ext._runner.trace = trace
+            mat.trace = atrace
         torch.cuda.synchronize(dev)
         barrier()
         torch.cuda.synchronize(dev)
@@ -776,8 +916,9 @@ def main():
         busy = time.perf_counter() - t0  # this rank's own steps; the closing barrier waits for the slowest rank
         barrier()
         elapsed_local = elapsed = time.perf_counter() - t0
-        ext._runner.trace = None
-        mat.trace = None
+        if args.full:
+            ext._runner.trace = None
+            mat.trace = None
 
     # max over ranks
     if world > 1:
@@ -791,23 +932,34 @@ def main():
     torch.cuda.synchronize(dev)
     gather_ms = (time.perf_counter() - tg) * 1e3
 
-    durs = trace.durations_ms()
-    adurs = atrace.durations_ms()
-    trace.close()
-    atrace.close()
+    if args.dump_outputs and rank == 0:  # what a caller of the timed path received from its last step
+        outputs = {**{k + "0": v for k, v in p0.items()}, **{k + "1": v for k, v in p1.items()}, **pred}
+        # (not the host timings such as extractor_core_time_ms0: they differ from run to run by nature)
+        written = dump_outputs(args.dump_outputs, {k: v for k, v in outputs.items() if "_time_ms" not in k})
+        print(f"bench: last timed step -> {len(written)} files in {args.dump_outputs}", file=sys.stderr)
 
-    # what the matrix pipe of THIS rank's GPU sustains right after the timed region (the data-sheet 157.3 TFLOP/s assumes
-    # 2.4 GHz), and every rank's own timings: one all_gather, outside the timed region
-    try:
-        tf, ghz = ctypes.c_float(0), ctypes.c_float(0)
-        nat.check(nat.lib().gfc_probe_mfma_peak(80000, ctypes.byref(tf), ctypes.byref(ghz), nat.stream_ptr(dev)), "probe")
-        probe = {"tflops": round(tf.value, 1), "shader_clock_ghz": round(ghz.value, 3),
-                 "note": "registers-only v_mfma_f32_32x32x2_f32 loop on every SIMD, measured after the timed region"}
-    except Exception as e:  # noqa: BLE001
-        probe = {"tflops": None, "shader_clock_ghz": None, "error": repr(e)[:120]}
+    durs = adurs = None
+    probe = {"tflops": None, "shader_clock_ghz": None}
+    if args.full:
+        durs = trace.durations_ms()
+        adurs = atrace.durations_ms()
+        trace.close()
+        atrace.close()
+        # what the matrix pipe of THIS rank's GPU sustains right after the timed region (the data-sheet 157.3 TFLOP/s
+        # assumes 2.4 GHz)
+        try:
+            tf, ghz = ctypes.c_float(0), ctypes.c_float(0)
+            nat.check(nat.lib().gfc_probe_mfma_peak(80000, ctypes.byref(tf), ctypes.byref(ghz), nat.stream_ptr(dev)),
+                      "probe")
+            probe = {"tflops": round(tf.value, 1), "shader_clock_ghz": round(ghz.value, 3),
+                     "note": "registers-only v_mfma_f32_32x32x2_f32 loop on every SIMD, measured after the timed region"}
+        except Exception as e:  # noqa: BLE001
+            probe = {"tflops": None, "shader_clock_ghz": None, "error": repr(e)[:120]}
+    # every rank's own timings: one all_gather, outside the timed region
     per_rank, per_rank_summary = per_rank_table(
-        [busy, elapsed_local, sum(adurs) / max(len(adurs), 1), sum(durs) / max(len(durs), 1), probe["tflops"],
-         probe["shader_clock_ghz"], int((pred["matches0"] >= 0).sum())], world, dev)
+        [busy, elapsed_local, sum(adurs) / max(len(adurs), 1) if args.full else None,
+         sum(durs) / max(len(durs), 1) if args.full else None, probe["tflops"], probe["shader_clock_ghz"],
+         int((pred["matches0"] >= 0).sum())], world, dev)
 
     if rank == 0:
         allrec = torch.cat(gathered)
@@ -817,84 +969,7 @@ def main():
         wino = conv_mode_of(args.conv_arithmetic) == "winograd"
         default_shape = args.workload == "c2" and b == 32 and args.joint_extract and wino
 
-        # ---- dominant kernel: attention (SURVEY.md 8d "attention-MFMA roofline") ------------------------------
-        # one product = Q.K^T or P.V of one problem over its 4 heads: 2 * K * K * 64 * 4 FLOP
-        prod = 2.0 * K * K * 64 * 4
-        self_alg = 2 * b * 2 * prod          # 2b images, QK^T + PV each
-        cross_alg = b * 3 * prod             # b pairs: ONE sim + two PV products (lightglue.py:207-217)
-        cross_exec = b * 4 * prod            # the kernel evaluates the second direction's sim again
-        self_ms, cross_ms = adurs[0::2], adurs[1::2]
-        n_self, n_cross = len(self_ms), len(cross_ms)
-        att_ms = sum(adurs)
-        att_alg = n_self * self_alg + n_cross * cross_alg
-        att_exec = n_self * self_alg + n_cross * cross_exec
-
-        def tflops(flops, ms):
-            return flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-
-        att_kernel = ("attention_kernel<2, 4>" if 2 * b * 4 * ((K + 255) // 256) >= 1024 else "attention_kernel<1, 4>")
-        att_traffic, att_src = pmc_traffic_bytes("attention_kernel<2, 4>") if default_shape else (None, None)
-        ach = tflops(att_alg, att_ms)
-        roof = {"bound": "mfma",
-                "kernel": att_kernel + " (flash-style self / bidirectional cross attention, fp32 MFMA 32x32x2; the "
-                          "kernel with the largest share of the step)",
-                "achieved": round(ach, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(ach / FP32_MFMA_PEAK_TFLOPS, 4),
-                "executed_tflops": round(tflops(att_exec, att_ms), 2),
-                "executed_frac": round(tflops(att_exec, att_ms) / FP32_MFMA_PEAK_TFLOPS, 4),
-                "traffic": att_traffic,
-                "traffic_note": ("HBM bytes/launch (mean of self and cross launches), rocprofv3 --pmc FETCH_SIZE(x2) + "
-                                 f"WRITE_SIZE passes of the default command ({att_src}); algorithmic per launch: Q, K, V "
-                                 f"read once + O written = {2 * b * K * 256 * 4 * 4 / 1e6:.1f} MB"),
-                "launches_timed": len(adurs),
-                "avg_launch_ms": round(att_ms / max(len(adurs), 1), 4),
-                "flops_per_launch": round(att_alg / max(len(adurs), 1)),
-                "share_of_step": round(att_ms / (elapsed * 1e3), 4),
-                "definition": "achieved = ALGORITHMIC attention FLOPs (QK^T + PV; cross attention counted with ONE "
-                              "shared sim) summed over the timed launches / their summed HIP-event durations; "
-                              "executed_* counts the cross sim twice, as the kernel evaluates it"}
-
-        # ---- the other traced kernels ---------------------------------------------------------------------------
-        kernels = [
-            {"kernel": att_kernel + " [self launches]", "launches_timed": n_self,
-             "avg_launch_ms": round(sum(self_ms) / max(n_self, 1), 4), "flops_per_launch": round(self_alg),
-             "achieved": round(tflops(n_self * self_alg, sum(self_ms)), 2),
-             "frac": round(tflops(n_self * self_alg, sum(self_ms)) / FP32_MFMA_PEAK_TFLOPS, 4)},
-            {"kernel": att_kernel + " [cross launches]", "launches_timed": n_cross,
-             "avg_launch_ms": round(sum(cross_ms) / max(n_cross, 1), 4), "flops_per_launch": round(cross_alg),
-             "achieved": round(tflops(n_cross * cross_alg, sum(cross_ms)), 2),
-             "frac": round(tflops(n_cross * cross_alg, sum(cross_ms)) / FP32_MFMA_PEAK_TFLOPS, 4),
-             "executed_frac": round(tflops(n_cross * cross_exec, sum(cross_ms)) / FP32_MFMA_PEAK_TFLOPS, 4)},
-        ]
-        stem_ms = sum(durs)
-        imgs_per_launch = 2 * b if args.joint_extract else b
-        stem_alg = STEM_FLOPS_PER_IMAGE * imgs_per_launch  # direct-convolution FLOPs of SURVEY.md 8d
-        # Winograd F(2x2,3x3): 16 instead of 36 multiplications per 2x2 output block and input channel, so the matrix
-        # pipe executes 4/9 of conv1b's direct FLOPs (conv1a, cin = 1, runs beside it on the VALU).
-        # F(4x4,3x3) stem (default): 36 per 4x4 block = 1/4 of conv1b's direct FLOPs, plus conv1a on the pipe: per
-        # 32x16-pixel work item 36 positions x 2 cout tiles x 32 k steps + 40 conv1a units x 5 = 2504 MFMAs of 4096 FLOP
-        if stem_is_f43(args.conv_arithmetic):
-            stem_exec = 2504 * 4096 * ((H + 15) // 16) * ((W + 31) // 32) * imgs_per_launch
-        else:
-            stem_exec = (2 * 4 * 64 * 64 * H * W * imgs_per_launch) if wino else stem_alg
-        stem_traffic, stem_src = (pmc_traffic_bytes("stem_wino43_kernel" if stem_is_f43(args.conv_arithmetic)
-                                                    else "conv3x3_wino_kernel<true, true")
-                                  if default_shape else (None, None))
-        kernels.append(
-            {"kernel": stem_kernel_name(args.conv_arithmetic), "launches_timed": len(durs),
-             "avg_launch_ms": round(stem_ms / max(len(durs), 1), 4),
-             "executed_flops_per_launch": stem_exec,
-             "achieved": round(tflops(len(durs) * stem_exec, stem_ms), 2),
-             "frac": round(tflops(len(durs) * stem_exec, stem_ms) / FP32_MFMA_PEAK_TFLOPS, 4),
-             "algorithmic_equiv_tflops": round(tflops(len(durs) * stem_alg, stem_ms), 2),
-             "share_of_step": round(stem_ms / (elapsed * 1e3), 4),
-             "traffic": stem_traffic,
-             "note": "frac = FLOPs the matrix pipe EXECUTES / peak; algorithmic_equiv_tflops = direct-convolution FLOPs "
-                     "(SURVEY.md 8d) / time: a Winograd kernel may exceed the pipe's peak in that unit, it is not a "
-                     f"roofline fraction; traffic from {stem_src}, algorithmic "
-                     f"{imgs_per_launch * H * W * 4 / 1e6:.1f} MB in + "
-                     f"{imgs_per_launch * (H // 2) * (W // 2) * 64 * 4 / 1e6:.1f} MB out"})
-        roof["kernels"] = kernels
+        roof = roofline_report(args, b, elapsed, durs, adurs, default_shape, wino) if args.full else None
 
         exec_pair_flops = PAIR_FLOPS_EXECUTED if args.workload == "c2" and stem_is_f43(args.conv_arithmetic) else None
         out = {
@@ -933,30 +1008,31 @@ def main():
                                                   if exec_pair_flops else None)},
             "roofline": roof,
         }
-        out["roofline"]["sustained_mfma_probe"] = probe  # rank 0's; every rank's is in config.per_rank
-        if args.workload == "c2" and not args.no_self_check:
+        if args.full:
+            out["roofline"]["sustained_mfma_probe"] = probe  # rank 0's; every rank's is in config.per_rank
+        if args.full and args.workload == "c2" and not args.no_self_check:
             try:
                 out["self_check"] = self_check(v0, v1, p0, p1, pred)
             except Exception as e:  # noqa: BLE001
                 out["self_check"] = {"pairs_equal": None, "error": repr(e)[:200]}
-        if args.workload == "c2" and not args.no_batch1:
+        if args.full and args.workload == "c2" and not args.no_batch1:
             try:  # information only: the batch-1 regime of the HPatches evaluation loop (never `value`)
                 out["batch1"] = batch1_latency(dev)
             except Exception as e:  # noqa: BLE001
                 out["batch1"] = {"pairs_per_s": None, "error": repr(e)[:200]}
-        if args.workload == "c2" and not args.no_batch1 and world == 1:
+        if args.full and args.workload == "c2" and not args.no_batch1 and world == 1:
             try:  # information only: config 3's regime at the batched rate (never `value`)
                 out["c3_regime"] = c3_regime(dev)
             except Exception as e:  # noqa: BLE001
                 out["c3_regime"] = {"pair_batch32": None, "error": repr(e)[:200]}
-        if args.workload == "c2" and not args.no_batch1 and world == 1:
+        if args.full and args.workload == "c2" and not args.no_batch1 and world == 1:
             for key, leg in (("c4", c4_shape), ("config5", config5)):
                 try:  # information only: the other BASELINE configs' shapes (never `value`)
                     out[key] = leg(dev)
                 except Exception as e:  # noqa: BLE001
                     out[key] = {"pairs_per_s": None, "error": repr(e)[:200]}
                 torch.cuda.empty_cache()
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, after the timed region and the gather; at N > 1 the other ranks wait at the closing barrier
             out["cpu_baseline"] = cpu_baseline(args.cpu_pairs, args.cpu_iters)
             if args.workload == "c2" and world == 1:

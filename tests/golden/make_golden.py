@@ -666,6 +666,54 @@ def golden_pad_random_c():
     save("pad_random_c", **out)
 
 
+from fuzz_cases import (auc_cases, lightglue_cases, row_checksums, sample_rows, superpoint_official_cases,  # noqa: E402
+                        superpoint_open_cases)
+
+
+def golden_reference_fuzz():
+    """The reference on the random configurations of tests/golden/fuzz_cases.py (inputs regenerated from seeds by the
+    test): open SuperPoint image by image, official SuperPoint, LightGlue, and the AUC of the evaluation summaries.
+    Descriptors and log-assignment matrices as SAMPLE_ROWS rows in full + a weighted checksum of every row (float32 for
+    descriptors, float64 for log_assignment): the full arrays would be ~40 MB."""
+    from gluefactory.utils.tools import cal_error_auc
+
+    out = {}
+
+    def pixel_keypoints(kp):  # key points without refinement sit on pixel centres: kp - 0.5 as int16, exactly
+        assert torch.equal(kp - 0.5, (kp - 0.5).round()) and (len(kp) == 0 or kp.abs().max() < 2 ** 15)
+        return npy(kp - 0.5).astype(np.int16)
+
+    def rows(prefix, a, checksum_dtype=np.float32):  # a [N, D]
+        idx = sample_rows(a.shape[0])
+        out[prefix + "_rows"], out[prefix + "_sample"] = idx, npy(a[idx])
+        out[prefix + "_checksums"] = npy(row_checksums(a)).astype(checksum_dtype)
+
+    for case, img, conf in superpoint_open_cases():
+        m = make_spo(**conf)
+        for i in range(img.shape[0]):  # the reference stacks per-image lists: image by image (b == 1 is its eval use)
+            p = m({"image": img[i:i + 1]})
+            out[f"open{case}_{i}_keypoints"] = pixel_keypoints(p["keypoints"][0])
+            out[f"open{case}_{i}_keypoint_scores"] = npy(p["keypoint_scores"][0])
+            rows(f"open{case}_{i}_descriptors", p["descriptors"][0])
+    for case, img, size, conf in superpoint_official_cases():
+        p = make_sp_official(**conf)({"image": img} if size is None else {"image": img, "image_size": size})
+        out[f"official{case}_keypoints"] = pixel_keypoints(p["keypoints"][0])
+        out[f"official{case}_keypoint_scores"] = npy(p["keypoint_scores"][0])
+        rows(f"official{case}_descriptors", p["descriptors"][0])
+    for case, data, th in lightglue_cases():
+        p = make_lg(filter_threshold=th)(data)
+        for key in ("matches0", "matches1", "matching_scores0"):
+            out[f"lg{case}_{key}"] = npy(p[key])
+        la = p["log_assignment"]  # [b, m + 1, n + 1]
+        out[f"lg{case}_log_assignment_shape"] = np.array(la.shape, dtype=np.int64)
+        rows(f"lg{case}_log_assignment", la.reshape(-1, la.shape[-1]), np.float64)
+        for i in range(p["ref_descriptors0"].shape[0]):  # [b, 1, m, D]
+            rows(f"lg{case}_{i}_ref_descriptors0", p["ref_descriptors0"][i, 0])
+    for n, errors, ths in auc_cases():
+        out[f"auc{n}_{ths[0]}"] = np.array([float(a) for a in cal_error_auc(errors, ths)], dtype=np.float64)
+    save("reference_fuzz", **out)
+
+
 if __name__ == "__main__":
     if "--only-pad" in sys.argv:
         golden_pad_random_c()
@@ -697,6 +745,9 @@ if __name__ == "__main__":
     if "--only-specular" in sys.argv:
         golden_specular()
         sys.exit(0)
+    if "--only-reference-fuzz" in sys.argv:
+        golden_reference_fuzz()
+        sys.exit(0)
     golden_specular()
     golden_scale_ori()
     golden_homography()
@@ -715,3 +766,4 @@ if __name__ == "__main__":
     golden_c4_pairs()
     golden_c2_fp64_order()
     golden_pad_random_c()
+    golden_reference_fuzz()

@@ -117,7 +117,7 @@ def test_stem_fused_conv1a_conv1b_pool(h, w, bn):
 
 
 @pytest.mark.parametrize("cin,cout,pool", [(64, 128, False), (64, 64, True), (128, 64, False)])
-def test_conv3x3_many_items_persistent_handover(cin, cout, pool):
+def test_conv3x3_many_items_persistent_handover(cin, cout, pool, tmp_path):
     """More work items than resident workgroups (512-768): persistent workgroups hand over from item to item with the
     next halo tile / weight slice prefetched; partial border tiles included.  Checked against the one-item-per-
     workgroup launch of the same kernel family (bit-identical) and against torch."""
@@ -148,18 +148,19 @@ def test_conv3x3_many_items_persistent_handover(cin, cout, pool):
     # process): all within tolerance of torch; for one chunk size the persistent and the one-item-per-workgroup
     # launch must be bit-identical (same MFMA order, only the staging differs)
     torch.save({"x": xd.cpu(), "wp": wp.cpu(), "bias": bias, "scale": scale, "shift": shift, "pool": pool,
-                "ref": ref.permute(0, 2, 3, 1).contiguous()}, "/tmp/gfc_conv_variants.pt")
+                "ref": ref.permute(0, 2, 3, 1).contiguous()}, tmp_path / "conv_variants.pt")
     code = (
         "import sys, torch; sys.path.insert(0, %r)\n"
         "from glue_factory_colon_amd import _native as nat\n"
-        "d = torch.load('/tmp/gfc_conv_variants.pt'); dev = torch.device('cuda', 0); lib = nat.lib()\n"
+        "d = torch.load(%r); dev = torch.device('cuda', 0); lib = nat.lib()\n"
         "x, wp, bi, sc, sh = (d[k].to(dev) for k in ('x', 'wp', 'bias', 'scale', 'shift'))\n"
         "y = torch.full(d['ref'].shape, float('nan'), device=dev)\n"
         "b, h, w, cin = x.shape; cout = wp.shape[1]\n"
         "nat.check(lib.gfc_conv3x3(nat.ptr(x), nat.ptr(wp), nat.ptr(bi), nat.ptr(sc), nat.ptr(sh), nat.ptr(y), b, h, w,"
         " cin, cout, 1, int(d['pool']), nat.stream_ptr(dev)), 'conv')\n"
         "torch.cuda.synchronize(); err = float((y.cpu() - d['ref']).abs().max()); assert err < 2e-5, err\n"
-        "import hashlib; print('VARIANT_OK', hashlib.sha1(y.cpu().numpy().tobytes()).hexdigest())\n") % ROOT
+        "import hashlib; print('VARIANT_OK', hashlib.sha1(y.cpu().numpy().tobytes()).hexdigest())\n") % (
+        ROOT, str(tmp_path / "conv_variants.pt"))
     digests = {}
     for kc, persist in ((16, 0), (16, 1), (32, 0), (32, 1)):
         env = dict(os.environ, GFC_CONV_KC=str(kc), GFC_CONV_PERSIST=str(persist))

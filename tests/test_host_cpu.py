@@ -203,42 +203,6 @@ def test_base_model_alias():
     assert lightglue.__main_model__ is lightglue.LightGlue and not issubclass(lightglue.LightGlue, base_model.BaseModel)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/gluefactory"), reason="reference checkout not present")
-def test_dropin_inside_reference_registry():
-    """Build container only: the REFERENCE's get_model / TwoViewPipeline resolve and construct this package's
-    modules from a config block (subclassing the reference's own BaseModel), and report initialised."""
-    code = (
-        "import sys\n"
-        f"sys.path[:0] = [{os.path.join(ROOT, 'tests', 'golden', '_standins')!r}, '/root/reference', {ROOT!r}]\n"
-        "sys.dont_write_bytecode = True\n"
-        "from gluefactory.models import get_model\n"
-        "from gluefactory.models.base_model import BaseModel\n"
-        "from gluefactory.models.two_view_pipeline import TwoViewPipeline\n"
-        "import glue_factory_colon_amd.base_model as bm\n"
-        "assert bm.USING_REFERENCE_BASE and bm.BaseModel is BaseModel\n"
-        "ext = get_model('glue_factory_colon_amd.superpoint_open')\n"
-        "mat = get_model('glue_factory_colon_amd.lightglue')\n"
-        "assert issubclass(ext, BaseModel) and mat.__name__ == 'LightGlue'\n"
-        "assert get_model('glue_factory_colon_amd.superpoint').__module__ == 'glue_factory_colon_amd.superpoint'\n"
-        "assert issubclass(get_model('glue_factory_colon_amd.lightglue_pretrained'), BaseModel)\n"
-        "pipe = TwoViewPipeline({'extractor': {'name': 'glue_factory_colon_amd.superpoint_open', 'weights': 'synthetic',\n"
-        "    'max_num_keypoints': 1024, 'detection_threshold': 0.0, 'nms_radius': 3},\n"
-        "    'matcher': {'name': 'glue_factory_colon_amd.lightglue_pretrained', 'features': 'superpoint',\n"
-        "    'weights': 'synthetic', 'filter_threshold': 0.1}}).eval()\n"
-        "assert pipe.extractor.conf.max_num_keypoints == 1024 and pipe.extractor.conf.remove_borders == 4\n"
-        "assert pipe.is_initialized()\n"
-        "# this package's pipeline class (the one with forward_pairs, for export_predictions(pair_batch=N)) by name\n"
-        "P = get_model('glue_factory_colon_amd.two_view_pipeline')\n"
-        "assert issubclass(P, BaseModel) and hasattr(P, 'forward_pairs') and not hasattr(TwoViewPipeline, 'forward_pairs')\n"
-        "p2 = P({'extractor': {'name': 'glue_factory_colon_amd.superpoint', 'weights': 'synthetic'},\n"
-        "        'matcher': {'name': 'glue_factory_colon_amd.lightglue', 'weights': 'synthetic'}}).eval()\n"
-        "assert p2.is_initialized() and hasattr(p2.extractor, 'forward_views') and hasattr(p2.matcher, 'forward_pairs')\n"
-        "print('DROPIN_OK')\n")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=240,
-                       env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-    assert r.returncode == 0 and "DROPIN_OK" in r.stdout, r.stdout + r.stderr
-
-
 def test_bench_multiprocess_plumbing_rehearsal():
     """bench.py --gpus 2 launched exactly as the driver does (torch.distributed.run), with --rehearse-cpu:
     rendezvous on 127.0.0.1, barriers, MAX all-reduce of the elapsed time, the final gather, one JSON line."""
@@ -246,15 +210,48 @@ def test_bench_multiprocess_plumbing_rehearsal():
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--pairs", "4", "--rehearse-cpu", "--cpu-pairs", "1", "--cpu-iters", "1"]
+           "--warmup", "1", "--pairs", "4", "--rehearse-cpu", "--full", "--cpu-pairs", "1", "--cpu-iters", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout + r.stderr
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["pairs_gathered"] == 8 and out["matches_per_rank"] == [10, 11]
-    # the N > 1 line carries the CPU baseline too (rank 0 times it after the gather; bounded sample here)
+    # with --full the N > 1 line carries the CPU baseline too (rank 0 times it after the gather; bounded sample here)
     base = out["cpu_baseline"]
     assert base is not None and base["value"] > 0 and base["kind"] == "port" and base["cores"] >= 1
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs writer: every array as <name>.npy in float32 / float64 (integers exactly), within the
+    byte budget; an array above its share of the budget as a fixed sample of rows beside their row numbers, the same
+    sample on every call."""
+    import numpy as np
+
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    arrays = {"keypoints0": torch.rand((4, 300, 2), generator=g), "matches0": torch.randint(-1, 300, (4, 300), generator=g),
+              "mask0": torch.rand((4, 300), generator=g) > 0.5, "descriptors0": torch.randn((4, 300, 256), generator=g),
+              "log_assignment": torch.randn((4, 301, 301), generator=g)}
+    budget = 1 << 20  # the two large arrays (1.2 and 1.4 MB) do not fit
+    a_dir, b_dir = tmp_path / "a", tmp_path / "b"
+    written = bench.dump_outputs(str(a_dir), arrays, budget=budget)
+    assert bench.dump_outputs(str(b_dir), arrays, budget=budget) == written
+    files = sorted(os.listdir(a_dir))
+    assert files == sorted(f + ".npy" for f in written)
+    assert sum(os.path.getsize(a_dir / f) for f in files) <= budget + 128 * len(files)  # + the .npy headers
+    for f in files:
+        a = np.load(a_dir / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, np.load(b_dir / f)), f
+    assert np.array_equal(np.load(a_dir / "matches0.npy"), arrays["matches0"].double().numpy())
+    assert np.array_equal(np.load(a_dir / "keypoints0.npy"), arrays["keypoints0"].numpy())
+    assert np.array_equal(np.load(a_dir / "mask0.npy"), arrays["mask0"].float().numpy())
+    for name in ("descriptors0", "log_assignment"):
+        rows = np.load(a_dir / (name + "_rows.npy")).astype(np.int64)
+        full = arrays[name].reshape(-1, arrays[name].shape[-1]).numpy()
+        assert 0 < len(rows) < len(full) and (np.diff(rows) > 0).all()
+        assert np.array_equal(np.load(a_dir / (name + ".npy")), full[rows])
+    assert bench.DUMP_BUDGET_BYTES + 4096 <= 64e6
 
 
 def test_bench_spawns_its_own_ranks_without_a_launcher():

@@ -1,180 +1,127 @@
-"""Differential sweep of the ORACLE against the reference's own modules on random configurations (CPU; runs only where
-/root/reference exists, i.e. in the build container -- the committed golden vectors pin fixed cases, this pins the
-restatement on shapes and options the fixtures do not hold: image sizes that are not multiples of 8, batches, every NMS
-radius, thresholds, border widths, top-k above / below the candidate count, RGB input, official legacy / fixed sampling
-with image_size, LightGlue on tiny and unequal key-point sets).  The reference is imported exactly as
-tests/golden/make_golden.py imports it (omegaconf stand-in, name-seeded weights, no network)."""
+"""Differential sweep of the ORACLE against the reference's own modules on random configurations (CPU): this pins the
+restatement on shapes and options the other fixtures do not hold: image sizes that are not multiples of 8, batches,
+every NMS radius, thresholds, border widths, top-k above / below the candidate count, RGB input, official legacy / fixed
+sampling with image_size, LightGlue on tiny and unequal key-point sets.  The configurations are drawn from seeds
+(tests/golden/fuzz_cases.py); what the reference returned for them is tests/golden/reference_fuzz.npz, written by
+tests/golden/make_golden.py::golden_reference_fuzz (the reference imported with the omegaconf stand-in, name-seeded
+weights, no network).  Descriptors and log-assignment matrices: SAMPLE_ROWS rows element-wise, every row through a
+weighted checksum (bounded by what the element-wise tolerance implies); key points as pixel indices (centre - 0.5)."""
 import os
 import sys
-import tempfile
 
-import pytest
 import torch
 
-REF = os.environ.get("GFC_REFERENCE", "/root/reference")
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "gluefactory")), reason="reference checkout not present")
-
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+sys.path.insert(0, os.path.join(HERE, "golden"))
+from fuzz_cases import (auc_cases, lightglue_cases, row_checksums, row_weights, sample_rows,  # noqa: E402
+                        superpoint_official_cases, superpoint_open_cases)
 
 
-@pytest.fixture(scope="module")
-def ref():
-    sys.dont_write_bytecode = True
-    added = [os.path.join(HERE, "golden", "_standins"), REF]
-    for p in added:
-        sys.path.insert(0, p)
-    try:
-        from gluefactory.models.extractors import superpoint_open as ref_spo
-        from gluefactory.models.matchers import lightglue as ref_lg
-        import gluefactory_nonfree.superpoint as ref_sp
-    finally:
-        for p in added:
-            sys.path.remove(p)
+def _keypoints(g, key):
+    """The reference's key points: stored as pixel indices (int16), the points are the pixel centres."""
+    return g[key].float() + 0.5
+
+
+def _descriptors_close(g, prefix, d, tol):
+    """d [N, D] against the reference's rows `prefix`_sample (element-wise) and `prefix`_checksums (every row; stored
+    as float32, whose rounding, below 1e-6 for unit rows, the tolerances leave room for)."""
+    rows = g[prefix + "_rows"]
+    assert torch.equal(rows, torch.as_tensor(sample_rows(d.shape[0]))), prefix
+    err = (d[rows] - g[prefix + "_sample"]).abs().max().item() if len(rows) else 0.0
+    c_err = (row_checksums(d) - g[prefix + "_checksums"].double()).abs().max().item() if d.shape[0] else 0.0
+    assert err <= tol and c_err <= tol, (prefix, err, c_err)
+    return max(err, c_err)
+
+
+def _log_assignment_close(g, prefix, la, tol):
+    """la [R, C] against the reference within |la - ref| <= tol * (1 + |la|) element-wise on the sampled rows, and on
+    every row's checksum within the bound that this element-wise tolerance implies: tol * (|w| . (1 + |la|))."""
+    rows = g[prefix + "_rows"]
+    assert torch.equal(rows, torch.as_tensor(sample_rows(la.shape[0]))), prefix
+    ref = g[prefix + "_sample"]
+    assert ((ref - la[rows]).abs() / (1 + la[rows].abs())).max().item() <= tol, prefix
+    c_err = (row_checksums(la) - g[prefix + "_checksums"]).abs()
+    bound = tol * ((1 + la.double().abs()) @ row_weights(la.shape[-1]).abs())
+    assert (c_err <= bound).all(), (prefix, (c_err / bound).max().item())
+
+
+def test_superpoint_open_oracle_equals_reference_on_random_configurations(golden):
     from glue_factory_colon_amd import weights
-    tmp = tempfile.mkdtemp()
-    path = os.path.join(tmp, "spo.pth")
-    torch.save(weights.superpoint_open_state_dict(0), path)
-
-    def make_official(**conf):
-        sd = weights.superpoint_state_dict(0)
-        orig = torch.hub.load_state_dict_from_url
-        torch.hub.load_state_dict_from_url = lambda *a, **k: sd  # no network: the constructor's fetch is redirected
-        try:
-            return ref_sp.SuperPoint(conf).eval()
-        finally:
-            torch.hub.load_state_dict_from_url = orig
-
-    def make_lg(**conf):
-        m = ref_lg.LightGlue({"input_dim": 256, **conf}).eval()
-        m.load_state_dict(weights.lightglue_state_dict(0), strict=False)
-        return m
-
-    return {"spo": lambda **c: ref_spo.SuperPoint({"weights": path, **c}).eval(), "official": make_official, "lg": make_lg,
-            "weights": weights}
-
-
-def _ri(g, lo, hi):
-    return int(torch.randint(lo, hi + 1, (1,), generator=g))
-
-
-def test_superpoint_open_oracle_equals_reference_on_random_configurations(ref):
-    from glue_factory_colon_amd import synthetic
     from oracle import superpoint as osp
 
-    g = torch.Generator().manual_seed(501)
-    sd = ref["weights"].superpoint_open_state_dict(0)
+    g = golden("reference_fuzz")
+    sd = weights.superpoint_open_state_dict(0)
     checked = ragged = 0
     worst = 0.0
     with torch.no_grad():
-        for case in range(14):
-            h, w = _ri(g, 40, 150), _ri(g, 40, 170)  # any size: the network floors to multiples of 8 on its way down
-            b = _ri(g, 1, 2)
-            r, border = _ri(g, 0, 4), (0, 4, 6)[_ri(g, 0, 2)]
-            th = (0.0, 0.005, 0.02)[_ri(g, 0, 2)]
-            k = (None, 30, 400)[_ri(g, 0, 2)]
-            img = synthetic.synthetic_images(b, h, w, seed=700 + case)
-            if case % 3 == 0:
-                img = torch.cat([img * 0.9, img, img * 0.8], 1).clamp(0, 1)
-            conf = dict(nms_radius=r, remove_borders=border, detection_threshold=th, max_num_keypoints=k)
-            m = ref["spo"](**conf)
-            for i in range(b):  # the reference stacks per-image lists: call it image by image (b == 1 is its eval use)
-                p = m({"image": img[i:i + 1]})
+        for case, img, conf in superpoint_open_cases():
+            b, h, w = img.shape[0], img.shape[-2], img.shape[-1]
+            for i in range(b):  # the reference stacks per-image lists: it ran image by image (b == 1 is its eval use)
                 o = osp.extract(sd, img[i:i + 1], "open", **conf)  # same batch size: the CPU convolutions block by batch
-                assert torch.equal(p["keypoints"][0], o["keypoints"][0]), (case, conf, h, w)
+                key = f"open{case}_{i}"
+                assert torch.equal(_keypoints(g, key + "_keypoints"), o["keypoints"][0]), (case, conf, h, w)
                 if len(o["keypoints"][0]):
-                    es = (p["keypoint_scores"][0] - o["keypoint_scores"][0]).abs().max().item()
-                    ed = (p["descriptors"][0] - o["descriptors"][0]).abs().max().item()
+                    es = (g[key + "_keypoint_scores"] - o["keypoint_scores"][0]).abs().max().item()
+                    assert es <= 1e-6, (case, conf, h, w, es)
+                    ed = _descriptors_close(g, key + "_descriptors", o["descriptors"][0], 1e-5)
                     worst = max(worst, es, ed)
-                    assert es <= 1e-6 and ed <= 1e-5, (case, conf, h, w, es, ed)
                 checked += 1
             ragged += int(h % 8 != 0 or w % 8 != 0)
     print('open: worst float difference', worst)
     assert checked >= 12 and ragged >= 5, (checked, ragged)
 
 
-def test_superpoint_official_oracle_equals_reference_on_random_configurations(ref):
-    from glue_factory_colon_amd import synthetic
+def test_superpoint_official_oracle_equals_reference_on_random_configurations(golden):
+    from glue_factory_colon_amd import weights
     from oracle import superpoint as osp
 
-    g = torch.Generator().manual_seed(502)
-    sd = ref["weights"].superpoint_state_dict(0)
+    g = golden("reference_fuzz")
+    sd = weights.superpoint_state_dict(0)
     checked = 0
     with torch.no_grad():
-        for case in range(10):
-            h, w = 8 * _ri(g, 6, 18), 8 * _ri(g, 6, 20)
-            r, border = _ri(g, 1, 4), (2, 4)[_ri(g, 0, 1)]
-            th = (0.0, 0.005)[_ri(g, 0, 1)]
-            k = (-1, 60, 2000)[_ri(g, 0, 2)]
-            legacy = bool(_ri(g, 0, 1))
-            img = synthetic.synthetic_images(1, h, w, seed=800 + case)
-            size = None
-            if case % 2:
-                size = torch.tensor([[float(w - _ri(g, 0, 12)), float(h - _ri(g, 0, 10))]])
-            conf = dict(nms_radius=r, remove_borders=border, detection_threshold=th, max_num_keypoints=k, legacy_sampling=legacy)
-            m = ref["official"](**conf)
-            data = {"image": img} if size is None else {"image": img, "image_size": size}
-            p = m(data)
+        for case, img, size, conf in superpoint_official_cases():
+            h, w = img.shape[-2:]
             o = osp.extract(sd, img, "official", image_size=size, **conf)
-            assert torch.equal(p["keypoints"][0], o["keypoints"][0]), (case, conf, h, w, size)
+            key = f"official{case}"
+            assert torch.equal(_keypoints(g, key + "_keypoints"), o["keypoints"][0]), (case, conf, h, w, size)
             if len(o["keypoints"][0]):
-                assert (p["keypoint_scores"][0] - o["keypoint_scores"][0]).abs().max().item() <= 1e-6
-                assert (p["descriptors"][0] - o["descriptors"][0]).abs().max().item() <= 1e-5
+                assert (g[key + "_keypoint_scores"] - o["keypoint_scores"][0]).abs().max().item() <= 1e-6
+                _descriptors_close(g, key + "_descriptors", o["descriptors"][0], 1e-5)
             checked += 1
     assert checked == 10
 
 
-def test_lightglue_oracle_equals_reference_on_random_key_point_sets(ref):
+def test_lightglue_oracle_equals_reference_on_random_key_point_sets(golden):
+    from glue_factory_colon_amd import weights
     from oracle import lightglue as olg
 
-    g = torch.Generator().manual_seed(503)
-    sd = ref["weights"].lightglue_state_dict(0)
+    g = golden("reference_fuzz")
+    sd = weights.lightglue_state_dict(0)
     with torch.no_grad():
-        for case in range(8):
-            b = _ri(g, 1, 2)
-            m_, n_ = (_ri(g, 1, 6), _ri(g, 1, 6)) if case < 2 else (_ri(g, 20, 260), _ri(g, 20, 260))
-            th = (0.0, 0.1, 0.3)[_ri(g, 0, 2)]
-            size = torch.tensor([[float(_ri(g, 200, 700)), float(_ri(g, 150, 500))]] * b)
-            kp0, kp1 = torch.rand((b, m_, 2), generator=g) * size[:, None], torch.rand((b, n_, 2), generator=g) * size[:, None]
-            d0 = torch.nn.functional.normalize(torch.randn((b, m_, 256), generator=g), dim=-1)
-            d1 = torch.nn.functional.normalize(torch.randn((b, n_, 256), generator=g), dim=-1)
-            if case % 2:  # correlated descriptors: real matches
-                n_common = min(m_, n_)
-                d1[:, :n_common] = torch.nn.functional.normalize(d0[:, :n_common] + 0.1 * torch.randn((b, n_common, 256), generator=g), dim=-1)
-            model = ref["lg"](filter_threshold=th)
-            data = {"keypoints0": kp0, "keypoints1": kp1, "descriptors0": d0, "descriptors1": d1,
-                    "view0": {"image_size": size}, "view1": {"image_size": size}}
-            p = model(data)
+        for case, data, th in lightglue_cases():
+            kp0, kp1, d0, d1 = data["keypoints0"], data["keypoints1"], data["descriptors0"], data["descriptors1"]
+            size = data["view0"]["image_size"]
+            (b, m_), n_ = kp0.shape[:2], kp1.shape[1]
             o = olg.match(sd, kp0, kp1, d0, d1, size, size, filter_threshold=th)
-            assert torch.equal(p["matches0"], o["matches0"]) and torch.equal(p["matches1"], o["matches1"]), (case, m_, n_, th)
-            assert (p["matching_scores0"] - o["matching_scores0"]).abs().max().item() <= 5e-5  # (measured 1.1e-5; the path's bar is 1e-4)
-            la_p, la_o = p["log_assignment"], o["log_assignment"]
-            assert la_p.shape == la_o.shape == (b, m_ + 1, n_ + 1)
+            key = f"lg{case}"
+            assert torch.equal(g[key + "_matches0"], o["matches0"]) and torch.equal(g[key + "_matches1"], o["matches1"]), \
+                (case, m_, n_, th)
+            # (measured 1.1e-5; the path's bar is 1e-4)
+            assert (g[key + "_matching_scores0"] - o["matching_scores0"]).abs().max().item() <= 5e-5
+            la_o = o["log_assignment"]
+            assert g[key + "_log_assignment_shape"].tolist() == list(la_o.shape) == [b, m_ + 1, n_ + 1]
             # (the restatement and the reference associate the attention / soft-max sums differently: measured 1.9e-5)
-            assert ((la_p - la_o).abs() / (1 + la_o.abs())).max().item() <= 5e-5
-            assert (p["ref_descriptors0"] - o["ref_descriptors0"]).abs().max().item() <= 1e-4
+            _log_assignment_close(g, key + "_log_assignment", la_o.reshape(-1, n_ + 1), 5e-5)
+            for i in range(b):
+                _descriptors_close(g, f"{key}_{i}_ref_descriptors0", o["ref_descriptors0"][i].reshape(m_, -1), 1e-4)
 
 
-def test_host_side_restatements_against_the_reference(ref, tmp_path):
+def test_host_side_restatements_against_the_reference(golden):
     """Host logic restated in the package against the reference's own function on random inputs: the AUC of the
-    evaluation summaries (utils/tools.py:137-149).  (`read_homography`, datasets/hpatches.py:23-35, cannot be imported
-    here -- its module needs cv2 -- and is tested on files the test writes, tests/test_hpatches_reader.py.)"""
-    import numpy as np
-
-    sys.path.insert(0, os.path.join(HERE, "golden", "_standins"))
-    sys.path.insert(0, REF)
-    try:
-        from gluefactory.utils.tools import cal_error_auc as ref_auc
-    finally:
-        sys.path.remove(REF)
-        sys.path.remove(os.path.join(HERE, "golden", "_standins"))
+    evaluation summaries (utils/tools.py:137-149).  (`read_homography`, datasets/hpatches.py:23-35, is tested on files
+    the test writes, tests/test_hpatches_reader.py.)"""
     from glue_factory_colon_amd.eval_hpatches import cal_error_auc
 
-    rng = np.random.default_rng(3)
-    for n in (1, 2, 7, 540):
-        errors = (rng.gamma(1.5, 2.0, n)).tolist()
-        if n == 540:
-            errors[5] = float("inf")  # a pair with fewer than four matches (eval/utils.py:289-291)
-            errors[9] = 3.0           # exactly on a threshold
-        for ths in ([1, 3, 5], [5, 10, 20]):
-            assert [float(a) for a in cal_error_auc(errors, ths)] == [float(a) for a in ref_auc(errors, ths)], (n, ths)
+    g = golden("reference_fuzz")
+    for n, errors, ths in auc_cases():
+        assert [float(a) for a in cal_error_auc(errors, ths)] == g[f"auc{n}_{ths[0]}"].tolist(), (n, ths)
