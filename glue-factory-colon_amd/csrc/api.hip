@@ -1,6 +1,8 @@
 // Host-side orchestration behind the C ABI: which kernels run, in which order, on which slices of
 // the caller's workspace.  No allocation, no synchronisation: everything is enqueued on the
 // caller's stream (graph-capturable).
+#include <climits>
+
 #include "common.h"
 
 // from the other translation units
@@ -8,8 +10,6 @@ int gfc_rgb_to_gray(const float* img, float* out, int B, int H, int W, hipStream
 int gfc_det_head_softmax_d2s(const float* hidden, int lda, const float* wp, const float* bias, const float* scale,
                              const float* shift, int B, int h8, int w8, float* heat, hipStream_t st);
 int gfc_rowdot256(const float* x, int ld, int rows, const float* w, const float* bias, float* z, hipStream_t st);
-int gfc_assign_inplace(float* scores, const float* z0, const float* z1, int B, int M, int N, float* stats,
-                       hipStream_t st);
 size_t gfc_assign_tail_bytes(int B, int M, int N);
 int gfc_assign_filter_fused(float* scores, const float* z0, const float* z1, int B, int M, int N, float threshold,
                             int64_t* m0, int64_t* m1, float* ms0, float* ms1, float* stats, void* tail,
@@ -216,50 +216,104 @@ extern "C" int gfc_sp_dense(const gfc_sp_params* p, const float* image, int B, i
 // ---------------------------------------------------------------------------------------------
 // LightGlue forward
 // ---------------------------------------------------------------------------------------------
-struct LgPlan {
-  size_t R;
-  size_t x, qkv, msg, cosb, sinb, csb, tables, total;
-};
-
 extern "C" size_t gfc_lg_layer_workspace_bytes(int rows);
 extern "C" size_t gfc_lg_assign_workspace_bytes(int B, int M, int N);
 
-// packed = the caller owns the row buffer x and hands over packed key points (gfc_lg_forward_packed): no x / msg slots
-static LgPlan lg_plan(int B, int M, int N, bool packed = false) {
-  LgPlan p;
-  p.R = (size_t)B * (M + N);
+// A batch of B pairs in GROUPS = maximal runs of consecutive pairs with equal (m, n).  Rows: group after group, inside
+// a group the side-0 rows of its pairs (pair-major) followed by their side-1 rows.  A uniform batch is one group.
+struct LgGroup {
+  int first, count, m, n, row0;  // first pair, pairs, key points per side, first row
+};
+struct LgGroups {  // by value to the tables kernel: 2.5 KB of kernel arguments
+  LgGroup g[GFC_LG_MAX_RAGGED_PAIRS];
+};
+struct LgBatch {
+  int B, groups, R, maxn;
+  LgGroups tab;
+  size_t stage;  // one layer's workspace, re-used by every group's assignment head afterwards
+  size_t qkv, cosb, sinb, csb, tables, total;  // workspace slots
+};
+
+// rows and workspace of the groups in b.tab; false for a non-positive count, or when row offsets x 768 columns would
+// leave the int arithmetic of the kernels
+static bool lg_layout(LgBatch& b) {
+  long long R = 0;
+  size_t asg = 0;
+  b.maxn = 0;
+  for (int i = 0; i < b.groups; ++i) {
+    LgGroup& g = b.tab.g[i];
+    if (g.count <= 0 || g.m <= 0 || g.n <= 0) return false;
+    g.row0 = (int)R;
+    R += (long long)g.count * ((long long)g.m + g.n);
+    if (R > INT_MAX / 768) return false;
+    if (g.m > b.maxn) b.maxn = g.m;
+    if (g.n > b.maxn) b.maxn = g.n;
+    const size_t a = gfc_lg_assign_workspace_bytes(g.count, g.m, g.n);
+    if (a > asg) asg = a;
+  }
+  b.R = (int)R;
+  b.stage = gfc_lg_layer_workspace_bytes(b.R);
+  if (asg > b.stage) b.stage = asg;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += gfc_align(bytes); return o; };
-  p.x = packed ? 0 : take(p.R * 256 * 4);
-  // stage scratch: one layer's workspace, re-used by the assignment head afterwards
-  size_t stage = gfc_lg_layer_workspace_bytes((int)p.R);
-  const size_t asg = gfc_lg_assign_workspace_bytes(B, M, N);
-  if (asg > stage) stage = asg;
-  p.qkv = take(stage);
-  p.msg = packed ? 0 : take(p.R * 4 * 4);  // packed key points [R][2] (+ scales / orientations [R][2]) for the rotary tables
-  p.cosb = take(p.R * 64 * 4);
-  p.sinb = take(p.R * 64 * 4);
-  p.csb = take(p.R * 64 * 4);  // the same values packed (cos, sin) per frequency: what the QKV epilogue reads
-  p.tables = take((size_t)B * (2 * 4 * 2 + 2 + 2 + 4) * 4 + 256);
-  p.total = off;
-  return p;
+  b.qkv = take(b.stage);
+  b.cosb = take(R * 64 * 4);
+  b.sinb = take(R * 64 * 4);
+  b.csb = take(R * 64 * 4);  // the same values packed (cos, sin) per frequency: what the QKV epilogue reads
+  b.tables = take((size_t)b.B * (2 * 4 * 2 + 2 + 2 + 4) * 4 + 256);
+  b.total = off;
+  return true;
 }
+
+// B equal pairs: one group, any B
+static bool lg_uniform(int B, int M, int N, LgBatch& b) {
+  b = LgBatch{};
+  b.B = B; b.groups = 1;
+  b.tab.g[0] = {0, B, M, N, 0};
+  return lg_layout(b);
+}
+
+// B <= GFC_LG_MAX_RAGGED_PAIRS pairs with their own (m[i], n[i])
+static bool lg_ragged(int B, const int32_t* m, const int32_t* n, LgBatch& b) {
+  if (B <= 0 || B > GFC_LG_MAX_RAGGED_PAIRS || !m || !n) return false;
+  b = LgBatch{};
+  b.B = B;
+  for (int i = 0; i < B;) {
+    int j = i + 1;
+    while (j < B && m[j] == m[i] && n[j] == n[i]) ++j;
+    b.tab.g[b.groups++] = {i, j - i, m[i], n[i], 0};
+    i = j;
+  }
+  return lg_layout(b);
+}
+
+// gfc_lg_forward stages its separate arrays in front of the batch's workspace: x [R,256] | kp [R,2] + so [R,2]
+static size_t lg_staging_bytes(const LgBatch& b) { return gfc_align((size_t)b.R * 256 * 4) + gfc_align((size_t)b.R * 4 * 4); }
 
 extern "C" size_t gfc_lg_workspace_bytes(int B, int M, int N) {
-  if (B <= 0 || M <= 0 || N <= 0) return 0;
-  return lg_plan(B, M, N).total;
+  LgBatch b;
+  return lg_uniform(B, M, N, b) ? lg_staging_bytes(b) + b.total : 0;
 }
 extern "C" size_t gfc_lg_packed_workspace_bytes(int B, int M, int N) {
-  if (B <= 0 || M <= 0 || N <= 0) return 0;
-  return lg_plan(B, M, N, true).total;
+  LgBatch b;
+  return lg_uniform(B, M, N, b) ? b.total : 0;
+}
+extern "C" size_t gfc_lg_ragged_workspace_bytes(int B, const int32_t* m, const int32_t* n) {
+  LgBatch b;
+  return lg_ragged(B, m, n, b) ? b.total : 0;
 }
 
-// tables: self problems [2B][4], cross problems [2B][4], row0 [2B], n [2B], sizes [2B][2]
-__global__ void lg_tables_kernel(int B, int M, int N, const float* size0, const float* size1, int* self_p,
+// tables: self problems [2B][4], cross problems [2B][4], row0 [2B], n [2B], sizes [2B][2]; problem b = side 0 of
+// pair b, B + b = side 1
+__global__ void lg_tables_kernel(LgGroups t, int groups, int B, const float* size0, const float* size1, int* self_p,
                                  int* cross_p, int* row0, int* nrow, float* sizes) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const int r0 = b * M, r1 = B * M + b * N;
+  int gi = 0;
+  while (gi + 1 < groups && b >= t.g[gi + 1].first) ++gi;
+  const LgGroup g = t.g[gi];
+  const int M = g.m, N = g.n, k = b - g.first;
+  const int r0 = g.row0 + k * M, r1 = g.row0 + g.count * M + k * N;
   int* s = self_p + 4 * b;
   s[0] = r0; s[1] = M; s[2] = r0; s[3] = M;
   s = self_p + 4 * (B + b);
@@ -400,12 +454,11 @@ extern "C" int gfc_lg_rowdot(const float* x, int ld, int rows, const float* w, c
   return GFC_OK;
 }
 
-// workspace of the assignment head: md [R,256] | z [R] | stats | filter scratch
+// workspace of the assignment head: md [R,256] | z [R] | stats | two-pass tail scratch
 extern "C" size_t gfc_lg_assign_workspace_bytes(int B, int M, int N) {
   if (B <= 0 || M <= 0 || N <= 0) return 0;
   const size_t R = (size_t)B * (M + N);
-  return gfc_align(R * 256 * 4) + gfc_align(R * 4) + gfc_align(2 * R * 4) + gfc_align(R * 8) +
-         gfc_assign_tail_bytes(B, M, N);
+  return gfc_align(R * 256 * 4) + gfc_align(R * 4) + gfc_align(2 * R * 4) + gfc_assign_tail_bytes(B, M, N);
 }
 
 // MatchAssignment of layer l + filter_matches (lightglue.py:279-288,294-319).  x0 [B*M,256], x1 [B*N,256].
@@ -423,8 +476,7 @@ extern "C" int gfc_lg_assign(const gfc_lg_params* p, int l, const float* x0, con
   float* md = (float*)base;
   float* z = (float*)(base + gfc_align(R * 256 * 4));
   float* stats = (float*)((char*)z + gfc_align(R * 4));
-  void* filt = (char*)stats + gfc_align(2 * R * 4);
-  void* tail = (char*)filt + gfc_align(R * 8);
+  void* tail = (char*)stats + gfc_align(2 * R * 4);
   float* md1 = md + (size_t)R0 * D;
   GFC_TRY(gfc_linear(x0, D, D, nullptr, 0, 0, p->final_proj_w[l], D, p->final_proj_b[l], nullptr, nullptr, 0.25f,
                      nullptr, nullptr, nullptr, 0, md, D, R0, D, st));
@@ -434,36 +486,33 @@ extern "C" int gfc_lg_assign(const gfc_lg_params* p, int l, const float* x0, con
   GFC_TRY(gfc_rowdot256(x1, D, R1, p->matchability_w[l], p->matchability_b[l], z + R0, st));
   GFC_TRY(gfc_batched_nt(md, D, (long long)M * D, md1, D, (long long)N * D, log_assignment, N + 1,
                          (long long)(M + 1) * (N + 1), M, N, D, B, st));
-  if (gfc_knobs().assign_mode != 1)  // default: statistics in one sweep, final scores + arg-max in a second one
-    return gfc_assign_filter_fused(log_assignment, z, z + R0, B, M, N, threshold, m0, m1, ms0, ms1, stats, tail, st);
-  GFC_TRY(gfc_assign_inplace(log_assignment, z, z + R0, B, M, N, stats, st));
-  GFC_TRY(gfc_lg_filter_matches(log_assignment, B, M, N, threshold, m0, m1, ms0, ms1, filt, (size_t)B * (M + N) * 8,
-                                st));
-  return GFC_OK;
+  // statistics in one sweep, final scores + arg-max in a second one
+  return gfc_assign_filter_fused(log_assignment, z, z + R0, B, M, N, threshold, m0, m1, ms0, ms1, stats, tail, st);
 }
 
-// Common body.  kp [R,2] / so [R,2] (nullable) / desc [R,Din]: rows of side 0 first, then side 1 (packed).
-// x [R,256]: the row buffer every layer updates in place; it ends up holding the last layer's descriptors.
-static int lg_forward_core(const gfc_lg_params* p, const float* kp, const float* so, const float* desc, const float* size0,
-                           const float* size1, int B, int M, int N, float threshold, int64_t* m0, int64_t* m1, float* ms0,
-                           float* ms1, float* log_assignment, float* x, char* base, const LgPlan& pl, gfc_trace* tr,
+// The matcher over a batch: tables -> rotary tables -> input_proj -> n_layers x layer -> one assignment head + filter
+// per group.  kp [R,2] / so [R,2] (nullable) / desc [R,Din] in the batch's row order; desc == NULL: the rows are
+// already in x.  x [R,256]: the row buffer every layer updates in place; it ends up holding the last layer's
+// descriptors.  Outputs are flat in pair order (one group: exactly the [B,M] / [B,N] / [B,M+1,N+1] arrays).
+static int lg_forward_core(const gfc_lg_params* p, const LgBatch& bt, const float* kp, const float* so, const float* desc,
+                           const float* size0, const float* size1, float threshold, int64_t* m0, int64_t* m1,
+                           float* ms0, float* ms1, float* log_assignment, float* x, char* base, gfc_trace* tr,
                            hipStream_t st) {
-  float* cosb = (float*)(base + pl.cosb);
-  float* sinb = (float*)(base + pl.sinb);
-  float* csb = (float*)(base + pl.csb);
-  int* self_p = (int*)(base + pl.tables);
+  const int B = bt.B, R = bt.R, D = 256;
+  float* cosb = (float*)(base + bt.cosb);
+  float* sinb = (float*)(base + bt.sinb);
+  float* csb = (float*)(base + bt.csb);
+  int* self_p = (int*)(base + bt.tables);
   int* cross_p = self_p + 8 * B;
   int* row0 = cross_p + 8 * B;
   int* nrow = row0 + 2 * B;
   float* sizes = (float*)(nrow + 2 * B);
-  const int R = (int)pl.R, R0 = B * M;
-  const int D = 256;
   const int pdim = p->posenc_dim == 0 ? 2 : p->posenc_dim;
 
-  hipLaunchKernelGGL(lg_tables_kernel, dim3((B + 63) / 64), dim3(64), 0, st, B, M, N, size0, size1, self_p, cross_p,
-                     row0, nrow, sizes);
+  hipLaunchKernelGGL(lg_tables_kernel, dim3((B + 63) / 64), dim3(64), 0, st, bt.tab, bt.groups, B, size0, size1, self_p,
+                     cross_p, row0, nrow, sizes);
   GFC_LAUNCH_CHECK();
-  GFC_TRY(gfc_lg_posenc_packed(kp, so, sizes, row0, nrow, 2 * B, M > N ? M : N, p->posenc_wr, pdim, cosb, sinb, csb, st));
+  GFC_TRY(gfc_lg_posenc_packed(kp, so, sizes, row0, nrow, 2 * B, bt.maxn, p->posenc_wr, pdim, cosb, sinb, csb, st));
 
   // descriptors -> rows.  input_dim == 256: layer 0's self block reads them where they are (no copy);
   // otherwise input_proj writes the rows (lightglue.py:352-355,464-465)
@@ -474,22 +523,28 @@ static int lg_forward_core(const gfc_lg_params* p, const float* kp, const float*
                        nullptr, nullptr, nullptr, 0, x, D, R, D, st));
     x_in = nullptr;
   }
-  const int maxn = M > N ? M : N;
   for (int l = 0; l < p->n_layers; ++l)
-    GFC_TRY(lg_layer_impl(p, l, x, cosb, sinb, csb, R, self_p, cross_p, 2 * B, maxn, base + pl.qkv,
-                          gfc_lg_layer_workspace_bytes(R), st, l == 0 ? x_in : nullptr, tr));
+    GFC_TRY(lg_layer_impl(p, l, x, cosb, sinb, csb, R, self_p, cross_p, 2 * B, bt.maxn, base + bt.qkv, bt.stage, st,
+                          l == 0 ? x_in : nullptr, tr));
 
-  // ---- assignment (lightglue.py:279-288) + filter (lightglue.py:294-319) ----
-  return gfc_lg_assign(p, p->n_layers - 1, x, x + (size_t)R0 * D, B, M, N, threshold, m0, m1, ms0, ms1, log_assignment,
-                       base + pl.qkv, gfc_lg_assign_workspace_bytes(B, M, N), st);
+  // ---- assignment (lightglue.py:279-288) + filter (lightglue.py:294-319), one batched call per group ----
+  size_t o0 = 0, o1 = 0, os = 0;
+  for (int i = 0; i < bt.groups; ++i) {
+    const LgGroup& g = bt.tab.g[i];
+    const float* x0 = x + (size_t)g.row0 * D;
+    const float* x1 = x0 + (size_t)g.count * g.m * D;
+    GFC_TRY(gfc_lg_assign(p, p->n_layers - 1, x0, x1, g.count, g.m, g.n, threshold, m0 + o0, m1 + o1, ms0 + o0,
+                          ms1 + o1, log_assignment + os, base + bt.qkv, bt.stage, st));
+    o0 += (size_t)g.count * g.m; o1 += (size_t)g.count * g.n; os += (size_t)g.count * (g.m + 1) * (g.n + 1);
+  }
+  return GFC_OK;
 }
 
-static int lg_forward_args_ok(const gfc_lg_params* p, int B, int M, int N, bool has_so) {
-  if (B <= 0 || M <= 0 || N <= 0 || p->n_layers <= 0 || p->n_layers > GFC_LG_MAX_LAYERS) return 0;
-  if (p->input_dim != 256 && (!p->input_proj_w || !p->input_proj_b || p->input_dim % 32)) return 0;
+static bool lg_params_ok(const gfc_lg_params* p, bool has_so) {
+  if (p->n_layers <= 0 || p->n_layers > GFC_LG_MAX_LAYERS) return false;
+  if (p->input_dim != 256 && (!p->input_proj_w || !p->input_proj_b || p->input_dim % 32)) return false;
   const int pdim = p->posenc_dim == 0 ? 2 : p->posenc_dim;
-  if ((pdim != 2 && pdim != 4) || ((pdim == 4) != has_so)) return 0;
-  return 1;
+  return (pdim == 2 || pdim == 4) && (pdim == 4) == has_so;
 }
 
 extern "C" int gfc_lg_forward_packed(const gfc_lg_params* p, const float* kpts, const float* desc, const float* size0,
@@ -498,94 +553,12 @@ extern "C" int gfc_lg_forward_packed(const gfc_lg_params* p, const float* kpts, 
                                      void* ws, size_t ws_bytes, gfc_trace* attention_trace, void* stream) {
   if (!p || !kpts || !desc || !size0 || !size1 || !m0 || !m1 || !ms0 || !ms1 || !log_assignment || !rows || !ws)
     return GFC_ERR_INVALID;
-  if (!lg_forward_args_ok(p, B, M, N, scale_ori != nullptr)) return GFC_ERR_INVALID;
+  LgBatch bt;
+  if (!lg_params_ok(p, scale_ori != nullptr) || !lg_uniform(B, M, N, bt)) return GFC_ERR_INVALID;
   if (rows == desc) return GFC_ERR_INVALID;  // the caller's descriptors are read-only
-  if (ws_bytes < gfc_lg_packed_workspace_bytes(B, M, N)) return GFC_ERR_WORKSPACE;
-  const LgPlan pl = lg_plan(B, M, N, true);
-  return lg_forward_core(p, kpts, scale_ori, desc, size0, size1, B, M, N, threshold, m0, m1, ms0, ms1, log_assignment,
-                         rows, (char*)ws, pl, attention_trace, (hipStream_t)stream);
-}
-
-// ---- ragged batch: B pairs with their own (m, n) ----
-struct LgRaggedTab {
-  int r0[GFC_LG_MAX_RAGGED_PAIRS], r1[GFC_LG_MAX_RAGGED_PAIRS], m[GFC_LG_MAX_RAGGED_PAIRS], n[GFC_LG_MAX_RAGGED_PAIRS];
-};
-struct LgRaggedPlan {
-  LgRaggedTab tab;
-  int groups, g_first[GFC_LG_MAX_RAGGED_PAIRS], g_count[GFC_LG_MAX_RAGGED_PAIRS];
-  long long R, sum_m, sum_n;
-  int maxn;
-  size_t stage;
-  LgPlan pl;
-};
-
-// rows of a group: side 0 of its pairs, then side 1 (the layout of gfc_lg_forward_packed per group)
-static bool lg_ragged_plan(int B, const int32_t* m, const int32_t* n, LgRaggedPlan& rp) {
-  if (B <= 0 || B > GFC_LG_MAX_RAGGED_PAIRS || !m || !n) return false;
-  rp.groups = 0; rp.R = 0; rp.sum_m = 0; rp.sum_n = 0; rp.maxn = 0;
-  size_t asg = 0;
-  for (int i = 0; i < B;) {
-    if (m[i] <= 0 || n[i] <= 0) return false;
-    int j = i;
-    while (j < B && m[j] == m[i] && n[j] == n[i]) ++j;
-    const int cnt = j - i;
-    rp.g_first[rp.groups] = i; rp.g_count[rp.groups] = cnt; ++rp.groups;
-    for (int k = i; k < j; ++k) {
-      rp.tab.m[k] = m[i]; rp.tab.n[k] = n[i];
-      rp.tab.r0[k] = (int)(rp.R + (long long)(k - i) * m[i]);
-      rp.tab.r1[k] = (int)(rp.R + (long long)cnt * m[i] + (long long)(k - i) * n[i]);
-    }
-    rp.R += (long long)cnt * (m[i] + n[i]);
-    rp.sum_m += (long long)cnt * m[i]; rp.sum_n += (long long)cnt * n[i];
-    if (m[i] > rp.maxn) rp.maxn = m[i];
-    if (n[i] > rp.maxn) rp.maxn = n[i];
-    const size_t a = gfc_lg_assign_workspace_bytes(cnt, m[i], n[i]);
-    if (a > asg) asg = a;
-    i = j;
-  }
-  if (rp.R > 0x7fffffffLL / 768) return false;  // row offsets x 768 columns stay inside int arithmetic of the kernels
-  for (int k = B; k < GFC_LG_MAX_RAGGED_PAIRS; ++k) rp.tab.m[k] = rp.tab.n[k] = rp.tab.r0[k] = rp.tab.r1[k] = 0;
-  // workspace: the packed plan's slots with R rows, B pairs, and the stage scratch large enough for every group's head
-  LgPlan& pl = rp.pl;
-  pl.R = (size_t)rp.R;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += gfc_align(bytes); return o; };
-  pl.x = 0; pl.msg = 0;
-  size_t stage = gfc_lg_layer_workspace_bytes((int)rp.R);
-  if (asg > stage) stage = asg;
-  rp.stage = stage;
-  pl.qkv = take(stage);
-  pl.cosb = take(pl.R * 64 * 4);
-  pl.sinb = take(pl.R * 64 * 4);
-  pl.csb = take(pl.R * 64 * 4);
-  pl.tables = take((size_t)B * (2 * 4 * 2 + 2 + 2 + 4) * 4 + 256);
-  pl.total = off;
-  return true;
-}
-
-extern "C" size_t gfc_lg_ragged_workspace_bytes(int B, const int32_t* m, const int32_t* n) {
-  LgRaggedPlan rp;
-  return lg_ragged_plan(B, m, n, rp) ? rp.pl.total : 0;
-}
-
-// the tables of lg_tables_kernel for per-pair counts (same slots: problem b = side 0 of pair b, B + b = side 1)
-__global__ void lg_ragged_tables_kernel(LgRaggedTab t, int B, const float* size0, const float* size1, int* self_p,
-                                        int* cross_p, int* row0, int* nrow, float* sizes) {
-  int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const int r0 = t.r0[b], r1 = t.r1[b], M = t.m[b], N = t.n[b];
-  int* s = self_p + 4 * b;
-  s[0] = r0; s[1] = M; s[2] = r0; s[3] = M;
-  s = self_p + 4 * (B + b);
-  s[0] = r1; s[1] = N; s[2] = r1; s[3] = N;
-  int* c = cross_p + 4 * b;
-  c[0] = r0; c[1] = M; c[2] = r1; c[3] = N;
-  c = cross_p + 4 * (B + b);
-  c[0] = r1; c[1] = N; c[2] = r0; c[3] = M;
-  row0[b] = r0; nrow[b] = M;
-  row0[B + b] = r1; nrow[B + b] = N;
-  sizes[2 * b] = size0[2 * b]; sizes[2 * b + 1] = size0[2 * b + 1];
-  sizes[2 * (B + b)] = size1[2 * b]; sizes[2 * (B + b) + 1] = size1[2 * b + 1];
+  if (ws_bytes < bt.total) return GFC_ERR_WORKSPACE;
+  return lg_forward_core(p, bt, kpts, scale_ori, desc, size0, size1, threshold, m0, m1, ms0, ms1, log_assignment, rows,
+                         (char*)ws, attention_trace, (hipStream_t)stream);
 }
 
 extern "C" int gfc_lg_forward_ragged(const gfc_lg_params* p, const float* kpts, const float* desc, const float* size0,
@@ -595,49 +568,12 @@ extern "C" int gfc_lg_forward_ragged(const gfc_lg_params* p, const float* kpts, 
                                      gfc_trace* attention_trace, void* stream) {
   if (!p || !kpts || !desc || !size0 || !size1 || !m0 || !m1 || !ms0 || !ms1 || !log_assignment || !rows || !ws)
     return GFC_ERR_INVALID;
-  LgRaggedPlan rp;
-  if (!lg_ragged_plan(B, m, n, rp)) return GFC_ERR_INVALID;
-  if (!lg_forward_args_ok(p, B, rp.maxn, rp.maxn, scale_ori != nullptr)) return GFC_ERR_INVALID;
+  LgBatch bt;
+  if (!lg_ragged(B, m, n, bt) || !lg_params_ok(p, scale_ori != nullptr)) return GFC_ERR_INVALID;
   if (rows == desc) return GFC_ERR_INVALID;  // the caller's descriptors are read-only
-  if (ws_bytes < rp.pl.total) return GFC_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const LgPlan& pl = rp.pl;
-  char* base = (char*)ws;
-  float* cosb = (float*)(base + pl.cosb);
-  float* sinb = (float*)(base + pl.sinb);
-  float* csb = (float*)(base + pl.csb);
-  int* self_p = (int*)(base + pl.tables);
-  int* cross_p = self_p + 8 * B;
-  int* row0 = cross_p + 8 * B;
-  int* nrow = row0 + 2 * B;
-  float* sizes = (float*)(nrow + 2 * B);
-  const int R = (int)pl.R, D = 256;
-  const int pdim = p->posenc_dim == 0 ? 2 : p->posenc_dim;
-  hipLaunchKernelGGL(lg_ragged_tables_kernel, dim3((B + 63) / 64), dim3(64), 0, st, rp.tab, B, size0, size1, self_p,
-                     cross_p, row0, nrow, sizes);
-  GFC_LAUNCH_CHECK();
-  GFC_TRY(gfc_lg_posenc_packed(kpts, scale_ori, sizes, row0, nrow, 2 * B, rp.maxn, p->posenc_wr, pdim, cosb, sinb, csb, st));
-  const float* x_in = desc;
-  if (p->input_dim != D) {
-    const int Din = p->input_dim;
-    GFC_TRY(gfc_linear(desc, Din, Din, nullptr, 0, 0, p->input_proj_w, Din, p->input_proj_b, nullptr, nullptr, 1.f,
-                       nullptr, nullptr, nullptr, 0, rows, D, R, D, st));
-    x_in = nullptr;
-  }
-  for (int l = 0; l < p->n_layers; ++l)
-    GFC_TRY(lg_layer_impl(p, l, rows, cosb, sinb, csb, R, self_p, cross_p, 2 * B, rp.maxn, base + pl.qkv,
-                          gfc_lg_layer_workspace_bytes(R), st, l == 0 ? x_in : nullptr, attention_trace));
-  // assignment + filter, one batched call per group of equal-shape pairs (outputs are flat in pair order)
-  size_t o0 = 0, o1 = 0, os = 0;
-  for (int g = 0; g < rp.groups; ++g) {
-    const int i = rp.g_first[g], cnt = rp.g_count[g], M = rp.tab.m[i], N = rp.tab.n[i];
-    const float* x0 = rows + (size_t)rp.tab.r0[i] * D;
-    const float* x1 = rows + (size_t)rp.tab.r1[i] * D;
-    GFC_TRY(gfc_lg_assign(p, p->n_layers - 1, x0, x1, cnt, M, N, threshold, m0 + o0, m1 + o1, ms0 + o0, ms1 + o1,
-                          log_assignment + os, base + pl.qkv, rp.stage, st));
-    o0 += (size_t)cnt * M; o1 += (size_t)cnt * N; os += (size_t)cnt * (M + 1) * (N + 1);
-  }
-  return GFC_OK;
+  if (ws_bytes < bt.total) return GFC_ERR_WORKSPACE;
+  return lg_forward_core(p, bt, kpts, scale_ori, desc, size0, size1, threshold, m0, m1, ms0, ms1, log_assignment, rows,
+                         (char*)ws, attention_trace, (hipStream_t)stream);
 }
 
 extern "C" int gfc_lg_forward(const gfc_lg_params* p, const float* kpts0, const float* kpts1, const float* desc0,
@@ -649,25 +585,26 @@ extern "C" int gfc_lg_forward(const gfc_lg_params* p, const float* kpts0, const 
   if (!p || !kpts0 || !kpts1 || !desc0 || !desc1 || !size0 || !size1 || !m0 || !m1 || !ms0 || !ms1 ||
       !log_assignment || !ws)
     return GFC_ERR_INVALID;
-  if (!lg_forward_args_ok(p, B, M, N, scale_ori0 != nullptr && scale_ori1 != nullptr)) return GFC_ERR_INVALID;
+  LgBatch bt;
+  if (!lg_params_ok(p, scale_ori0 != nullptr && scale_ori1 != nullptr) || !lg_uniform(B, M, N, bt))
+    return GFC_ERR_INVALID;
   if ((scale_ori0 != nullptr) != (scale_ori1 != nullptr)) return GFC_ERR_INVALID;
-  if (ws_bytes < gfc_lg_workspace_bytes(B, M, N)) return GFC_ERR_WORKSPACE;
+  const size_t staging = lg_staging_bytes(bt);
+  if (ws_bytes < staging + bt.total) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const LgPlan pl = lg_plan(B, M, N);
-  char* base = (char*)ws;
-  float* x = (float*)(base + pl.x);
-  float* msg = (float*)(base + pl.msg);
+  float* x = (float*)ws;
+  float* kp = (float*)((char*)ws + gfc_align((size_t)bt.R * 256 * 4));
+  char* base = (char*)ws + staging;  // the batch's own workspace
   const int R0 = B * M, R1 = B * N;
-  const size_t R = pl.R;
   const int Din = p->input_dim;
   auto d2d = [&](void* dst, const void* src, size_t bytes) {
     return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
   };
   // the two sides arrive as separate arrays: pack key points (and scales / orientations) behind each other
-  if (!d2d(msg, kpts0, (size_t)R0 * 2 * 4) || !d2d(msg + (size_t)R0 * 2, kpts1, (size_t)R1 * 2 * 4)) return GFC_ERR_LAUNCH;
+  if (!d2d(kp, kpts0, (size_t)R0 * 2 * 4) || !d2d(kp + (size_t)R0 * 2, kpts1, (size_t)R1 * 2 * 4)) return GFC_ERR_LAUNCH;
   float* so = nullptr;
   if (scale_ori0) {
-    so = msg + R * 2;
+    so = kp + (size_t)bt.R * 2;
     if (!d2d(so, scale_ori0, (size_t)R0 * 2 * 4) || !d2d(so + (size_t)R0 * 2, scale_ori1, (size_t)R1 * 2 * 4))
       return GFC_ERR_LAUNCH;
   }
@@ -675,14 +612,14 @@ extern "C" int gfc_lg_forward(const gfc_lg_params* p, const float* kpts0, const 
   // memory -- read in place; with an input projection the packed copy lives in the (not yet used) layer scratch
   const float* desc = desc0;
   if (desc1 != desc0 + (size_t)R0 * Din) {
-    float* stage = Din == 256 ? x : (float*)(base + pl.qkv);
+    float* stage = Din == 256 ? x : (float*)(base + bt.qkv);
     if (!d2d(stage, desc0, (size_t)R0 * Din * 4) || !d2d(stage + (size_t)R0 * Din, desc1, (size_t)R1 * Din * 4))
       return GFC_ERR_LAUNCH;
     desc = stage;
   }
   // (desc == x is fine here: layer 0 then simply works in place)
-  GFC_TRY(lg_forward_core(p, msg, so, desc == x ? nullptr : desc, size0, size1, B, M, N, threshold, m0, m1, ms0, ms1,
-                          log_assignment, x, base, pl, nullptr, st));
+  GFC_TRY(lg_forward_core(p, bt, kp, so, desc == x ? nullptr : desc, size0, size1, threshold, m0, m1, ms0, ms1,
+                          log_assignment, x, base, nullptr, st));
   if (ref_desc0 && !d2d(ref_desc0, x, (size_t)R0 * 256 * 4)) return GFC_ERR_LAUNCH;
   if (ref_desc1 && !d2d(ref_desc1, x + (size_t)R0 * 256, (size_t)R1 * 256 * 4)) return GFC_ERR_LAUNCH;
   return GFC_OK;

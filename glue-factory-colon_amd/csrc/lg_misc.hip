@@ -208,8 +208,8 @@ __global__ __launch_bounds__(256) void assign_finalize_kernel(const float* __res
 // Two-pass tail of the assignment head (lightglue.py:257-269 + the arg-max half of :294-319): the
 // [B,M,N] similarity block is read ONCE for the row and column soft-max statistics and once more for the final
 // scores, which are written in place together with the row / column arg-max of the finished matrix.
-// HBM traffic: 1 read + (1 read + 1 write) of the matrix; the five-pass form above (kept for
-// gfc_lg_log_assignment / gfc_nn_match and behind GFC_ASSIGN_MODE=1) moved ~8.4x the matrix
+// HBM traffic: 1 read + (1 read + 1 write) of the matrix; the five-pass form above (kept for the stage-isolated
+// gfc_lg_log_assignment / gfc_lg_filter_matches and for gfc_nn_match) moved ~8.4x the matrix
 // (profiles/r01_pmc_summary.json: strided column walks read it twice each).
 //
 // Workgroup = one band of AS_RB rows of one pair, 4 waves; a wave walks whole rows with its lanes along the
@@ -444,8 +444,6 @@ __global__ void assign_colarg_merge_kernel(const float* __restrict__ cpart_v, co
   col_arg[(size_t)b * N + j] = ix;
 }
 
-// In-place variant used by gfc_lg_forward: sim was written by the GEMM straight into the inner block of
-// the [M+1][N+1] output (ld = N+1).
 // scratch of the two-pass tail behind `stats`: column partials of both passes, row / column arg-max
 size_t gfc_assign_tail_bytes(int B, int M, int N) {
   const size_t nb = (size_t)(M + AS_RB - 1) / AS_RB;
@@ -479,21 +477,6 @@ int gfc_assign_filter_fused(float* scores, const float* z0, const float* z1, int
   const int mn = M > N ? M : N;
   hipLaunchKernelGGL(mutual_kernel, dim3((mn + 255) / 256, B), dim3(256), 0, st, rbest, rarg, carg, M, N, threshold,
                      (long long*)m0, (long long*)m1, ms0, ms1);
-  GFC_LAUNCH_CHECK();
-  return GFC_OK;
-}
-
-int gfc_assign_inplace(float* scores, const float* z0, const float* z1, int B, int M, int N, float* stats,
-                       hipStream_t st) {
-  float* rmax = stats;
-  float* rlog = rmax + (size_t)B * M;
-  float* cmax = rlog + (size_t)B * M;
-  float* clog = cmax + (size_t)B * N;
-  const long long sb = (long long)(M + 1) * (N + 1);
-  hipLaunchKernelGGL(lse_rows_kernel, dim3((M + 3) / 4, B), dim3(256), 0, st, scores, sb, N + 1, M, N, rmax, rlog);
-  hipLaunchKernelGGL(lse_cols_kernel, dim3((N + 31) / 32, B), dim3(256), 0, st, scores, sb, N + 1, M, N, cmax, clog);
-  hipLaunchKernelGGL(assign_finalize_kernel, dim3((N + 1 + 255) / 256, M + 1, B), dim3(256), 0, st, scores, sb, N + 1,
-                     z0, z1, M, N, rmax, rlog, cmax, clog, scores);
   GFC_LAUNCH_CHECK();
   return GFC_OK;
 }

@@ -11,6 +11,7 @@ sub-modules are parameter containers only; the forward pass is one call into lib
     model.matcher.name = glue_factory_colon_amd.lightglue
 """
 import ctypes
+import itertools
 import sys
 import threading
 from pathlib import Path
@@ -84,6 +85,17 @@ def _pack_sides(a, b):
             and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()):
         return a.as_strided((ra + rb, c), (c, 1))
     return torch.cat([a.reshape(ra, c), b.reshape(rb, c)], 0)
+
+
+def _image_size(data, side):
+    """`view{side}.image_size` like the reference (lightglue.py:430-434); a view without one normalises by the extent
+    of its own key points (normalize_keypoints, lightglue.py:31-32).  (The reference leaves the size unbound when a
+    view is absent; here that is treated like a missing size.)"""
+    size = data.get("view" + side, {}).get("image_size")
+    kp = data["keypoints" + side]
+    if size is None and kp.shape[-2] > 0:
+        size = 1 + kp.float().amax(-2) - kp.float().amin(-2)
+    return size
 
 
 class LightGlue(nn.Module):
@@ -303,11 +315,26 @@ class LightGlue(nn.Module):
             p.token_w[i], p.token_b[i] = dev(tc.token[0].weight.reshape(-1)), dev(tc.token[0].bias)
         return p, keep, device
 
+    def _check_ready(self, data=None):
+        if data is not None:
+            for key in self.required_data_keys:
+                assert key in data, f"Missing key {key} in data"
+        if not self.are_weights_initialized:
+            raise RuntimeError("LightGlue weights are not loaded (conf.weights or load_state_dict)")
+
+    def _result(self, m0, m1, ms0, ms1, ref0, ref1, scores, prune0=None, prune1=None):
+        n = self.conf.n_layers
+        return {
+            "matches0": m0, "matches1": m1, "matching_scores0": ms0, "matching_scores1": ms1,
+            "ref_descriptors0": ref0, "ref_descriptors1": ref1, "log_assignment": scores,
+            "prune0": torch.full_like(ms0, n) if prune0 is None else prune0,
+            "prune1": torch.full_like(ms1, n) if prune1 is None else prune1,
+        }
+
     def ensure_packed(self, device):
         """The device copies of the weights in the library's layouts, built on the CALLING thread's current stream if
         they do not exist yet (export workers share them: the caller packs before its worker streams start)."""
-        if not self.are_weights_initialized:
-            raise RuntimeError("LightGlue weights are not loaded (conf.weights or load_state_dict)")
+        self._check_ready()
         if self._packed is None or self._packed[2] != device:
             self._packed = self._pack(device)
             self._graphs = {}
@@ -315,27 +342,16 @@ class LightGlue(nn.Module):
 
     # -- forward ------------------------------------------------------------------------
     def forward(self, data: dict) -> dict:
-        for key in self.required_data_keys:
-            assert key in data, f"Missing key {key} in data"
+        self._check_ready(data)
         conf = self.conf
         if self.training:
             raise NotImplementedError("training (loss, checkpointing) is out of scope: inference path only")
-        if not self.are_weights_initialized:
-            raise RuntimeError("LightGlue weights are not loaded (conf.weights or load_state_dict)")
         kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
         nat.require_cuda(kpts0, "data['keypoints0']")
         b, m, _ = kpts0.shape
         b, n, _ = kpts1.shape
         device = kpts0.device
-        # like the reference (lightglue.py:430-434) the image sizes come from the views; a view without
-        # `image_size` normalises by the extent of its own key points (normalize_keypoints, lightglue.py:31-32).
-        # (The reference leaves size0/size1 unbound when a view is absent; here that is treated like a missing size.)
-        size0 = data.get("view0", {}).get("image_size")
-        size1 = data.get("view1", {}).get("image_size")
-        if size0 is None and m > 0:
-            size0 = 1 + kpts0.float().amax(-2) - kpts0.float().amin(-2)
-        if size1 is None and n > 0:
-            size1 = 1 + kpts1.float().amax(-2) - kpts1.float().amin(-2)
+        size0, size1 = _image_size(data, "0"), _image_size(data, "1")
         desc0 = data["descriptors0"].contiguous().float()
         desc1 = data["descriptors1"].contiguous().float()
         assert desc0.shape[-1] == conf.input_dim
@@ -390,20 +406,7 @@ class LightGlue(nn.Module):
             ms0, ms1 = torch.zeros((b, m), device=device), torch.zeros((b, n), device=device)
             scores = torch.zeros((b, m + 1, n + 1), device=device)
             rows = torch.zeros((b * (m + n), d), device=device)
-        ref0 = rows[: b * m].view(b, 1, m, d)
-        ref1 = rows[b * m:].view(b, 1, n, d)
-        # m == 0 or n == 0: the reference's early return (lightglue.py:298-303) -> all -1 / zeros
-        return {
-            "matches0": m0,
-            "matches1": m1,
-            "matching_scores0": ms0,
-            "matching_scores1": ms1,
-            "ref_descriptors0": ref0,
-            "ref_descriptors1": ref1,
-            "log_assignment": scores,
-            "prune0": torch.full_like(ms0, conf.n_layers),
-            "prune1": torch.full_like(ms1, conf.n_layers),
-        }
+        return self._result(m0, m1, ms0, ms1, rows[: b * m].view(b, 1, m, d), rows[b * m:].view(b, 1, n, d), scores)
 
     # -- several pairs of DIFFERENT sizes through one launch sequence -----------------------------
     def forward_pairs(self, items: list) -> list:
@@ -419,8 +422,7 @@ class LightGlue(nn.Module):
         outs = [None] * len(items)
         rag = []
         for i, data in enumerate(items):
-            for key in self.required_data_keys:
-                assert key in data, f"Missing key {key} in data"
+            self._check_ready(data)
             k0, k1 = data["keypoints0"], data["keypoints1"]
             if adaptive or k0.shape[0] != 1 or k0.shape[1] == 0 or k1.shape[1] == 0 or self.training:
                 outs[i] = self(data)
@@ -434,8 +436,6 @@ class LightGlue(nn.Module):
 
     def _forward_ragged(self, items):
         conf, lib = self.conf, nat.lib()
-        if not self.are_weights_initialized:
-            raise RuntimeError("LightGlue weights are not loaded (conf.weights or load_state_dict)")
         device = items[0]["keypoints0"].device
         nat.require_cuda(items[0]["keypoints0"], "data['keypoints0']")
         self.ensure_packed(device)
@@ -443,14 +443,11 @@ class LightGlue(nn.Module):
         # equal shapes next to each other (stable): every run of equal (m, n) is one batched assignment head
         shapes = [(int(it["keypoints0"].shape[1]), int(it["keypoints1"].shape[1])) for it in items]
         order = sorted(range(len(items)), key=lambda i: shapes[i])
+        groups = [(m, n, list(idx)) for (m, n), idx in itertools.groupby(order, key=lambda i: shapes[i])]
         kp_parts, de_parts, so_parts, s0, s1 = [], [], [], [], []
-        g = 0
-        while g < len(order):
-            h = g
-            while h < len(order) and shapes[order[h]] == shapes[order[g]]:
-                h += 1
+        for _, _, idx in groups:
             for side in ("0", "1"):
-                for i in order[g:h]:
+                for i in idx:
                     it = items[i]
                     kp = it["keypoints" + side][0].float()
                     de = it["descriptors" + side][0].float()
@@ -460,20 +457,15 @@ class LightGlue(nn.Module):
                     if conf.add_scale_ori:
                         sc, ori = it["scales" + side][0], it["oris" + side][0]
                         so_parts.append(torch.stack([sc.reshape(-1), ori.reshape(-1)], -1).float())
-            g = h
-        for i in order:
-            it = items[i]
-            for side, acc in (("0", s0), ("1", s1)):
-                size = it.get("view" + side, {}).get("image_size")
-                kp = it["keypoints" + side]
-                if size is None:  # normalize_keypoints without a size: the extent of the key points (lightglue.py:31-32)
-                    size = 1 + kp.float().amax(-2) - kp.float().amin(-2)
-                acc.append(torch.as_tensor(size, device=device, dtype=torch.float32).reshape(-1, 2)[:1])
-        b = len(order)
+            for i in idx:
+                for side, acc in (("0", s0), ("1", s1)):
+                    size = _image_size(items[i], side)
+                    acc.append(torch.as_tensor(size, device=device, dtype=torch.float32).reshape(-1, 2)[:1])
         kp = torch.cat(kp_parts, 0).contiguous()
         de = torch.cat(de_parts, 0).contiguous()
         so = torch.cat(so_parts, 0).contiguous() if so_parts else None
         size0, size1 = torch.cat(s0, 0).contiguous(), torch.cat(s1, 0).contiguous()
+        b = len(order)
         ms = [shapes[i][0] for i in order]
         ns = [shapes[i][1] for i in order]
         cm, cn = (ctypes.c_int32 * b)(*ms), (ctypes.c_int32 * b)(*ns)
@@ -492,25 +484,16 @@ class LightGlue(nn.Module):
         # per-pair views of the flat outputs; rows: group after group, side 0 then side 1 inside a group
         outs = [None] * b
         o0 = o1 = os_ = r = 0
-        g = 0
-        while g < b:
-            h = g
-            while h < b and (ms[h], ns[h]) == (ms[g], ns[g]):
-                h += 1
-            m, n, cnt = ms[g], ns[g], h - g
-            for j in range(cnt):
-                ms0_, ms1_ = sc0[o0:o0 + m].view(1, m), sc1[o1:o1 + n].view(1, n)
-                outs[order[g + j]] = {
-                    "matches0": m0[o0:o0 + m].view(1, m), "matches1": m1[o1:o1 + n].view(1, n),
-                    "matching_scores0": ms0_, "matching_scores1": ms1_,
-                    "ref_descriptors0": rows[r + j * m: r + (j + 1) * m].view(1, 1, m, d),
-                    "ref_descriptors1": rows[r + cnt * m + j * n: r + cnt * m + (j + 1) * n].view(1, 1, n, d),
-                    "log_assignment": scores[os_:os_ + (m + 1) * (n + 1)].view(1, m + 1, n + 1),
-                    "prune0": torch.full_like(ms0_, conf.n_layers), "prune1": torch.full_like(ms1_, conf.n_layers),
-                }
+        for m, n, idx in groups:
+            cnt = len(idx)
+            for j, i in enumerate(idx):
+                outs[i] = self._result(
+                    m0[o0:o0 + m].view(1, m), m1[o1:o1 + n].view(1, n), sc0[o0:o0 + m].view(1, m),
+                    sc1[o1:o1 + n].view(1, n), rows[r + j * m: r + (j + 1) * m].view(1, 1, m, d),
+                    rows[r + cnt * m + j * n: r + cnt * m + (j + 1) * n].view(1, 1, n, d),
+                    scores[os_:os_ + (m + 1) * (n + 1)].view(1, m + 1, n + 1))
                 o0, o1, os_ = o0 + m, o1 + n, os_ + (m + 1) * (n + 1)
             r += cnt * (m + n)
-            g = h
         return outs
 
     # -- adaptive depth / width (lightglue.py:500-521,555-580) -----------------------------------
@@ -613,14 +596,10 @@ class LightGlue(nn.Module):
             else:
                 m0, m1, ms0, ms1 = pm0, pm1, ps0, ps1
         if not do_prune:
-            prune0 = torch.ones_like(ms0) * conf.n_layers
-            prune1 = torch.ones_like(ms1) * conf.n_layers
-        return {
-            "matches0": m0, "matches1": m1, "matching_scores0": ms0, "matching_scores1": ms1,
-            "ref_descriptors0": x[None, None, :cm], "ref_descriptors1": x[None, None, cm:],
-            "log_assignment": scores, "prune0": prune0, "prune1": prune1,
-            "stop_layer": torch.full((1,), last + 1, device=device, dtype=torch.long),
-        }
+            prune0 = prune1 = None  # every point ran through all n_layers
+        out = self._result(m0, m1, ms0, ms1, x[None, None, :cm], x[None, None, cm:], scores, prune0, prune1)
+        out["stop_layer"] = torch.full((1,), last + 1, device=device, dtype=torch.long)
+        return out
 
     def loss(self, pred, data):
         raise NotImplementedError("training loss (lightglue.py:588-637) is out of scope")

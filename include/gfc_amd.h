@@ -403,7 +403,7 @@ int gfc_lg_filter_matches(const float* scores, int B, int M, int N, float thresh
 /* One transformer layer (self block on every image + bidirectional cross block, lightglue.py:231-245) on the
  * packed descriptor rows x [rows,256] (updated in place), with rotary tables cos/sin [rows,64] and attention
  * problem tables {q_row0, n_q, kv_row0, n_kv} (int32 x4 per entry, n_problems entries each; device).
- * Building block of gfc_lg_forward; driven layer by layer by the host for adaptive depth / width
+ * Building block of the whole-matcher entry points; driven layer by layer by the host for adaptive depth / width
  * (early stop and point pruning, lightglue.py:500-521), where rows are re-packed between layers. */
 size_t gfc_lg_layer_workspace_bytes(int rows);
 int gfc_lg_layer(const gfc_lg_params* p, int layer, float* x, const float* cos_tab, const float* sin_tab, int rows,
@@ -422,11 +422,18 @@ int gfc_lg_assign(const gfc_lg_params* p, int layer, const float* x0, const floa
                   float threshold, int64_t* m0, int64_t* m1, float* ms0, float* ms1, float* log_assignment, void* ws,
                   size_t ws_bytes, void* stream);
 
-/* Whole matcher: LightGlue.forward (lightglue.py:422-553) with early stop / pruning disabled.
+/* Whole matcher: LightGlue.forward (lightglue.py:422-553) with early stop / pruning disabled.  The three whole-matcher
+ * entry points (gfc_lg_forward, gfc_lg_forward_packed, gfc_lg_forward_ragged) describe their batch as groups of equal
+ * (m, n) pairs -- a uniform batch is one group -- and run the same launch sequence on it: problem tables, rotary tables,
+ * input_proj (input_dim != 256), n_layers x gfc_lg_layer, gfc_lg_assign once per group.  Every workspace size comes
+ * from the same planner, and every entry point refuses a batch whose total row count B*(M+N) (ragged: sum(m) + sum(n))
+ * exceeds INT_MAX / 768 (workspace 0, GFC_ERR_INVALID).
  * kpts0 [B,M,2], kpts1 [B,N,2] (pixel coords), desc0 [B,M,Din], desc1 [B,N,Din],
  * size0/size1 [B,2] = (w,h) floats; scale_ori0 [B,M,2] / scale_ori1 [B,N,2] = (scales, oris) of the key points when
  * p->posenc_dim == 4 (add_scale_ori), NULL otherwise.  Outputs as filter_matches + log_assignment [B,M+1,N+1]
- * + ref_desc0 [B,M,256], ref_desc1 [B,N,256] (last-layer descriptors, lightglue.py:495-498). */
+ * + ref_desc0 [B,M,256], ref_desc1 [B,N,256] (last-layer descriptors, lightglue.py:495-498).  The two sides are
+ * packed into the front of ws (descriptors read in place when desc1 starts where desc0 ends), then the packed
+ * layout below runs on the rest. */
 int gfc_lg_forward(const gfc_lg_params* p, const float* kpts0, const float* kpts1, const float* desc0,
                    const float* desc1, const float* size0, const float* size1, const float* scale_ori0,
                    const float* scale_ori1, int B, int M, int N,
@@ -439,7 +446,7 @@ int gfc_lg_forward(const gfc_lg_params* p, const float* kpts0, const float* kpts
  * caller's row buffer: layer 0 reads the descriptors where they are (desc is never written), every later layer
  * works in place on `rows`, which ends up holding the last layer's descriptors = ref_descriptors0 (first B*M rows)
  * and ref_descriptors1.  attention_trace: optional event pairs around the attention launches (see gfc_trace).
- * Replaces the same reference lines as gfc_lg_forward (lightglue.py:422-553). */
+ * The uniform batch: one group of B pairs.  Replaces the same reference lines as gfc_lg_forward (lightglue.py:422-553). */
 size_t gfc_lg_packed_workspace_bytes(int B, int M, int N);
 int gfc_lg_forward_packed(const gfc_lg_params* p, const float* kpts, const float* desc, const float* size0,
                           const float* size1, const float* scale_ori, int B, int M, int N, float threshold, int64_t* m0,
@@ -454,7 +461,8 @@ int gfc_lg_forward_packed(const gfc_lg_params* p, const float* kpts, const float
  * anyway), the assignment head once per GROUP = maximal run of consecutive pairs with equal (m, n).
  * Row layout of kpts [R,2] / desc [R,Din] / scale_ori [R,2] / rows [R,256], R = sum(m) + sum(n): group after group,
  * inside a group the side-0 rows of its pairs (pair-major) followed by their side-1 rows -- i.e. every group is laid out
- * as gfc_lg_forward_packed lays out a uniform batch (B equal pairs = one group = exactly that function's layout).
+ * as gfc_lg_forward_packed lays out a uniform batch (B equal pairs = one group = the same batch, the same launches and
+ * the same workspace size as that function's).
  * Outputs are flat, in pair order: m0 / ms0 [sum m], m1 / ms1 [sum n], log_assignment [sum (m+1)(n+1)] (pair i's
  * [m+1, n+1] matrix contiguous).  size0 / size1 [B,2] (device).  No allocation, no synchronisation; the counts travel
  * to the device as kernel arguments.  Same arithmetic per pair as gfc_lg_forward_packed (lightglue.py:422-553). */

@@ -1057,18 +1057,6 @@ def test_assignment_head_two_pass_tail_vs_oracle(b, m, n):
     assert torch.equal(m0.cpu(), f0) and torch.equal(m1.cpu(), f1)
 
 
-def test_assignment_tail_variants_via_knob():
-    """GFC_ASSIGN_MODE=1 (the five-pass tail of round 1) stays selectable and passes the same test."""
-    import subprocess
-    import sys
-
-    env = dict(os.environ, GFC_ASSIGN_MODE="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-x", "-k",
-                        "(assignment_head_two_pass) and not via_knob", "-p", "no:cacheprovider"], capture_output=True, text=True, env=env,
-                       timeout=600, cwd=ROOT)
-    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-400:])
-
-
 def test_dispatch_order_variants_via_knob():
     """GFC_XCD_REMAP=0 (work items in plain dispatch order instead of the XCD-contiguous order of common.h:
     gfc_xcd_chunk) stays selectable; the order is a speed choice only, so the same tests pass -- including the

@@ -1,6 +1,7 @@
 """CPU-side checks (no GPU, no compute calls into the HIP library): the C-ABI library loads and
 exports every declared symbol, the boundary modules mirror the reference's module contract, the
 product path refuses CPU tensors (no fallback), weight packing order, sharding helpers."""
+import ctypes
 import os
 import re
 import subprocess
@@ -28,6 +29,35 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in gfc_amd.h but not exported"
     assert declared == set(nat.SIGNATURES), declared ^ set(nat.SIGNATURES)
     assert b"gfx950" in lib.gfc_version()
+
+
+def test_lightglue_workspace_sizes_come_from_one_planner():
+    """Host arithmetic only (no HIP call): B equal pairs size the packed and the ragged entry point alike, the ragged
+    one refuses more than GFC_LG_MAX_RAGGED_PAIRS pairs and non-positive counts, and every entry point refuses batches
+    whose row offsets x 768 columns would leave the kernels' int arithmetic."""
+    lib = nat.lib()
+
+    def ragged(ms, ns):
+        b = len(ms)
+        return lib.gfc_lg_ragged_workspace_bytes(b, (ctypes.c_int32 * b)(*ms), (ctypes.c_int32 * b)(*ns))
+
+    for b in (1, 2, 7, 32, nat.GFC_LG_MAX_RAGGED_PAIRS):
+        for m, n in ((1, 1), (5, 300), (512, 512), (1024, 2048), (2048, 1000), (3000, 17)):
+            packed = lib.gfc_lg_packed_workspace_bytes(b, m, n)
+            assert packed > 0 and ragged([m] * b, [n] * b) == packed, (b, m, n)
+            assert lib.gfc_lg_workspace_bytes(b, m, n) > packed, (b, m, n)  # + the staging of the separate arrays
+    over = nat.GFC_LG_MAX_RAGGED_PAIRS + 1
+    assert ragged([4] * over, [4] * over) == 0
+    assert ragged([4, 0], [4, 4]) == 0 and ragged([4, 4], [4, -1]) == 0
+    rmax = (2 ** 31 - 1) // 768  # rows
+    assert ragged([rmax - 1], [1]) > 0 and ragged([rmax], [1]) == 0
+    for b, m, n in ((1, rmax - 1, 1), (7, rmax // 14, rmax // 14), (1000, 1000, rmax // 1000 - 1000)):
+        assert b * (m + n) <= rmax
+        assert lib.gfc_lg_packed_workspace_bytes(b, m, n) > 0 and lib.gfc_lg_workspace_bytes(b, m, n) > 0, (b, m, n)
+    for b, m, n in ((1, rmax, 1), (1000, 1400, 1400), (32, 2 ** 30, 2 ** 30), (2 ** 20, 2048, 2048)):
+        assert b * (m + n) > rmax
+        assert lib.gfc_lg_packed_workspace_bytes(b, m, n) == 0, (b, m, n)
+        assert lib.gfc_lg_workspace_bytes(b, m, n) == 0, (b, m, n)
 
 
 def test_no_oracle_import_in_product():
