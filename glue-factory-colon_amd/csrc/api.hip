@@ -454,22 +454,15 @@ static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* c
     return gfc_linear(a0, lda0, k0, a1, lda1, k1, w, ldw, bias, nullptr, nullptr, 1.f, resid, rc, rs, rot_cols, y, ldy, R,
                       n, st);
   };
-  // ffn[0] -> LayerNorm -> GELU (lightglue.py:143-148) into hbuf: one row-owning kernel once there are enough
-  // 128-row tiles to cover the chip (>= 128: batch >= 8 pairs of 1024 points), else GEMM + in-place LayerNorm pass
-  const bool ffn_fused = gfc_knobs().ffn_fused >= 0 ? gfc_knobs().ffn_fused != 0 : R >= 128 * 128;  // knob: 0 off, 1 / 2 tile variants
-  auto ffn01 = [&](const float* a0, const float* a1, const float* w0, const float* b0, const float* ln_g,
-                   const float* ln_b) -> int {
-    if (ffn_fused) return gfc_linear_layernorm_gelu(a0, D, D, a1, D, D, w0, 512, b0, ln_g, ln_b, hbuf, 512, R, 512, st);
-    GFC_TRY(lin(a0, D, D, a1, D, D, w0, 512, b0, nullptr, nullptr, nullptr, 0, hbuf, 512, 512));
-    return gfc_layernorm_gelu(hbuf, 512, R, 512, ln_g, ln_b, st);
-  };
-  // the whole FFN (ffn[0] -> LayerNorm -> GELU -> ffn[3] + residual) in one kernel where the row-owning kernel runs
-  // (knob: GFC_FFN_MLP = 0 keeps ffn[3] as a GEMM of its own; results are bit-identical either way)
-  const bool ffn_mlp = ffn_fused && gfc_knobs().ffn_fused != 1 && gfc_knobs().ffn_mlp != 0;
+  // the whole FFN (ffn[0] -> LayerNorm -> GELU -> ffn[3] + residual, lightglue.py:143-148) in one row-owning kernel once
+  // there are enough 128-row tiles to cover the chip (>= 128: batch >= 8 pairs of 1024 points), else GEMM into hbuf +
+  // in-place LayerNorm / GELU pass + GEMM
+  const bool ffn_fused = R >= 128 * 128;
   auto ffn = [&](const float* a0, const float* a1, const float* w0, const float* b0, const float* ln_g, const float* ln_b,
                  const float* w3, const float* b3, const float* resid) -> int {
-    if (ffn_mlp) return gfc_ffn_fused(a0, D, D, a1, D, D, w0, 512, b0, ln_g, ln_b, w3, 512, b3, resid, x, D, R, st);
-    GFC_TRY(ffn01(a0, a1, w0, b0, ln_g, ln_b));
+    if (ffn_fused) return gfc_ffn_fused(a0, D, D, a1, D, D, w0, 512, b0, ln_g, ln_b, w3, 512, b3, resid, x, D, R, st);
+    GFC_TRY(lin(a0, D, D, a1, D, D, w0, 512, b0, nullptr, nullptr, nullptr, 0, hbuf, 512, 512));
+    GFC_TRY(gfc_layernorm_gelu(hbuf, 512, R, 512, ln_g, ln_b, st));
     return lin(hbuf, 512, 512, nullptr, 0, 0, w3, 512, b3, resid, nullptr, nullptr, 0, x, D, D);
   };
   const float* xs = x_in ? x_in : x;  // what the self block reads

@@ -21,6 +21,7 @@
 #define AK 64    // keys per LDS tile
 #define AD 64    // head dim
 #define AKLD (AD + 4)
+#define AW 4     // waves per workgroup
 
 #ifdef ATT_DIAG  // diagnostic build (tools/micro/attn_timeline.py): per-wave cycle accounting, 8 words per wave
 __device__ unsigned long long* g_att_diag_dev = nullptr;
@@ -36,9 +37,8 @@ extern "C" void gfc_diag_set_attn_stamps(void* p) {
 // QT = 32-query tiles per wave (1 or 2): a workgroup covers 128*QT queries.  With QT = 2 every K / V
 // fragment read from LDS feeds two independent score tiles, the barrier count per query halves, and
 // the MFMAs of one tile can issue while the softmax of the other runs on the VALU.
-// AW = waves per workgroup (4, or 2 for small problems: twice the workgroups for the same queries).
-template <int QT, int AW>
-__global__ __launch_bounds__(64 * AW, AW == 4 ? 2 : 1) void attention_kernel(const float* __restrict__ Q, int ldq,
+template <int QT>
+__global__ __launch_bounds__(64 * AW, 2) void attention_kernel(const float* __restrict__ Q, int ldq,
                                                            const float* __restrict__ Kp, int ldk,
                                                            const float* __restrict__ V, int ldv,
                                                            float* __restrict__ O, int ldo,
@@ -114,9 +114,8 @@ __global__ __launch_bounds__(64 * AW, AW == 4 ? 2 : 1) void attention_kernel(con
   const float* kbase = Kp + head * AD + st_c4;
   const float* vbase = V + head * AD + st_c4;
   // named prefetch registers (arrays were demoted to private memory by hipcc)
-  float4 kr0, kr1, kr2, kr3, kr4, kr5, kr6, kr7, vr0, vr1, vr2, vr3, vr4, vr5, vr6, vr7;
-  kr4 = kr5 = kr6 = kr7 = vr4 = vr5 = vr6 = vr7 = make_float4(0.f, 0.f, 0.f, 0.f);
-  static_assert(NLD == 4 || NLD == 8, "staging layout");
+  float4 kr0, kr1, kr2, kr3, vr0, vr1, vr2, vr3;
+  static_assert(NLD == 4, "staging layout");
 #define ATT_LOAD(kt_)                                                                                                                                                                       \
   do {                                                                                                                                                                                      \
     const int kb_ = (kt_) * AK + st_key;                                                                                                                                                    \
@@ -124,12 +123,6 @@ __global__ __launch_bounds__(64 * AW, AW == 4 ? 2 : 1) void attention_kernel(con
     { const size_t r_ = kv_row0 + min(kb_ + (T / 16) * 1, nk - 1); kr1 = *reinterpret_cast<const float4*>(kbase + r_ * ldk); vr1 = *reinterpret_cast<const float4*>(vbase + r_ * ldv); }    \
     { const size_t r_ = kv_row0 + min(kb_ + (T / 16) * 2, nk - 1); kr2 = *reinterpret_cast<const float4*>(kbase + r_ * ldk); vr2 = *reinterpret_cast<const float4*>(vbase + r_ * ldv); }    \
     { const size_t r_ = kv_row0 + min(kb_ + (T / 16) * 3, nk - 1); kr3 = *reinterpret_cast<const float4*>(kbase + r_ * ldk); vr3 = *reinterpret_cast<const float4*>(vbase + r_ * ldv); }    \
-    if constexpr (NLD == 8) {                                                                                                                                                               \
-      { const size_t r_ = kv_row0 + min(kb_ + (T / 16) * 4, nk - 1); kr4 = *reinterpret_cast<const float4*>(kbase + r_ * ldk); vr4 = *reinterpret_cast<const float4*>(vbase + r_ * ldv); }  \
-      { const size_t r_ = kv_row0 + min(kb_ + (T / 16) * 5, nk - 1); kr5 = *reinterpret_cast<const float4*>(kbase + r_ * ldk); vr5 = *reinterpret_cast<const float4*>(vbase + r_ * ldv); }  \
-      { const size_t r_ = kv_row0 + min(kb_ + (T / 16) * 6, nk - 1); kr6 = *reinterpret_cast<const float4*>(kbase + r_ * ldk); vr6 = *reinterpret_cast<const float4*>(vbase + r_ * ldv); }  \
-      { const size_t r_ = kv_row0 + min(kb_ + (T / 16) * 7, nk - 1); kr7 = *reinterpret_cast<const float4*>(kbase + r_ * ldk); vr7 = *reinterpret_cast<const float4*>(vbase + r_ * ldv); }  \
-    }                                                                                                                                                                                       \
   } while (0)
 #define ATT_STORE(buf_)                                                                                                                                    \
   do {                                                                                                                                                     \
@@ -139,12 +132,6 @@ __global__ __launch_bounds__(64 * AW, AW == 4 ? 2 : 1) void attention_kernel(con
     { const int key_ = st_key + (T / 16) * 1; *reinterpret_cast<float4*>(kd_ + key_ * AKLD) = kr1; *reinterpret_cast<float4*>(vd_ + key_ * AD) = vr1; }    \
     { const int key_ = st_key + (T / 16) * 2; *reinterpret_cast<float4*>(kd_ + key_ * AKLD) = kr2; *reinterpret_cast<float4*>(vd_ + key_ * AD) = vr2; }    \
     { const int key_ = st_key + (T / 16) * 3; *reinterpret_cast<float4*>(kd_ + key_ * AKLD) = kr3; *reinterpret_cast<float4*>(vd_ + key_ * AD) = vr3; }    \
-    if constexpr (NLD == 8) {                                                                                                                              \
-      { const int key_ = st_key + (T / 16) * 4; *reinterpret_cast<float4*>(kd_ + key_ * AKLD) = kr4; *reinterpret_cast<float4*>(vd_ + key_ * AD) = vr4; }  \
-      { const int key_ = st_key + (T / 16) * 5; *reinterpret_cast<float4*>(kd_ + key_ * AKLD) = kr5; *reinterpret_cast<float4*>(vd_ + key_ * AD) = vr5; }  \
-      { const int key_ = st_key + (T / 16) * 6; *reinterpret_cast<float4*>(kd_ + key_ * AKLD) = kr6; *reinterpret_cast<float4*>(vd_ + key_ * AD) = vr6; }  \
-      { const int key_ = st_key + (T / 16) * 7; *reinterpret_cast<float4*>(kd_ + key_ * AKLD) = kr7; *reinterpret_cast<float4*>(vd_ + key_ * AD) = vr7; }  \
-    }                                                                                                                                                      \
   } while (0)
 
   if (kt0 < kt1) {
@@ -324,19 +311,17 @@ extern "C" int gfc_attention(const float* Q, int ldq, const float* K, int ldk, c
                              void* ws, size_t ws_bytes, void* stream) {
   if (!Q || !K || !V || !O || !problems || n_problems <= 0 || max_nq <= 0 || heads <= 0) return GFC_ERR_INVALID;
   if (ldq % 4 || ldk % 4 || ldv % 4 || ldo % 4) return GFC_ERR_INVALID;
-  // tuning knob (tools/bench_kernels.py): GFC_ATTN_CFG = 1: 2 q-tiles/wave, 4 waves (256 queries / workgroup)
-  //                                                      2: 1 q-tile/wave, 4 waves (128);  3: 1 q-tile, 2 waves (64)
+  // tuning knob (tools/bench_kernels.py): GFC_ATTN_CFG = 1: 2 q-tiles/wave (256 queries / workgroup), 2: 1 q-tile/wave
+  // (128); anything else = automatic
   const int forced = gfc_knobs().attn_cfg;
   auto wgs = [&](int aq) { return (long long)((max_nq + aq - 1) / aq) * heads * n_problems; };
   // the largest query block that still fills the chip twice over (256 CUs x 2 workgroups)
-  // (cfg 3, 64 queries per 2-wave workgroup, measured no faster than cfg 2 at batch 1: knob only)
-  const int cfg = forced ? forced : (wgs(256) >= 1024 ? 1 : 2);
+  const int cfg = (forced == 1 || forced == 2) ? forced : (wgs(256) >= 1024 ? 1 : 2);
   const float sl2 = scale * 1.4426950408889634f;
   hipStream_t st = (hipStream_t)stream;
   const int4* pt = reinterpret_cast<const int4*>(problems);
   // key split for small problem sets (batch 1..2): few 128-query blocks cannot fill 1024 SIMDs, so each block's
   // keys are shared out over up to 8 workgroups and a tiny merge kernel combines the partial soft-maxes
-  const int xcd = gfc_knobs().xcd_remap != 0;
   int ksplit = 1;
   if (cfg == 2 && ws != nullptr) {
     const long long w = wgs(128);
@@ -346,18 +331,15 @@ extern "C" int gfc_attention(const float* Q, int ldq, const float* K, int ldk, c
     ksplit = want < 1 ? 1 : want;
   }
   if (cfg == 1) {
-    hipLaunchKernelGGL((attention_kernel<2, 4>), dim3((max_nq + 255) / 256, heads, n_problems), dim3(256), 0, st, Q,
-                       ldq, K, ldk, V, ldv, O, ldo, pt, sl2, 1, (float*)nullptr, max_nq, xcd);
-  } else if (cfg == 2) {
+    hipLaunchKernelGGL(attention_kernel<2>, dim3((max_nq + 255) / 256, heads, n_problems), dim3(256), 0, st, Q, ldq, K,
+                       ldk, V, ldv, O, ldo, pt, sl2, 1, (float*)nullptr, max_nq, 1);
+  } else {
     float* part = ksplit > 1 ? (float*)ws : nullptr;
-    hipLaunchKernelGGL((attention_kernel<1, 4>), dim3(((max_nq + 127) / 128) * ksplit, heads, n_problems), dim3(256), 0,
-                       st, Q, ldq, K, ldk, V, ldv, O, ldo, pt, sl2, ksplit, part, max_nq, xcd);
+    hipLaunchKernelGGL(attention_kernel<1>, dim3(((max_nq + 127) / 128) * ksplit, heads, n_problems), dim3(256), 0, st,
+                       Q, ldq, K, ldk, V, ldv, O, ldo, pt, sl2, ksplit, part, max_nq, 1);
     if (ksplit > 1)
       hipLaunchKernelGGL(attention_merge_kernel, dim3((max_nq + 3) / 4, heads, n_problems), dim3(256), 0, st, part, O,
                          ldo, pt, ksplit, max_nq, sl2);
-  } else {
-    hipLaunchKernelGGL((attention_kernel<1, 2>), dim3((max_nq + 63) / 64, heads, n_problems), dim3(128), 0, st, Q, ldq,
-                       K, ldk, V, ldv, O, ldo, pt, sl2, 1, (float*)nullptr, max_nq, xcd);
   }
   GFC_LAUNCH_CHECK();
   return GFC_OK;

@@ -114,11 +114,18 @@ struct ConvArgs {
 #ifndef CONV_LOAD_TAP
 #define CONV_LOAD_TAP 2   // tap at which the next input chunk's global loads are issued (stored after tap 8)
 #endif
-// KC = channels per chunk: 32 (65 KB LDS, 2 workgroups / CU) or 16 (36 KB, 3 workgroups / CU)
-// PERSIST = workgroups walk several work items with the next item's operands prefetched (see below); without it the
-// grid has one workgroup per item and the hand-over code (and its registers) is compiled out.
-template <bool POOL, bool STEM, int KC, bool PERSIST>
-__global__ __launch_bounds__(256, (KC == 16 && !PERSIST) ? 3 : 2) void conv3x3_mfma_kernel(ConvArgs a) {
+// Variant per layer kind (same-box A/B, tools/ab_build.sh + tools/bench_kernels.py --only conv, 32 VGA images):
+//  * pooled layers and the stem: KC = 16 channels per chunk (36 KB LDS: three workgroups per CU), one workgroup per
+//    item (persistent workgroups cost the third resident workgroup in registers: stem -1.5 %, conv2b -1 %);
+//  * un-pooled layers: KC = 32 (65 KB: two workgroups per CU), PERSIST: workgroups walk several work items with the
+//    next item's operands prefetched (see below; +1.5..2 %, small grids such as conv4a at 60x80 +16 %, because two
+//    resident workgroups per CU then share the items evenly).  Without PERSIST the grid has one workgroup per item and
+//    the hand-over code (and its registers) is compiled out.
+__host__ __device__ constexpr int conv_kc(bool pool) { return pool ? 16 : 32; }
+template <bool POOL, bool STEM>
+__global__ __launch_bounds__(256, POOL ? 3 : 2) void conv3x3_mfma_kernel(ConvArgs a) {
+  constexpr int KC = conv_kc(POOL);
+  constexpr bool PERSIST = !POOL;
   constexpr int CLD = KC + 4;                        // LDS row stride in floats (bank-conflict padding, 16B aligned)
   constexpr int C4 = KC / 4;                         // float4 per staged row
   constexpr int NI = (CH * CH * C4 + 255) / 256;     // input float4 per thread per chunk
@@ -464,12 +471,13 @@ extern "C" int gfc_conv3x3(const float* x, const float* w_packed, const float* b
   return launch_conv(a, pool != 0, false, st);
 }
 
-template <bool POOL, bool STEM, int KC, bool PERSIST>
+template <bool POOL, bool STEM>
 static int launch_conv_t(const ConvArgs& a, dim3 grid, hipStream_t st) {
+  constexpr int KC = conv_kc(POOL);
   const size_t lds = (size_t)(CH * CH * (KC + 4) + 2 * CNB * (KC + 4) + (STEM ? CIM * CIM + 768 : 0)) * sizeof(float);
   static std::atomic<unsigned long long> lds_ok{0};  // per (instantiation, device): runtime.h
-  if (lds > 64 * 1024) gfc_allow_dynamic_lds((const void*)conv3x3_mfma_kernel<POOL, STEM, KC, PERSIST>, lds, lds_ok);
-  hipLaunchKernelGGL((conv3x3_mfma_kernel<POOL, STEM, KC, PERSIST>), grid, dim3(256), lds, st, a);
+  if (lds > 64 * 1024) gfc_allow_dynamic_lds((const void*)conv3x3_mfma_kernel<POOL, STEM>, lds, lds_ok);
+  hipLaunchKernelGGL((conv3x3_mfma_kernel<POOL, STEM>), grid, dim3(256), lds, st, a);
   GFC_LAUNCH_CHECK();
   return GFC_OK;
 }
@@ -477,32 +485,13 @@ static int launch_conv_t(const ConvArgs& a, dim3 grid, hipStream_t st) {
 static int launch_conv(ConvArgs a, bool pool, bool stem, hipStream_t st) {
   a.tiles_x = (a.W + CT - 1) / CT;
   a.tiles_y = (a.H + CT - 1) / CT;
-  const int ncu = gfc_device_cus();
-  // Variant per layer kind (same-box A/B, tools/ab_build.sh + tools/bench_kernels.py --only conv, 32 VGA images):
-  //  * pooled layers and the stem: 16-channel LDS chunks (36 KB: three workgroups per CU), one workgroup per item
-  //    (persistent workgroups cost the third resident workgroup in registers: stem -1.5 %, conv2b -1 %);
-  //  * un-pooled layers: 32-channel chunks, persistent workgroups (+1.5..2 %; small grids such as conv4a at
-  //    60x80 +16 %, because two resident workgroups per CU then share the items evenly).
-  // GFC_CONV_KC=32|16 and GFC_CONV_PERSIST=0|1 force a variant.
-  const int forced_kc = gfc_knobs().conv_kc, forced_p = gfc_knobs().conv_persist;
-  const int kc = forced_kc ? forced_kc : (pool ? 16 : 32);
-  const bool persist = forced_p >= 0 ? forced_p != 0 : !pool;
+  // un-pooled layers run persistent workgroups (conv3x3_mfma_kernel: PERSIST), two resident per CU
   const long long nitems = (long long)a.tiles_x * a.tiles_y * a.B * (a.cout / CNB);
-  const long long resident = (long long)ncu * 2;
-  dim3 grid((unsigned)(persist && nitems > resident ? resident : nitems));
-#define CONV_DISPATCH(KC_, P_)                                                      \
-  do {                                                                              \
-    if (stem) return launch_conv_t<true, true, KC_, P_>(a, grid, st);               \
-    if (pool) return launch_conv_t<true, false, KC_, P_>(a, grid, st);              \
-    return launch_conv_t<false, false, KC_, P_>(a, grid, st);                       \
-  } while (0)
-  if (kc == 16) {
-    if (persist) CONV_DISPATCH(16, true);
-    CONV_DISPATCH(16, false);
-  }
-  if (persist) CONV_DISPATCH(32, true);
-  CONV_DISPATCH(32, false);
-#undef CONV_DISPATCH
+  const long long resident = (long long)gfc_device_cus() * 2;
+  dim3 grid((unsigned)(!pool && nitems > resident ? resident : nitems));
+  if (stem) return launch_conv_t<true, true>(a, grid, st);
+  if (pool) return launch_conv_t<true, false>(a, grid, st);
+  return launch_conv_t<false, false>(a, grid, st);
 }
 
 // conv1a (1 -> 64) + conv1b (64 -> 64) + 2x2 max-pool in one launch: gray image [B,H,W] -> [B,H/2,W/2,64].

@@ -37,7 +37,7 @@
 #define WIM_R 20                   // STEM: image patch rows
 #define WIM_C 12                   // STEM: image patch columns
 #ifndef WINO_DIAG
-#define WINO_DIAG 0                // diagnostic builds (tools/ab_build.sh): 1 no conv1a, 2 no B reloads, 8 no patch loads, 16 no column transform, 64 no chunk barrier, 256 phase accounting (tools/micro/wino_timeline.py), 512 no output stores
+#define WINO_DIAG 0                // diagnostic builds (tools/ab_build.sh): 256 = phase accounting (tools/micro/wino_timeline.py)
 #endif
 
 struct WinoArgs {
@@ -53,7 +53,7 @@ struct WinoArgs {
   const float* b1;
   const float* s1;
   const float* t1;
-  int xcd_remap;  // walk the work items in XCD-contiguous order (runtime.h: GFC_XCD_REMAP)
+  int xcd_remap;  // walk the work items in XCD-contiguous order (common.h: gfc_xcd_chunk)
 #if WINO_DIAG & 256
   unsigned long long* diag;  // diagnostic build (tools/micro/wino_timeline.py): 8 words per wave
 #endif
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
 #define WINO_LOAD_IN(xin_, chunk_)                                                                \
   _Pragma("unroll") for (int i_ = 0; i_ < 3; ++i_) {                                               \
     float4 v_ = make_float4(0.f, 0.f, 0.f, 0.f);                                                   \
-    if (st_gofs[i_] >= 0 && !(WINO_DIAG & 8)) v_ = *reinterpret_cast<const float4*>((xin_) + st_gofs[i_] + (chunk_) * WKC); \
+    if (st_gofs[i_] >= 0) v_ = *reinterpret_cast<const float4*>((xin_) + st_gofs[i_] + (chunk_) * WKC); \
     ireg[i_] = v_;                                                                                 \
   }
 #define WINO_FILL_IN(chunk_)                                                                      \
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
     const float4 t1_ = *reinterpret_cast<const float4*>(c1_s + 704 + c0_);                         \
     _Pragma("unroll") for (int i_ = 0; i_ < 3; ++i_) {                                             \
       float4 v_ = make_float4(0.f, 0.f, 0.f, 0.f);  /* outside the image: conv1b's zero padding */ \
-      if (st_gofs[i_] >= 0 && !(WINO_DIAG & 1)) {                                                  \
+      if (st_gofs[i_] >= 0) {                                                                      \
         const float* ip_ = img_s + st_gofs[i_];                                                    \
         _Pragma("unroll") for (int t2_ = 0; t2_ < 9; ++t2_) {                                      \
           const float f_ = ip_[(t2_ / 3) * WIM_C + t2_ % 3];                                       \
@@ -266,12 +266,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
   for (int c = 0; c < nchunks; ++c) {
     const bool has_next = c + 1 < nchunks;
     const float* ps = in_s + (c & 1) * WPATCH;
-#if WINO_DIAG & 128  // diagnostic: request the next patch at the top of the chunk instead of after group 0
-    if constexpr (!STEM) {
-      if (has_next) { WINO_LOAD_IN(xin, c + 1); }
-      else if (more) { WINO_GOFS(ny0, nx0); WINO_LOAD_IN(nxin, 0); }
-    }
-#endif
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       const float* p1 = ps + (g ? (o1 ^ 8) : o1);
@@ -282,17 +276,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
       const float4 t2 = f4_axpy(sg, *reinterpret_cast<const float4*>(p2 + 1 * WKC), *reinterpret_cast<const float4*>(p1 + 1 * WKC));
       const float4 t3 = f4_axpy(sg, *reinterpret_cast<const float4*>(p2 + 6 * WKC), *reinterpret_cast<const float4*>(p1 + 6 * WKC));
       float4 v[4];
-      if (WINO_DIAG & 16) {  // diagnostic: fragments without the column transform
-        v[0] = t0; v[1] = t1; v[2] = t2; v[3] = t3;
-      } else {
-        v[0] = f4_sub(t0, t2);
-        v[1] = f4_add(t1, t2);
-        v[2] = f4_sub(t2, t1);
-        v[3] = f4_sub(t1, t3);
-      }
+      v[0] = f4_sub(t0, t2);
+      v[1] = f4_add(t1, t2);
+      v[2] = f4_sub(t2, t1);
+      v[3] = f4_sub(t1, t3);
       const int kg_next = 2 * c + g + 1;
       // next fragments: the following k group of this item, or group 0 of the next item
-      const bool more_b = (kg_next < cin / 8 || more) && !(WINO_DIAG & 2);
+      const bool more_b = kg_next < cin / 8 || more;
       const float4* bsrc = kg_next < cin / 8 ? wp + (size_t)kg_next * 512 : nwp;
 #pragma unroll
       for (int nu = 0; nu < 4; ++nu) {
@@ -316,15 +306,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
         if constexpr (STEM) {
           if (has_next) { WINO_FILL_IN(c + 1); }  // VALU work under the MFMAs of this chunk
         } else {
-#if !(WINO_DIAG & 128)
           if (has_next) { WINO_LOAD_IN(xin, c + 1); }
           else if (more) { WINO_GOFS(ny0, nx0); WINO_LOAD_IN(nxin, 0); }
-#endif
         }
       }
     }
     if (has_next) WINO_STORE_IN((c + 1) & 1);
-    if (!(WINO_DIAG & 64)) __syncthreads();
+    __syncthreads();
   }
 
   WINO_T(t_b);
@@ -378,7 +366,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
       const int Ho = a.H >> 1, Wo = a.W >> 1;
       if (oy < Ho && ox < Wo) {
         const float4 u = yv[0][0], v = yv[0][1], w = yv[1][0], z = yv[1][1];
-        if (!(WINO_DIAG & 512) || oy < 0)  // diagnostic 512: no output stores
         *reinterpret_cast<float4*>(a.y + (((size_t)b * Ho + oy) * Wo + ox) * a.cout + co) =
             make_float4(fmaxf(fmaxf(u.x, v.x), fmaxf(w.x, z.x)), fmaxf(fmaxf(u.y, v.y), fmaxf(w.y, z.y)),
                         fmaxf(fmaxf(u.z, v.z), fmaxf(w.z, z.z)), fmaxf(fmaxf(u.w, v.w), fmaxf(w.w, z.w)));
@@ -389,7 +376,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(WinoArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int gy = 2 * oy + i, gx = 2 * ox + j;
-          if (gy < a.H && gx < a.W && (!(WINO_DIAG & 512) || gy < 0))  // diagnostic 512: no output stores
+          if (gy < a.H && gx < a.W)
             *reinterpret_cast<float4*>(a.y + (((size_t)b * a.H + gy) * a.W + gx) * a.cout + co) = yv[i][j];
         }
     }
@@ -432,10 +419,9 @@ static int launch_wino(const WinoArgs& a, hipStream_t st) {
   const long long nitems = (long long)a.tiles_x * a.tiles_y * a.B * (a.cout / 64);
   long long resident = ((long long)gfc_device_cus() * 2) & ~7ll;  // two workgroups per CU (registers, 64-68 KB LDS);
   if (resident < 8) resident = 8;                               // a multiple of 8: the XCD label of an item = item % 8
-  const int forced = gfc_knobs().conv_persist;                 // GFC_CONV_PERSIST=0: one workgroup per item
-  const long long grid = (STEM || forced == 0 || nitems < resident) ? nitems : resident;
+  const long long grid = (STEM || nitems < resident) ? nitems : resident;
   WinoArgs wa = a;
-  wa.xcd_remap = gfc_knobs().xcd_remap != 0 && nitems >= 16;
+  wa.xcd_remap = nitems >= 16;
 #if WINO_DIAG & 256
   wa.diag = g_wino_diag;
 #endif

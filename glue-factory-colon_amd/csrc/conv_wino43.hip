@@ -49,7 +49,7 @@
 #define S4_EX (6 * 2 * 32 * 32)                // exchange buffer floats (one cout tile, one column pair): [xi][jj][tile][cout]
 #define S4_THREADS 768
 #ifndef S4_DIAG
-#define S4_DIAG 0  // diagnostic builds (tools/ab_build.sh WORKTREE s4 "-DS4_DIAG=1"): 1 = per-wave phase accounting (tools/micro/stem43_timeline.py); ablations with wrong results: 2 no conv1a stores, 4 no conv1a units inside the chunks, 8 no patch reads, 16 no filter-fragment loads, 32 no epilogue
+#define S4_DIAG 0  // diagnostic builds (tools/ab_build.sh WORKTREE s4 "-DS4_DIAG=1"): 1 = per-wave phase accounting (tools/micro/stem43_timeline.py)
 #endif
 #if S4_DIAG & 1
 static unsigned long long* g_s4_diag = nullptr;
@@ -130,13 +130,7 @@ __device__ __forceinline__ v2f v2_mul(float s, v2f a) { return v2f{s * a.x, s * 
 // LDS read of one channel pair.  volatile: hipcc would otherwise fuse neighbouring reads into ds_read2_b64, which is
 // banked modulo 32 in 16-lane groups (2-way conflicts on this layout) at half the bandwidth of ds_read_b64
 typedef const volatile __attribute__((address_space(3))) v2f* lds_v2f_ptr;
-__device__ __forceinline__ v2f lds_pair(const float* p) {
-#if S4_DIAG & 8
-  return v2f{(float)(size_t)p, 1.f};
-#else
-  return *(lds_v2f_ptr)(p);
-#endif
-}
+__device__ __forceinline__ v2f lds_pair(const float* p) { return *(lds_v2f_ptr)(p); }
 
 __global__ __launch_bounds__(S4_THREADS, 1) void stem_wino43_kernel(Stem43Args args) {
   // (plain locals: the lambdas below capture by reference, and a by-value kernel argument struct whose address is
@@ -267,9 +261,6 @@ __global__ __launch_bounds__(S4_THREADS, 1) void stem_wino43_kernel(Stem43Args a
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int rr = (r & 3) + 8 * (r >> 2);
-#if S4_DIAG & 2  // ablation: no conv1a stores (wrong results)
-          if (d[r] == 12345.678f)
-#endif
           o[((rr & 3) * 9 + (rr >> 2)) * 8] = fmaxf(d[r], 0.f) * sc + sh;
         }
       } else {
@@ -352,10 +343,10 @@ __global__ __launch_bounds__(S4_THREADS, 1) void stem_wino43_kernel(Stem43Args a
 #pragma unroll 1
       for (int half = 0; half < 4; ++half) {  // (not unrolled: one copy of the conv1a code and of the half k group)
         const int g = half >> 1, hh = half & 1;
-        // conv1a, staggered over the three waves of a SIMD (one of them transforms pixels while the other two keep
+        // conv1a, taken in turn by the three waves of a SIMD (one of them transforms pixels while the other two keep
         // the matrix pipe busy): chunk 1 -> this item's chunks 2, 3 (buffers A, C); chunk 3 -> the next item's
         // chunks 0, 1 (buffers A, B)
-        if ((c & 1) && (c == 1 || have_next) && !(S4_DIAG & 4)) {
+        if ((c & 1) && (c == 1 || have_next)) {
           S4_T(tu);
           conv1a_at_half(half, c == 1 ? 1 : 0, c == 1 ? y0 : ny0, c == 1 ? x0 : nx0, bufA, c == 1 ? bufC : bufB);
 #if S4_DIAG & 1
@@ -370,7 +361,7 @@ __global__ __launch_bounds__(S4_THREADS, 1) void stem_wino43_kernel(Stem43Args a
         // they are live neither during conv1a above nor during the epilogue (register budget)
         float2 bq[6];
 #pragma unroll
-        for (int nu = 0; nu < 6; ++nu) bq[nu] = (S4_DIAG & 16) ? make_float2(1.f + nu, 0.5f) : bfrag(4 * c + half, nu);
+        for (int nu = 0; nu < 6; ++nu) bq[nu] = bfrag(4 * c + half, nu);
         const float* pl = ps + g * S4_PLANE;
         const float* pA = pl + (offA ^ (2 * hh));
         const float* pB = pl + (offB ^ (2 * hh));
@@ -459,18 +450,8 @@ __global__ __launch_bounds__(S4_THREADS, 1) void stem_wino43_kernel(Stem43Args a
     asm volatile("" : "+v"(tq));  // (opaque: keeps the reader's index arithmetic out of the item loop's live ranges)
     const int co_q = (tq & 7) * 4, ip2 = (tq >> 3) & 1, tile = tq >> 4;  // reader role (tid < 512)
     const int Ho = a_H >> 1, Wo = a_W >> 1;
-#if S4_DIAG & 32  // ablation: no epilogue; the accumulators stay alive
-    {
-      float sum_ = 0.f;
-#pragma unroll
-      for (int nu = 0; nu < 6; ++nu)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum_ += acc[nu][r];
-      if (sum_ == 12345.678f) a_y[tid] = sum_;
-    }
-#endif
 #pragma unroll 1
-    for (int pnt = 0; pnt < ((S4_DIAG & 32) ? 0 : 2); ++pnt)  // output-channel tile
+    for (int pnt = 0; pnt < 2; ++pnt)  // output-channel tile
 #pragma unroll
     for (int jp = 0; jp < 2; ++jp) {   // pooled column inside the Winograd tile = output columns 2 jp, 2 jp + 1
       if (nt == pnt) {

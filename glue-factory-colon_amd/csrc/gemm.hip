@@ -32,10 +32,7 @@ struct GemmArgs {
   int lda0, lda1, ldw, ldy;
   int K0, K1, M, N, rot_cols;
   float alpha;
-  int xcd_remap;  // gemm_nt_kernel: walk the tiles in XCD-contiguous order (runtime.h: GFC_XCD_REMAP)
-  int wide_stores;  // every epilogue through the per-wave LDS transpose: float4 stores (runtime.h: GFC_GEMM_EPI)
-  int stagger;      // first-round workgroups start (wave slot & 3) * stagger * 8128 cycles late (GFC_GEMM_STAGGER)
-  int first_round;  // number of workgroups resident at once (4 per CU)
+  int xcd_remap;  // gemm_nt_kernel: walk the tiles in XCD-contiguous order (common.h: gfc_xcd_chunk)
 #if defined(GEMM_DIAG) && (GEMM_DIAG & 16)
   unsigned long long* stamps;  // diagnostic build (tools/micro/gemm_timeline.py): 8 words per wave
 #endif
@@ -132,7 +129,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[M
   const int l31 = lane & 31, h = lane >> 5;
   // (workgroup-uniform: column tiles at or beyond rot_cols -- the V third of the fused QKV projection -- carry no
   // rotary and take the direct path as well)
-  if (((g.rot_cos == nullptr && g.rot_cs == nullptr) || n0 >= g.rot_cols) && g.residual == nullptr && !g.wide_stores) {
+  if (((g.rot_cos == nullptr && g.rot_cs == nullptr) || n0 >= g.rot_cols) && g.residual == nullptr) {
     // plain epilogue: straight from the accumulator layout (column on the lane, rows in registers);
     // measured faster than the LDS transpose below when nothing has to be loaded per element
 #pragma unroll
@@ -157,9 +154,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[M
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const float v = ((acc[mt][nt][r] + bi) * sc + sh) * g.alpha;
-#if defined(GEMM_DIAG) && (GEMM_DIAG & 1)
-            if (v == 12345.678f)  // diagnostic: no stores
-#endif
             yp[(size_t)((r & 3) + 8 * (r >> 2)) * g.ldy] = v;
           }
         } else {
@@ -167,11 +161,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[M
           for (int r = 0; r < 16; ++r) {
             const int row = row0 + acc_row(r, h);
             const float v = ((acc[mt][nt][r] + bi) * sc + sh) * g.alpha;
-#if defined(GEMM_DIAG) && (GEMM_DIAG & 1)
-            if (row < g.M && col_ok && v == 12345.678f) Y[(size_t)row * g.ldy + col] = v;  // diagnostic: no stores
-#else
             if (row < g.M && col_ok) Y[(size_t)row * g.ldy + col] = v;
-#endif
           }
         }
       }
@@ -318,15 +308,6 @@ __global__ __launch_bounds__(128 * NW, MT * MTN > 4 ? 2 : (BK == 16 ? 4 : 2)) vo
     t -= bz * per_z;
     by = t / gridDim.x;
     bx = t - by * gridDim.x;
-  }
-  // De-phasing (K = 256 GEMMs are two lock-step rounds of four workgroups per CU: every CU stores its 64 KB tiles at
-  // the same moment, the chip-wide burst is HBM-write bound and the matrix pipe waits): the workgroups of the FIRST
-  // round start staggered by their wave slot, so that later K loops and epilogues of a CU interleave.
-  if (g.stagger > 0 && (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) < g.first_round) {
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    const int naps = (int)(hw & 3u) * g.stagger;
-    for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(127);
   }
   const int m0 = by * GBM, n0 = bx * BN;
   const long long z = bz;
@@ -504,13 +485,7 @@ __device__ __forceinline__ float halfwave_transpose_sum32(const float (&x)[32], 
   return mine + __shfl_xor(theirs, 16);
 }
 
-// WM = row groups of 64 per workgroup:
-//   WM = 2: 128 x 512 tile, 8 waves, K tile 16, 100 KB LDS: one workgroup per CU;
-//   WM = 1:  64 x 512 tile, 4 waves, K tile 8,   54 KB LDS: two workgroups per CU that run out of phase, so the
-//            VALU-heavy epilogue (LayerNorm + erf, ~50 instructions per element) and the store drain of one
-//            overlap the MFMAs of the other.
-//
-// MLP = true (WM = 2 only; round 4): the WHOLE LightGlue FFN in the kernel -- Linear(512,512) -> LayerNorm -> GELU ->
+// MLP = true (round 4): the WHOLE LightGlue FFN in the kernel -- Linear(512,512) -> LayerNorm -> GELU ->
 // Linear(512,256) + residual (lightglue.py:143-148,162-164).  The activated 128 x 512 hidden tile stays in the
 // accumulator registers; it is handed to the second GEMM through LDS in four 128-column chunks (the column group wn = c
 // owns chunk c), which the eight waves consume as the A operand of Y[128,256] += H[:, chunk] . W3[:, chunk]^T with W3
@@ -519,13 +494,12 @@ __device__ __forceinline__ float halfwave_transpose_sum32(const float (&x)[32], 
 // (ascending 8-deep groups, k = 4h + s inside a group), same epilogue association (residual + (acc + bias)): the
 // results are bit-identical to the two-kernel path.  The [M,512] hidden activation never exists in HBM.
 #define FF_HLD 148  // hidden-chunk row stride in floats (= 20 mod 64: the conflict-free ds_read_b128 pattern of the K-tile rows)
-template <int WM, bool MLP = false>
-__global__ __launch_bounds__(256 * WM, 2) void gemm_rows512_ln_gelu_kernel(GemmArgs g, const float* __restrict__ gamma,
-                                                                           const float* __restrict__ beta,
-                                                                           const float* __restrict__ W3, int ldw3,
-                                                                           const float* __restrict__ b3) {
-  static_assert(!MLP || WM == 2, "the fused MLP is built for the 128-row tile");
-  constexpr int BM = 64 * WM, BK = WM == 2 ? 16 : 8, LD = BK + 4, C4 = BK / 4;
+template <bool MLP>
+__global__ __launch_bounds__(512, 2) void gemm_rows512_ln_gelu_kernel(GemmArgs g, const float* __restrict__ gamma,
+                                                                      const float* __restrict__ beta,
+                                                                      const float* __restrict__ W3, int ldw3,
+                                                                      const float* __restrict__ b3) {
+  constexpr int BM = 128, BK = 16, LD = BK + 4, C4 = BK / 4;
   constexpr int TILE = (BM + GW_BN) * LD;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -536,7 +510,7 @@ __global__ __launch_bounds__(256 * WM, 2) void gemm_rows512_ln_gelu_kernel(GemmA
   const float* A1 = g.A1;
   const int ktiles = (g.K0 + g.K1) / BK;
 #if defined(GEMM_DIAG) && (GEMM_DIAG & 16)
-  unsigned long long* stamp_base = g.stamps ? g.stamps + ((size_t)blockIdx.x * (4 * WM) + wave) * 8 : nullptr;
+  unsigned long long* stamp_base = g.stamps ? g.stamps + ((size_t)blockIdx.x * 8 + wave) * 8 : nullptr;
   if (g.stamps && lane == 0) {
     unsigned hw, xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
@@ -547,13 +521,12 @@ __global__ __launch_bounds__(256 * WM, 2) void gemm_rows512_ln_gelu_kernel(GemmA
   GEMM_STAMP(0);
 #endif
 
-  // staging: thread -> float4 column s_c4 of tile row s_r0 (weights: rows s_r0 + 128 i).  For the 16-deep tile the
-  // rows are permuted inside blocks of 8 so that the ds_write_b128 is conflict-free (see gemm_nt_kernel).
+  // staging: thread -> float4 column s_c4 of tile row s_r0 (weights: rows s_r0 + 128 i).  The rows are permuted inside
+  // blocks of 8 so that the ds_write_b128 is conflict-free (see gemm_nt_kernel).
   const int s_c4 = (tid % C4) * 4;
   const int q_ = tid / C4;                       // 0..127
-  const int s_r0 = C4 == 4 ? ((q_ & ~7) | ((q_ & 1) << 2) | ((q_ >> 1) & 3)) : q_;
-  const bool stage_a = s_r0 < BM;                // WM = 1: half of the threads carry an A row
-  const size_t ar = (size_t)min(m0 + (stage_a ? s_r0 : 0), g.M - 1);
+  const int s_r0 = (q_ & ~7) | ((q_ & 1) << 2) | ((q_ >> 1) & 3);
+  const size_t ar = (size_t)min(m0 + s_r0, g.M - 1);
   const float* w0p = g.W + (size_t)(s_r0)*g.ldw + s_c4;
   const float* w1p = w0p + (size_t)128 * g.ldw;
   const float* w2p = w0p + (size_t)256 * g.ldw;
@@ -565,7 +538,7 @@ __global__ __launch_bounds__(256 * WM, 2) void gemm_rows512_ln_gelu_kernel(GemmA
     const bool first_ = k0_ < g.K0;                                              \
     const float* ab_ = (first_ ? A0 : A1) + (first_ ? k0_ : k0_ - g.K0) + s_c4;  \
     const size_t ld_ = first_ ? g.lda0 : g.lda1;                                 \
-    if (WM == 2 || stage_a) areg = *reinterpret_cast<const float4*>(ab_ + ar * ld_); \
+    areg = *reinterpret_cast<const float4*>(ab_ + ar * ld_);                     \
     wreg0 = *reinterpret_cast<const float4*>(w0p + k0_);                         \
     wreg1 = *reinterpret_cast<const float4*>(w1p + k0_);                         \
     wreg2 = *reinterpret_cast<const float4*>(w2p + k0_);                         \
@@ -574,7 +547,7 @@ __global__ __launch_bounds__(256 * WM, 2) void gemm_rows512_ln_gelu_kernel(GemmA
 #define GW_STORE(buf_)                                                           \
   do {                                                                           \
     float* bs_ = smem + (buf_) * TILE + BM * LD + s_r0 * LD + s_c4;              \
-    if (WM == 2 || stage_a) *reinterpret_cast<float4*>(smem + (buf_) * TILE + s_r0 * LD + s_c4) = areg; \
+    *reinterpret_cast<float4*>(smem + (buf_) * TILE + s_r0 * LD + s_c4) = areg;  \
     *reinterpret_cast<float4*>(bs_) = wreg0;                                     \
     *reinterpret_cast<float4*>(bs_ + 128 * LD) = wreg1;                          \
     *reinterpret_cast<float4*>(bs_ + 256 * LD) = wreg2;                          \
@@ -728,15 +701,7 @@ __global__ __launch_bounds__(256 * WM, 2) void gemm_rows512_ln_gelu_kernel(GemmA
           float* yp = g.Y + (size_t)row * g.ldy + wn * 128 + l31;
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) {
-            float y = (acc[mt][nt][r] - mu[mt][r]) * rs[j] * ga[nt] + be[nt];
-#if !defined(GW_DIAG) || GW_DIAG < 1  // diagnostic builds (tools/ab_build.sh): 1 = no erf, 2 = no store either
-            y = gfc_gelu(y);
-#endif
-#if !defined(GW_DIAG) || GW_DIAG < 2
-            yp[nt * 32] = y;
-#else
-            if (y == 1234.5678f) yp[nt * 32] = y;
-#endif
+            yp[nt * 32] = gfc_gelu((acc[mt][nt][r] - mu[mt][r]) * rs[j] * ga[nt] + be[nt]);
           }
         }
       }
@@ -836,22 +801,6 @@ __global__ __launch_bounds__(256 * WM, 2) void gemm_rows512_ln_gelu_kernel(GemmA
 #undef FF_STORE
 }
 
-template <int WM>
-static int launch_rows512(const GemmArgs& g, const float* gamma, const float* beta, hipStream_t st) {
-  constexpr int BM = 64 * WM, BK = WM == 2 ? 16 : 8;
-  constexpr size_t lds = (size_t)2 * (BM + GW_BN) * (BK + 4) * sizeof(float);
-  static std::atomic<unsigned long long> lds_ok{0};
-  if (lds > 64 * 1024) gfc_allow_dynamic_lds((const void*)gemm_rows512_ln_gelu_kernel<WM>, lds, lds_ok);
-  GemmArgs gd = g;
-#if defined(GEMM_DIAG) && (GEMM_DIAG & 16)
-  gd.stamps = g_diag_stamps;
-#endif
-  hipLaunchKernelGGL(gemm_rows512_ln_gelu_kernel<WM>, dim3((g.M + BM - 1) / BM), dim3(256 * WM), lds, st, gd, gamma, beta,
-                     (const float*)nullptr, 0, (const float*)nullptr);
-  GFC_LAUNCH_CHECK();
-  return GFC_OK;
-}
-
 extern "C" int gfc_ffn_fused(const float* A0, int lda0, int K0, const float* A1, int lda1, int K1, const float* W0,
                              int ldw0, const float* b0, const float* gamma, const float* beta, const float* W3, int ldw3,
                              const float* b3, const float* residual, float* Y, int ldy, int M, void* stream) {
@@ -866,11 +815,11 @@ extern "C" int gfc_ffn_fused(const float* A0, int lda0, int K0, const float* A1,
   constexpr size_t k1 = (size_t)2 * (128 + GW_BN) * 20, k2 = (size_t)128 * FF_HLD + (size_t)2 * 256 * 20;
   constexpr size_t lds = (k1 > k2 ? k1 : k2) * sizeof(float);
   static std::atomic<unsigned long long> lds_ok{0};
-  gfc_allow_dynamic_lds((const void*)gemm_rows512_ln_gelu_kernel<2, true>, lds, lds_ok);
+  gfc_allow_dynamic_lds((const void*)gemm_rows512_ln_gelu_kernel<true>, lds, lds_ok);
 #if defined(GEMM_DIAG) && (GEMM_DIAG & 16)
   g.stamps = g_diag_stamps;
 #endif
-  hipLaunchKernelGGL((gemm_rows512_ln_gelu_kernel<2, true>), dim3((M + 127) / 128), dim3(512), lds, (hipStream_t)stream, g,
+  hipLaunchKernelGGL(gemm_rows512_ln_gelu_kernel<true>, dim3((M + 127) / 128), dim3(512), lds, (hipStream_t)stream, g,
                      gamma, beta, W3, ldw3, b3);
   GFC_LAUNCH_CHECK();
   return GFC_OK;
@@ -887,11 +836,18 @@ extern "C" int gfc_linear_layernorm_gelu(const float* A0, int lda0, int K0, cons
   g.A0 = A0; g.A1 = A1; g.W = W; g.bias = bias; g.Y = Y;
   g.lda0 = lda0; g.lda1 = lda1; g.ldw = ldw; g.ldy = ldy;
   g.K0 = K0; g.K1 = K1; g.M = M; g.N = N; g.alpha = 1.f;
-  // 128-row / 8-wave tiles by default (same-box A/B at M = 65536: 336 us; 64-row tiles with two workgroups per CU
-  // 357 us -- the 8-deep K tile doubles the barriers; GEMM + LayerNorm pass 390 us).  GFC_FFN_FUSED = 1 forces the
-  // 64-row variant.
-  if (gfc_knobs().ffn_fused == 1) return launch_rows512<1>(g, gamma, beta, (hipStream_t)stream);
-  return launch_rows512<2>(g, gamma, beta, (hipStream_t)stream);
+  // 128-row / 8-wave tiles (same-box A/B at M = 65536: 336 us; 64-row tiles with two workgroups per CU 357 us -- the
+  // 8-deep K tile doubles the barriers; GEMM + LayerNorm pass 390 us)
+  constexpr size_t lds = (size_t)2 * (128 + GW_BN) * 20 * sizeof(float);
+  static std::atomic<unsigned long long> lds_ok{0};
+  gfc_allow_dynamic_lds((const void*)gemm_rows512_ln_gelu_kernel<false>, lds, lds_ok);
+#if defined(GEMM_DIAG) && (GEMM_DIAG & 16)
+  g.stamps = g_diag_stamps;
+#endif
+  hipLaunchKernelGGL(gemm_rows512_ln_gelu_kernel<false>, dim3((M + 127) / 128), dim3(512), lds, (hipStream_t)stream, g,
+                     gamma, beta, (const float*)nullptr, 0, (const float*)nullptr);
+  GFC_LAUNCH_CHECK();
+  return GFC_OK;
 }
 
 template <int NW, int MT, int BK, int MTN = MT>
@@ -904,11 +860,7 @@ static int launch_gemm_t(const GemmArgs& g, int batch, hipStream_t st) {
   if (lds > 64 * 1024) gfc_allow_dynamic_lds((const void*)gemm_nt_kernel<NW, MT, BK, MTN>, lds, lds_ok);
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, batch);
   GemmArgs ga = g;
-  ga.xcd_remap = gfc_knobs().xcd_remap != 0 && (long long)grid.x * grid.y * grid.z >= 16;
-  ga.stagger = gfc_knobs().gemm_stagger;
-  ga.first_round = gfc_device_cus() * 4;
-  ga.wide_stores = gfc_knobs().gemm_epi == 1 && g.ldy % 4 == 0 && (reinterpret_cast<size_t>(g.Y) & 15) == 0 &&
-                   g.strideY % 4 == 0;
+  ga.xcd_remap = (long long)grid.x * grid.y * grid.z >= 16;
 #if defined(GEMM_DIAG) && (GEMM_DIAG & 16)
   ga.stamps = g_diag_stamps;
 #endif

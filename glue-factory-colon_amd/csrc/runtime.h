@@ -4,8 +4,10 @@
 //    the same values;
 //  * per-device facts (CU count) and per-(kernel, device) attributes (dynamic LDS above 64 KB) are keyed by the
 //    current HIP device, so one process may drive several GPUs.
-// Nothing here influences results: the knobs select between kernel variants that are held to the same parity
-// tests (tests/test_gpu_primitives.py::test_gemm_tile_variants_via_knob etc.).
+// The knobs are for tests and tuning: GFC_GEMM_TILE, GFC_ATTN_CFG and GFC_NMS_MODE force a variant that the automatic
+// choice also takes at some problem size, so that tests can cover it on small inputs; GFC_STEM_F43 = 0 selects the
+// F(2x2,3x3) stem, the fallback for the F(4x4,3x3) numerics.  The variants are held to the same parity tests
+// (tests/test_gpu_primitives.py::test_gemm_tile_variants_via_knob etc.).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,16 +15,9 @@
 
 struct GfcKnobs {
   int gemm_tile;     // GFC_GEMM_TILE: 0 = by problem size, 3 = 64x64 tiles everywhere, 4 = 128x128 tiles everywhere
-  int attn_cfg;      // GFC_ATTN_CFG: 0 = automatic
-  int conv_kc;       // GFC_CONV_KC: 0 = automatic
-  int conv_persist;  // GFC_CONV_PERSIST: -1 = automatic
-  int ffn_fused;     // GFC_FFN_FUSED: -1 = automatic, 0 = GEMM + layernorm_gelu pass, 1 = row-owning fused GEMM
-  int ffn_mlp;       // GFC_FFN_MLP: -1 = automatic, 0 = ffn[3] as a GEMM of its own, 1 = whole FFN + residual in one kernel
-  int gemm_epi;      // GFC_GEMM_EPI: 0 = automatic, 1 = float4 stores through the LDS transpose for every epilogue, 2 = direct
-  int gemm_stagger;  // GFC_GEMM_STAGGER: start skew of the first-round GEMM workgroups in units of 8128 cycles per wave slot
+  int attn_cfg;      // GFC_ATTN_CFG: 0 / anything else = by problem size, 1 = 256 queries per workgroup, 2 = 128 queries
   int nms_mode;      // GFC_NMS_MODE: 0 (default) = by problem size, 1 = LDS-image kernel, 2 = streaming kernel (waves walk column bands, rings in registers)
   int stem_f43;      // GFC_STEM_F43: 1 (default) = Winograd F(4x4,3x3) stem when its filters are supplied, 0 = F(2x2,3x3) stem
-  int xcd_remap;     // GFC_XCD_REMAP: 1 (default) = XCD-aware work order (common.h: gfc_xcd_chunk), 0 = dispatch order
 };
 const GfcKnobs& gfc_knobs();
 

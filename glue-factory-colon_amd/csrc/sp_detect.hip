@@ -432,7 +432,7 @@ static int launch_nms(const float* heat, int B, int H, int W, int border, const 
   if (lds > 64 * 1024) gfc_allow_dynamic_lds((const void*)nms_kernel<RAD>, lds, lds_ok);
   dim3 grid(((W + NT - 1) / NT) * ((H + NT - 1) / NT), B);
   hipLaunchKernelGGL(nms_kernel<RAD>, grid, dim3(1024), lds, st, heat, H, W, border, valid_wh, out, cand_thr, cand,
-                     cand_count, gfc_knobs().xcd_remap != 0 && (long long)grid.x * grid.y >= 16);
+                     cand_count, (long long)grid.x * grid.y >= 16);
   GFC_LAUNCH_CHECK();
   return GFC_OK;
 }

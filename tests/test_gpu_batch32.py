@@ -2,7 +2,7 @@
 matcher exactly as `bench.py::step` does (both views in one extractor call of 64 images, `force_num_keypoints`).
 
 At this size the library dispatches, on its own, to the kernel variants the benchmark measures
-(gemm_nt_kernel<2,2,16>, attention_kernel<2,4> / the shared-sim cross kernel, the row-owning FFN GEMM, the
+(gemm_nt_kernel<2,2,16>, attention_kernel<2> / the shared-sim cross kernel, the row-owning FFN GEMM, the
 two-pass assignment tail); smaller test batches never reach them.  Checked here:
   * ALL 32 pairs against THE REFERENCE ITSELF (tests/golden/c2_batch32.npz: the reference's TwoViewPipeline run on
     the same 32 pairs in the build container, make_golden.py::golden_c2_batch32): key points, scores, descriptors,
@@ -113,8 +113,8 @@ def test_c2_batch32_vs_reference_fixture(c2_batch32, golden):
 
 
 def test_c2_batch32_matcher_stage_isolated(c2_batch32):
-    """The matcher call the benchmark makes (ONE call, 32 pairs: attention_kernel<2,4>, gemm_nt_kernel<2,2,16,2>,
-    gemm_rows512_ln_gelu_kernel<2,true>, two-pass assignment tail), element-wise: its own inputs through the CPU
+    """The matcher call the benchmark makes (ONE call, 32 pairs: attention_kernel<2>, gemm_nt_kernel<2,2,16,2>,
+    gemm_rows512_ln_gelu_kernel<true>, two-pass assignment tail), element-wise: its own inputs through the CPU
     oracle's matcher must give the same matches0 / matches1, index by index (lightglue.py:294-319)."""
     _, _, _, _, p0, p1, out = c2_batch32
     sd_lg = weights.lightglue_state_dict(0)
@@ -149,7 +149,7 @@ def test_c2_batch32_batch_invariance(c2_batch32):
     # every image had >= K detections (no random padding), otherwise the comparison below would depend on the RNG
     assert (p0["keypoint_scores"] > 0).all() and (p1["keypoint_scores"] > 0).all()
     with torch.no_grad():
-        for s in range(0, B, 8):  # 8 at a time: other GEMM tile (64x64), other attention variant (<1,4>), no key split
+        for s in range(0, B, 8):  # 8 at a time: other GEMM tile (64x64), other attention variant (<1>), no key split
             q0, q1, o8 = run_batch(ext, mat, v0[s:s + 8], v1[s:s + 8])
             for k in keys_ext:
                 assert torch.equal(q0[k], p0[k][s:s + 8]) and torch.equal(q1[k], p1[k][s:s + 8]), (s, k)

@@ -2,7 +2,7 @@
 GPUs), through extractor and matcher exactly as `bench.py --workload c4` does (both views in one extractor call of
 64 images, `force_num_keypoints`).
 
-Only at this batch does the library dispatch the kernel variants that workload is timed on: `attention_kernel<2,4>` on
+Only at this batch does the library dispatch the kernel variants that workload is timed on: `attention_kernel<2>` on
 2048 x 2048 problems (64 problems x 4 heads x 8 query blocks), the 128 x 128 GEMM tile and the row-owning FFN GEMM on
 131072 rows, the two-sweep assignment tail on a [32, 2049, 2049] matrix (537 MB).  Checked here:
   * 4 of the 32 pairs against THE REFERENCE ITSELF (tests/golden/c4_pairs.npz: the reference's TwoViewPipeline on
@@ -13,7 +13,7 @@ Only at this batch does the library dispatch the kernel variants that workload i
   * 2 of the 32 pairs end to end against the live CPU oracle (reference path restated, oracle/): key-point sets
     (0 unexplained flips), matched coordinate pairs, scores <= 1e-4 (GFC_TEST_ORACLE_PAIRS=9 for the round-5 spread);
   * batch invariance: all 32 pairs identical on every integer output (key points, matches0/1) -- and within 1e-4 on
-    the scores -- to the same pairs run 2 at a time (other GEMM tile, attention_kernel<1,4>).
+    the scores -- to the same pairs run 2 at a time (other GEMM tile, attention_kernel<1>).
 Reference: gluefactory/models/matchers/lightglue.py:422-553, extractors/superpoint_open.py:126-232.
 """
 import os
@@ -113,7 +113,7 @@ def test_c4_batch32_vs_reference_fixture(c4_batch32, golden):
 
 
 def test_c4_batch32_matcher_stage_isolated(c4_batch32):
-    """Rows C4_PAIRS of the ONE matcher call on 32 pairs (attention_kernel<2,4> on 2048 x 2048 problems, 128 x 128 GEMM
+    """Rows C4_PAIRS of the ONE matcher call on 32 pairs (attention_kernel<2> on 2048 x 2048 problems, 128 x 128 GEMM
     tiles, the two-sweep assignment tail), element-wise: the same inputs through the CPU oracle's matcher must give the
     same matches0 / matches1, index by index (lightglue.py:294-319)."""
     _, _, _, _, p0, p1, out = c4_batch32
@@ -151,7 +151,7 @@ def test_c4_batch32_batch_invariance(c4_batch32):
     assert int(ok.sum(1).min()) > 1000
     worst = 0.0
     with torch.no_grad():
-        for s in range(0, B, 2):  # 2 at a time: 64 x 64 GEMM tiles, attention_kernel<1,4>
+        for s in range(0, B, 2):  # 2 at a time: 64 x 64 GEMM tiles, attention_kernel<1>
             q0, q1, o2 = run_batch(ext, mat, v0[s:s + 2], v1[s:s + 2])
             for k in keys_ext_exact:
                 assert torch.equal(q0[k], p0[k][s:s + 2]) and torch.equal(q1[k], p1[k][s:s + 2]), (s, k)

@@ -34,9 +34,9 @@ KERNELS = [
     ("stem_wino43_kernel", "conv_wino43.hip", 48.7),
     ("conv3x3_wino_kernel<true, true", "conv_wino.hip", 70.5),
     ("conv3x3_wino_kernel<false, false", "conv_wino.hip", 70.5),
-    ("gemm_rows512_ln_gelu_kernel<2, true", "gemm.hip", 76.2),
+    ("gemm_rows512_ln_gelu_kernel<true", "gemm.hip", 76.2),
     ("gemm_nt_kernel<2, 2, 16, 2", "gemm.hip", 73.0),
-    ("attention_kernel<2, 4", "attention.hip", 82.3),
+    ("attention_kernel<2>", "attention.hip", 82.3),
 ]
 
 # cycles of matrix-pipe time per instruction and wave (r05_mfma_valu_hybrid.txt: (cycles with 8 per MFMA - 512) / 64)

@@ -1,4 +1,4 @@
-"""Per-wave cycle accounting of attention_kernel<2,4> (diagnostic build -DATT_DIAG, tools/ab_build.sh WORKTREE astamps
+"""Per-wave cycle accounting of attention_kernel<2> (diagnostic build -DATT_DIAG, tools/ab_build.sh WORKTREE astamps
 "-DATT_DIAG"): prologue (Q fragments, first K/V tile), key loop, of which: waiting for
 the staged next tile (global loads + LDS writes) and at the workgroup barrier, epilogue.
 

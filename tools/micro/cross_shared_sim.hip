@@ -1,6 +1,6 @@
 // Round-5 decision experiment (DESIGN.md 8.1 option (a)): bidirectional cross attention with ONE
 // evaluation of sim = qk0 . qk1^T per tile (reference gluefactory/models/matchers/lightglue.py:207-217), timed against
-// today's launch (attention_kernel<2,4>, both directions as two problems, sim evaluated twice).
+// today's launch (attention_kernel<2>, both directions as two problems, sim evaluated twice).
 //
 // One workgroup = 4 waves = 128 rows of image 0 for one (pair, head); wave w owns 32 rows.  Sweep over the columns
 // (key points of image 1) in tiles of 32:

@@ -1,4 +1,4 @@
-# same-box A/B of one environment knob on the whole bench:  bash tools/micro/knob_ab.sh GFC_GEMM_EPI 0 1 [rounds]
+# same-box A/B of one environment knob on the whole bench:  bash tools/micro/knob_ab.sh GFC_NMS_MODE 1 2 [rounds]
 knob=$1; a=$2; b=$3; rounds=${4:-3}
 for i in $(seq $rounds); do
   for v in $a $b; do
