@@ -138,6 +138,9 @@ SIGNATURES = {
     "gfc_sp_mask_scores": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 2),
     "gfc_sp_filter_keypoints": (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] + [c_int] * 2 + [c_void_p, c_float, c_void_p]),
     "gfc_eval_homography_dlt": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p] * 3),
+    "gfc_eval_homography_ransac_workspace_bytes": (c_size_t, [c_int] * 4),
+    "gfc_eval_homography_ransac": (c_int, [c_void_p] * 6 + [c_int] * 3 + [POINTER(c_float)] + [c_int] * 3
+                                   + [ctypes.c_uint64] + [c_void_p] * 8 + [c_size_t, c_void_p]),
     "gfc_preprocess_resize": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] + [c_int] * 4 + [c_void_p]),
     "gfc_lg_layer_workspace_bytes": (c_size_t, [c_int]),
     "gfc_lg_layer": (c_int, [POINTER(LgParams), c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,

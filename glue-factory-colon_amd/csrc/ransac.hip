@@ -1,0 +1,505 @@
+// Robust homography estimation on the GPU: RANSAC with MSAC scoring at T thresholds at once and a local
+// optimisation by the normalised DLT of eval_common.h.  Counterpart of the estimators behind eval_homography_robust
+// (reference gluefactory/eval/utils.py:225-273; there OpenCV / PoseLib on the CPU -- randomised third-party code,
+// parity with them is unpinned).  The algorithm is written down in DESIGN.md ("Robust homography"); a float64
+// restatement of it is tests/ransac_reference.py.
+//
+//   ransac_compact_kernel  one workgroup per pair: the matches (i, m0[i]) with 0 <= m0[i] < N in ascending i
+//                          -> (x0, y0, x1, y1) records + their key-point-0 index + the count n.
+//   ransac_score_kernel<T> one workgroup per (pair, hypothesis range): correspondences staged in LDS, ONE LANE PER
+//                          HYPOTHESIS: counter-based sample -> closed-form 4-point homography (fp64) -> residual of every
+//                          correspondence (all lanes of a wave read the same record: LDS broadcast) feeding T MSAC
+//                          sums in correspondence order -> (score, h) argmin per threshold.
+//   ransac_lo_kernel       one workgroup per (pair, threshold): merge the ranges (score, then h), re-solve the winner,
+//                          up to lo_iters rounds of {inliers -> DLT -> accept iff the MSAC score drops}, outputs.
+// A hypothesis's score is one lane's serial sum and the winner is chosen by (score, h): the result does not depend on
+// the number of ranges, the batch or the launch shape.
+#include "eval_common.h"
+
+#define RS_MAX_T 8
+#define RS_LDS_CORR_BYTES (128 * 1024)
+#define RS_DET_EPS 1e-10
+
+struct rs_thresholds { double t2[RS_MAX_T]; };
+
+// ---- sampler: splitmix64 finaliser as a counter-based generator ---------------------------------------------
+__device__ __host__ __forceinline__ unsigned long long rs_mix64(unsigned long long z) {
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+__device__ __host__ __forceinline__ unsigned long long rs_key(unsigned long long seed, unsigned long long stream) {
+  return rs_mix64(rs_mix64(seed + 0x9E3779B97F4A7C15ull) ^ stream);
+}
+// 4 distinct indices in [0, n), n >= 4: partial Fisher-Yates over a virtual array a[p] = p ("take a[r], move the last
+// live element into the hole"), draws r_j in [0, n - j) by multiply-high of the upper 32 bits.
+__device__ __forceinline__ void rs_sample(unsigned long long key, int h, int n, int& i0, int& i1, int& i2, int& i3) {
+  const unsigned long long base = 4ull * (unsigned long long)h;
+  const int r0 = (int)(((rs_mix64(key + 0x9E3779B97F4A7C15ull * (base + 1)) >> 32) * (unsigned long long)n) >> 32);
+  const int r1 = (int)(((rs_mix64(key + 0x9E3779B97F4A7C15ull * (base + 2)) >> 32) * (unsigned long long)(n - 1)) >> 32);
+  const int r2 = (int)(((rs_mix64(key + 0x9E3779B97F4A7C15ull * (base + 3)) >> 32) * (unsigned long long)(n - 2)) >> 32);
+  const int r3 = (int)(((rs_mix64(key + 0x9E3779B97F4A7C15ull * (base + 4)) >> 32) * (unsigned long long)(n - 3)) >> 32);
+  i0 = r0;
+  const int p0 = r0, v0 = n - 1;  // a[r0] <- a[n-1]
+  i1 = (r1 == p0) ? v0 : r1;
+  const int l1 = n - 2;
+  const int p1 = r1, v1 = (l1 == p0) ? v0 : l1;  // a[r1] <- a[n-2]
+  i2 = (r2 == p1) ? v1 : (r2 == p0) ? v0 : r2;
+  const int l2 = n - 3;
+  const int p2 = r2, v2 = (l2 == p1) ? v1 : (l2 == p0) ? v0 : l2;  // a[r2] <- a[n-3]
+  i3 = (r3 == p2) ? v2 : (r3 == p1) ? v1 : (r3 == p0) ? v0 : r3;
+}
+
+// ---- minimal solve ---------------------------------------------------------------------------------------
+// twice the signed area of the triangle (a, b, c)
+__device__ __forceinline__ double rs_area2(double ax, double ay, double bx, double by, double cx, double cy) {
+  return (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
+}
+
+// Hartley normalisation of 4 points: centroid, mean distance -> sqrt 2 (the scale of find_homography_dlt)
+__device__ __forceinline__ void rs_normalise4(const double* x, const double* y, double* u, double* v, double& mx,
+                                              double& my, double& s) {
+  mx = (((x[0] + x[1]) + x[2]) + x[3]) * 0.25;
+  my = (((y[0] + y[1]) + y[2]) + y[3]) * 0.25;
+  double d = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double ax = x[k] - mx, ay = y[k] - my;
+    d += sqrt(ax * ax + ay * ay);
+  }
+  s = 1.4142135623730951 / (d * 0.25 + 1e-8);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { u[k] = s * (x[k] - mx); v[k] = s * (y[k] - my); }
+}
+
+// The projective map that sends the basis e1, e2, e3, (1,1,1) to the four points: columns l_k * (u_k, v_k, 1), with
+// l = adj([p1 p2 p3]) p4 (Cramer; the common factor det[p1 p2 p3] is an overall scale).  Returns the smallest of the
+// four |triangle areas| (any three points collinear <=> the 8x8 system is singular).
+__device__ __forceinline__ double rs_basis(const double* u, const double* v, double* Bm) {
+  const double d = rs_area2(u[0], v[0], u[1], v[1], u[2], v[2]);
+  const double l0 = rs_area2(u[3], v[3], u[1], v[1], u[2], v[2]);
+  const double l1 = rs_area2(u[0], v[0], u[3], v[3], u[2], v[2]);
+  const double l2 = rs_area2(u[0], v[0], u[1], v[1], u[3], v[3]);
+  Bm[0] = l0 * u[0]; Bm[1] = l1 * u[1]; Bm[2] = l2 * u[2];
+  Bm[3] = l0 * v[0]; Bm[4] = l1 * v[1]; Bm[5] = l2 * v[2];
+  Bm[6] = l0;        Bm[7] = l1;        Bm[8] = l2;
+  return fmin(fmin(fabs(d), fabs(l0)), fmin(fabs(l1), fabs(l2)));
+}
+
+// Homography through 4 correspondences (x0, y0) -> (x1, y1), fp64, closed form on Hartley-normalised points:
+// Hn = B1 adj(B0), H = T1^-1 Hn T0, divided by H[2][2].  false: singular (three points collinear in either image)
+// or a non-finite entry.
+__device__ __forceinline__ bool rs_homography_4pt(const double* x0, const double* y0, const double* x1,
+                                                  const double* y1, double* H) {
+  double u0[4], v0[4], u1[4], v1[4], mx0, my0, s0, mx1, my1, s1, A[9], Bq[9];
+  rs_normalise4(x0, y0, u0, v0, mx0, my0, s0);
+  rs_normalise4(x1, y1, u1, v1, mx1, my1, s1);
+  const double e0 = rs_basis(u0, v0, A);
+  const double e1 = rs_basis(u1, v1, Bq);
+  double C[9];  // adj(A)
+  C[0] = A[4] * A[8] - A[5] * A[7]; C[1] = A[2] * A[7] - A[1] * A[8]; C[2] = A[1] * A[5] - A[2] * A[4];
+  C[3] = A[5] * A[6] - A[3] * A[8]; C[4] = A[0] * A[8] - A[2] * A[6]; C[5] = A[2] * A[3] - A[0] * A[5];
+  C[6] = A[3] * A[7] - A[4] * A[6]; C[7] = A[1] * A[6] - A[0] * A[7]; C[8] = A[0] * A[4] - A[1] * A[3];
+  double h[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) h[r * 3 + c] = (Bq[r * 3] * C[c] + Bq[r * 3 + 1] * C[3 + c]) + Bq[r * 3 + 2] * C[6 + c];
+  double g[9], f[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    g[r * 3 + 0] = h[r * 3 + 0] * s0;
+    g[r * 3 + 1] = h[r * 3 + 1] * s0;
+    g[r * 3 + 2] = (h[r * 3 + 2] - g[r * 3 + 0] * mx0) - g[r * 3 + 1] * my0;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    f[0 * 3 + c] = g[0 * 3 + c] / s1 + mx1 * g[2 * 3 + c];
+    f[1 * 3 + c] = g[1 * 3 + c] / s1 + my1 * g[2 * 3 + c];
+    f[2 * 3 + c] = g[2 * 3 + c];
+  }
+  bool ok = (e0 > RS_DET_EPS) && (e1 > RS_DET_EPS);
+  const double inv = 1.0 / f[8];
+#pragma unroll
+  for (int r = 0; r < 9; ++r) { H[r] = f[r] * inv; ok = ok && isfinite(H[r]); }
+  return ok;
+}
+
+// squared forward transfer error; +inf when the projective denominator is <= 0 or not finite
+__device__ __forceinline__ double rs_residual2(const double* H, double x0, double y0, double x1, double y1) {
+  const double X = (H[0] * x0 + H[1] * y0) + H[2];
+  const double Y = (H[3] * x0 + H[4] * y0) + H[5];
+  const double W = (H[6] * x0 + H[7] * y0) + H[8];
+  const double iw = 1.0 / W;
+  const double dx = X * iw - x1, dy = Y * iw - y1;
+  const double r2 = dx * dx + dy * dy;
+  return (W > 0.0 && W < INFINITY) ? r2 : INFINITY;
+}
+
+// the four sampled correspondences of hypothesis h -> model
+__device__ __forceinline__ bool rs_hypothesis(const float4* corr, unsigned long long key, int h, int n, double* H) {
+  int i0, i1, i2, i3;
+  rs_sample(key, h, n, i0, i1, i2, i3);
+  const float4 c0 = corr[i0], c1 = corr[i1], c2 = corr[i2], c3 = corr[i3];
+  const double x0[4] = {c0.x, c1.x, c2.x, c3.x}, y0[4] = {c0.y, c1.y, c2.y, c3.y};
+  const double x1[4] = {c0.z, c1.z, c2.z, c3.z}, y1[4] = {c0.w, c1.w, c2.w, c3.w};
+  return rs_homography_4pt(x0, y0, x1, y1, H);
+}
+
+// ---- kernels -----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(EM_THREADS) void ransac_compact_kernel(const float* __restrict__ kp0,
+                                                                    const float* __restrict__ kp1,
+                                                                    const long long* __restrict__ m0, int M, int N,
+                                                                    float4* __restrict__ corr, int* __restrict__ cidx,
+                                                                    int* __restrict__ cnt) {
+  __shared__ int wsum[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* p0 = kp0 + (size_t)b * M * 2;
+  const float* p1 = kp1 + (size_t)b * N * 2;
+  const long long* mm = m0 + (size_t)b * M;
+  float4* cc = corr + (size_t)b * M;
+  int* ci = cidx + (size_t)b * M;
+  int base = 0;
+  for (int i0 = 0; i0 < M; i0 += EM_THREADS) {
+    const int i = i0 + tid;
+    long long j = -1;
+    if (i < M) j = mm[i];
+    const bool valid = (i < M) && j > -1 && j < N;
+    const unsigned long long bal = __ballot(valid);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wsum[wave] = __popcll(bal);
+    __syncthreads();
+    int off = base;
+    for (int w = 0; w < wave; ++w) off += wsum[w];
+    const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (valid) {
+      const int pos = off + before;  // < M: at most one slot per valid i
+      cc[pos] = make_float4(p0[2 * i], p0[2 * i + 1], p1[2 * j], p1[2 * j + 1]);
+      ci[pos] = i;
+    }
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) cnt[b] = base;
+}
+
+template <int T>
+__device__ __forceinline__ void rs_score_range(const float4* corr, int n, unsigned long long key, int h_lo, int h_hi,
+                                               const rs_thresholds& th, double* best, int* best_h) {
+#pragma unroll
+  for (int t = 0; t < T; ++t) { best[t] = INFINITY; best_h[t] = 0x7fffffff; }
+  for (int h = h_lo + (int)threadIdx.x; h < h_hi; h += EM_THREADS) {
+    double H[9];
+    const bool ok = rs_hypothesis(corr, key, h, n, H);
+    double acc[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) acc[t] = 0.0;
+    for (int c = 0; c < n; ++c) {
+      const float4 q = corr[c];  // the same address in every lane
+      const double r2 = rs_residual2(H, q.x, q.y, q.z, q.w);
+#pragma unroll
+      for (int t = 0; t < T; ++t) acc[t] += (r2 < th.t2[t]) ? r2 : th.t2[t];
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const double s = ok ? acc[t] : INFINITY;
+      if (s < best[t]) { best[t] = s; best_h[t] = h; }
+    }
+  }
+}
+
+template <int T>
+__global__ __launch_bounds__(EM_THREADS) void ransac_score_kernel(const float4* __restrict__ corr_all,
+                                                                  const int* __restrict__ cnt,
+                                                                  const long long* __restrict__ stream_id,
+                                                                  unsigned long long seed, int M, int S, int NH,
+                                                                  int use_lds, rs_thresholds th,
+                                                                  double* __restrict__ part_score,
+                                                                  int* __restrict__ part_h) {
+  extern __shared__ __attribute__((aligned(16))) float4 lds_corr[];
+  __shared__ double ws[4 * RS_MAX_T];
+  __shared__ int wh[4 * RS_MAX_T];
+  const int b = blockIdx.x / S, s = blockIdx.x % S, tid = threadIdx.x;
+  const int n = cnt[b];
+  const float4* corr = corr_all + (size_t)b * M;
+  double* ps = part_score + (size_t)blockIdx.x * T;
+  int* ph = part_h + (size_t)blockIdx.x * T;
+  if (n < 4) {
+    if (tid < T) { ps[tid] = INFINITY; ph[tid] = -1; }
+    return;
+  }
+  const unsigned long long key = rs_key(seed, stream_id ? (unsigned long long)stream_id[b] : (unsigned long long)b);
+  const int chunk = (NH + S - 1) / S;
+  const int h_lo = s * chunk, h_hi = min(NH, h_lo + chunk);
+  double best[T];
+  int best_h[T];
+  if (use_lds) {
+    for (int c = tid; c < n; c += EM_THREADS) lds_corr[c] = corr[c];
+    __syncthreads();
+    rs_score_range<T>(lds_corr, n, key, h_lo, h_hi, th, best, best_h);
+  } else {
+    rs_score_range<T>(corr, n, key, h_lo, h_hi, th, best, best_h);
+  }
+  // argmin over the block by (score, h)
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    double sc = best[t];
+    int hh = best_h[t];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double os = __shfl_xor(sc, o, 64);
+      const int oh = __shfl_xor(hh, o, 64);
+      if (os < sc || (os == sc && oh < hh)) { sc = os; hh = oh; }
+    }
+    if ((tid & 63) == 0) { ws[(tid >> 6) * RS_MAX_T + t] = sc; wh[(tid >> 6) * RS_MAX_T + t] = hh; }
+  }
+  __syncthreads();
+  if (tid < T) {
+    double sc = ws[tid];
+    int hh = wh[tid];
+    for (int w = 1; w < 4; ++w) {
+      const double os = ws[w * RS_MAX_T + tid];
+      const int oh = wh[w * RS_MAX_T + tid];
+      if (os < sc || (os == sc && oh < hh)) { sc = os; hh = oh; }
+    }
+    ps[tid] = sc;
+    ph[tid] = (sc < INFINITY) ? hh : -1;
+  }
+}
+
+// MSAC score of H over the n correspondences, block-wide (thread-strided partial sums, then block_sum_f64)
+__device__ __forceinline__ double rs_block_msac(const double* H, const float4* corr, int n, double t2, double* red,
+                                                int tid) {
+  double v[1] = {0.0};
+  for (int c = tid; c < n; c += EM_THREADS) {
+    const float4 q = corr[c];
+    const double r2 = rs_residual2(H, q.x, q.y, q.z, q.w);
+    v[0] += (r2 < t2) ? r2 : t2;
+  }
+  block_sum_f64<1>(v, red, tid);
+  return v[0];
+}
+
+__global__ __launch_bounds__(EM_THREADS) void ransac_lo_kernel(
+    const float4* __restrict__ corr_all, const int* __restrict__ cidx_all, const int* __restrict__ cnt,
+    const long long* __restrict__ m0, const long long* __restrict__ stream_id, unsigned long long seed, int M, int N,
+    int S, int T, int lo_iters, rs_thresholds th, const double* __restrict__ part_score,
+    const int* __restrict__ part_h, const float* __restrict__ Hgt, const float* __restrict__ size0,
+    double* __restrict__ Hout, unsigned char* __restrict__ inl_out, int* __restrict__ ninl_out,
+    unsigned char* __restrict__ success_out, int* __restrict__ besth_out, double* __restrict__ Hmin_out,
+    float* __restrict__ err_out) {
+  __shared__ double red[4 * 45];
+  __shared__ double A[81], V[81];
+  __shared__ double sH[9];
+  __shared__ int sflag;
+  const int b = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
+  const size_t o = blockIdx.x;  // (b, t)
+  const int n = cnt[b];
+  const float4* corr = corr_all + (size_t)b * M;
+  const int* cidx = cidx_all + (size_t)b * M;
+  const long long* mm = m0 + (size_t)b * M;
+  unsigned char* inl = inl_out + o * M;
+  double t2 = th.t2[0];
+#pragma unroll
+  for (int q = 1; q < RS_MAX_T; ++q) t2 = (q == t) ? th.t2[q] : t2;
+  // winner over the hypothesis ranges: lowest score, ties to the lower h
+  double bs = INFINITY;
+  int bh = -1;
+  if (n >= 4)
+    for (int s = 0; s < S; ++s) {
+      const double os = part_score[((size_t)b * S + s) * T + t];
+      const int oh = part_h[((size_t)b * S + s) * T + t];
+      if (oh >= 0 && (os < bs || (os == bs && oh < bh))) { bs = os; bh = oh; }
+    }
+  double cur[9];
+  bool ok = bh >= 0;
+  if (ok) {
+    const unsigned long long key = rs_key(seed, stream_id ? (unsigned long long)stream_id[b] : (unsigned long long)b);
+    ok = rs_hypothesis(corr, key, bh, n, cur);
+  }
+  if (!ok) {  // uniform over the block
+    for (int i = tid; i < M; i += EM_THREADS) inl[i] = 0;
+    if (tid < 9) { Hout[o * 9 + tid] = (tid % 4 == 0) ? 1.0 : 0.0; Hmin_out[o * 9 + tid] = (tid % 4 == 0) ? 1.0 : 0.0; }
+    if (tid == 0) {
+      ninl_out[o] = 0; success_out[o] = 0; besth_out[o] = -1;
+      if (err_out) err_out[o] = INFINITY;
+    }
+    return;
+  }
+  if (tid < 9) Hmin_out[o * 9 + tid] = cur[tid];
+  double cur_score = rs_block_msac(cur, corr, n, t2, red, tid);
+  for (int it = 0; it < lo_iters; ++it) {
+    // normalised DLT over the inliers of the current model (unit weights), as dlt_kernel
+    double s5[5] = {0, 0, 0, 0, 0};
+    for (int c = tid; c < n; c += EM_THREADS) {
+      const float4 q = corr[c];
+      if (rs_residual2(cur, q.x, q.y, q.z, q.w) < t2) { s5[0] += 1.0; s5[1] += q.x; s5[2] += q.y; s5[3] += q.z; s5[4] += q.w; }
+    }
+    block_sum_f64<5>(s5, red, tid);
+    const double ni = s5[0];
+    if (ni < 4.0) break;
+    const double mx0 = s5[1] / ni, my0 = s5[2] / ni, mx1 = s5[3] / ni, my1 = s5[4] / ni;
+    double d2[2] = {0, 0};
+    for (int c = tid; c < n; c += EM_THREADS) {
+      const float4 q = corr[c];
+      if (rs_residual2(cur, q.x, q.y, q.z, q.w) < t2) {
+        const double ax = q.x - mx0, ay = q.y - my0, bx = q.z - mx1, by = q.w - my1;
+        d2[0] += sqrt(ax * ax + ay * ay);
+        d2[1] += sqrt(bx * bx + by * by);
+      }
+    }
+    block_sum_f64<2>(d2, red, tid);
+    const double sc_a = 1.4142135623730951 / (d2[0] / ni + 1e-8), sc_b = 1.4142135623730951 / (d2[1] / ni + 1e-8);
+    double acc[45];
+#pragma unroll
+    for (int q = 0; q < 45; ++q) acc[q] = 0.0;
+    for (int c = tid; c < n; c += EM_THREADS) {
+      const float4 q = corr[c];
+      if (rs_residual2(cur, q.x, q.y, q.z, q.w) < t2)
+        dlt_accumulate(acc, 1.0, sc_a * (q.x - mx0), sc_a * (q.y - my0), sc_b * (q.z - mx1), sc_b * (q.w - my1));
+    }
+    block_sum_f64<45>(acc, red, tid);
+    if (tid == 0) {
+      double f[9];
+      dlt_solve(acc, A, V, sc_a, mx0, my0, sc_b, mx1, my1, f);
+      const double inv = 1.0 / f[8];
+      bool fin = true;
+      for (int r = 0; r < 9; ++r) { sH[r] = f[r] * inv; fin = fin && isfinite(sH[r]); }
+      sflag = fin ? 1 : 0;
+    }
+    __syncthreads();
+    double cand[9];
+#pragma unroll
+    for (int r = 0; r < 9; ++r) cand[r] = sH[r];
+    const int fin = sflag;
+    __syncthreads();
+    if (!fin) break;
+    const double cand_score = rs_block_msac(cand, corr, n, t2, red, tid);
+    if (!(cand_score < cur_score)) break;
+#pragma unroll
+    for (int r = 0; r < 9; ++r) cur[r] = cand[r];
+    cur_score = cand_score;
+  }
+  // outputs: inliers in key-point-0 indexing (every i is written exactly once: unmatched rows here, matched rows below)
+  for (int i = tid; i < M; i += EM_THREADS) {
+    const long long j = mm[i];
+    if (!(j > -1 && j < N)) inl[i] = 0;
+  }
+  double cntv[1] = {0.0};
+  for (int c = tid; c < n; c += EM_THREADS) {
+    const float4 q = corr[c];
+    const bool in = rs_residual2(cur, q.x, q.y, q.z, q.w) < t2;
+    inl[cidx[c]] = in ? 1 : 0;  // cidx[c] < M by construction (ransac_compact_kernel)
+    cntv[0] += in ? 1.0 : 0.0;
+  }
+  block_sum_f64<1>(cntv, red, tid);
+  if (tid == 0) {
+    float Hf[9];
+    bool fin = true;
+    for (int r = 0; r < 9; ++r) { Hf[r] = (float)cur[r]; fin = fin && isfinite(Hf[r]); }
+    for (int r = 0; r < 9; ++r) Hout[o * 9 + r] = cur[r];  // fp64, as computed; the corner error is fp32 like dlt_kernel's
+    ninl_out[o] = (int)cntv[0];
+    success_out[o] = 1;
+    besth_out[o] = bh;
+    if (err_out) err_out[o] = fin ? corner_error(Hf, Hgt + (size_t)b * 9, size0[b * 2], size0[b * 2 + 1]) : INFINITY;
+  }
+}
+
+// ---- C ABI -------------------------------------------------------------------------------------------------
+// Hypothesis ranges per pair: ceil(512 / B) of them, so that a small batch still fills the device, but at most
+// floor(NH / 256): a range (ceil(NH / S) hypotheses, the last one what is left) then has at least one hypothesis per
+// lane whenever NH >= 256.  The winner does not depend on S.
+static int rs_splits(int B, int NH) {
+  const int want = (512 + B - 1) / B, most = NH / EM_THREADS;
+  return (want < most ? want : most) < 1 ? 1 : (want < most ? want : most);
+}
+
+struct rs_layout { size_t corr, cidx, cnt, pscore, ph, total; };
+static rs_layout rs_plan(int B, int M, int T, int NH) {
+  rs_layout L;
+  const size_t S = (size_t)rs_splits(B, NH);
+  size_t off = 0;
+  L.corr = off; off += gfc_align((size_t)B * M * sizeof(float4));
+  L.cidx = off; off += gfc_align((size_t)B * M * sizeof(int));
+  L.cnt = off; off += gfc_align((size_t)B * sizeof(int));
+  L.pscore = off; off += gfc_align((size_t)B * S * T * sizeof(double));
+  L.ph = off; off += gfc_align((size_t)B * S * T * sizeof(int));
+  L.total = off;
+  return L;
+}
+
+extern "C" size_t gfc_eval_homography_ransac_workspace_bytes(int B, int M, int T, int num_hypotheses) {
+  if (B <= 0 || M < 0 || T <= 0 || T > RS_MAX_T || num_hypotheses <= 0) return 0;
+  return rs_plan(B, M, T, num_hypotheses).total;
+}
+
+template <int T>
+static int rs_launch_score(int blocks, size_t lds, hipStream_t st, const float4* corr, const int* cnt,
+                            const long long* stream_id, unsigned long long seed, int M, int S, int NH, int use_lds,
+                            const rs_thresholds& th, double* ps, int* ph) {
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)ransac_score_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return GFC_ERR_LAUNCH;
+  hipLaunchKernelGGL(ransac_score_kernel<T>, dim3(blocks), dim3(EM_THREADS), lds, st, corr, cnt, stream_id, seed, M, S, NH,
+                     use_lds, th, ps, ph);
+  return GFC_OK;
+}
+
+extern "C" int gfc_eval_homography_ransac(const float* kp0, const float* kp1, const int64_t* m0,
+                                          const int64_t* stream_id, const float* H_gt, const float* image_size0, int B,
+                                          int M, int N, const float* thresholds, int T, int num_hypotheses, int lo_iters,
+                                          uint64_t seed, double* H_out, uint8_t* inliers, int32_t* num_inliers,
+                                          uint8_t* success, int32_t* best_hypothesis, double* H_minimal, float* err_out,
+                                          void* ws, size_t ws_bytes, void* stream) {
+  if (B <= 0 || M < 0 || N < 0 || T <= 0 || T > RS_MAX_T || num_hypotheses <= 0 || lo_iters < 0) return GFC_ERR_INVALID;
+  // an empty side has nothing to point at: its arrays may be NULL
+  if ((M > 0 && (!kp0 || !m0 || !inliers)) || (N > 0 && !kp1) || !thresholds || !H_out || !num_inliers || !success ||
+      !best_hypothesis || !H_minimal || !ws)
+    return GFC_ERR_INVALID;
+  if ((H_gt == nullptr) != (image_size0 == nullptr) || (H_gt == nullptr) != (err_out == nullptr)) return GFC_ERR_INVALID;
+  if ((size_t)B * (size_t)T > 0x7fffffffull || (size_t)B * (size_t)rs_splits(B, num_hypotheses) > 0x7fffffffull)
+    return GFC_ERR_INVALID;
+  rs_thresholds th;
+  for (int t = 0; t < RS_MAX_T; ++t) {
+    const float v = thresholds[t < T ? t : T - 1];
+    if (!(v > 0.f) || !(v < INFINITY)) return GFC_ERR_INVALID;
+    th.t2[t] = (double)v * (double)v;
+  }
+  const rs_layout L = rs_plan(B, M, T, num_hypotheses);
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
+  char* w = (char*)ws;
+  float4* corr = (float4*)(w + L.corr);
+  int* cidx = (int*)(w + L.cidx);
+  int* cnt = (int*)(w + L.cnt);
+  double* ps = (double*)(w + L.pscore);
+  int* ph = (int*)(w + L.ph);
+  hipStream_t st = (hipStream_t)stream;
+  const int S = rs_splits(B, num_hypotheses);
+  const long long* sid = (const long long*)stream_id;
+  hipLaunchKernelGGL(ransac_compact_kernel, dim3(B), dim3(EM_THREADS), 0, st, kp0, kp1, (const long long*)m0, M, N, corr,
+                     cidx, cnt);
+  GFC_LAUNCH_CHECK();
+  const size_t corr_bytes = (size_t)M * sizeof(float4);
+  const int use_lds = corr_bytes <= RS_LDS_CORR_BYTES ? 1 : 0;  // beyond: the records are read through L2
+  const size_t lds = use_lds ? corr_bytes : 0;
+  const int blocks = B * S;
+  int rc;
+  switch (T) {
+    case 1: rc = rs_launch_score<1>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
+    case 2: rc = rs_launch_score<2>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
+    case 3: rc = rs_launch_score<3>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
+    case 4: rc = rs_launch_score<4>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
+    case 5: rc = rs_launch_score<5>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
+    case 6: rc = rs_launch_score<6>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
+    case 7: rc = rs_launch_score<7>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
+    default: rc = rs_launch_score<8>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
+  }
+  if (rc != GFC_OK) return rc;
+  GFC_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ransac_lo_kernel, dim3(B * T), dim3(EM_THREADS), 0, st, corr, cidx, cnt, (const long long*)m0, sid,
+                     (unsigned long long)seed, M, N, S, T, lo_iters, th, ps, ph, H_gt, image_size0, H_out, inliers,
+                     num_inliers, success, best_hypothesis, H_minimal, err_out);
+  GFC_LAUNCH_CHECK();
+  return GFC_OK;
+}

@@ -3,14 +3,18 @@
 -> files decoded on the host (`hpatches.HPatches`, `image_io`) -> images preprocessed on the GPU (`HostImageFeeder`) ->
 `export_predictions` (pair batches, a sequence's reference image extracted once, pairs sharded over the ranks with one
 gather) -> `predictions.h5` in the reference's layout -> per-pair match metrics and DLT homography error on the GPU
-(`eval_utils`) -> the reference's summaries (`med_*`, `mean_*`, `H_error_dlt@{1,3,5}px`).
+(`eval_utils`) -> the reference's summaries (`med_*`, `mean_*`, `H_error_dlt@{1,3,5}px`), and -- with an estimator selected
+(`eval_conf={"estimator": "gfc_amd", "ransac_th": -1}`, `--estimator gfc_amd`) -- the robust homography of
+eval/hpatches.py:144-172: RANSAC on the GPU for every threshold of the sweep in one kernel call per key-point-count
+group, the best threshold by mean AUC, `H_error_ransac@{1,3,5}px`, `H_error_ransac_mAA`, `ransac_inl`, `ransac_inl%`.
 
     python -m glue_factory_colon_amd.eval_hpatches --data_dir /data/hpatches-sequences-release \\
-        --extractor_weights superpoint_v6_from_tf.pth --matcher_weights superpoint_lightglue.pth [--gpus 8]
+        --extractor_weights superpoint_v6_from_tf.pth --matcher_weights superpoint_lightglue.pth [--gpus 8] \\
+        [--estimator gfc_amd --ransac_th -1]
 
-What is NOT here: the robust estimators of `eval_homography_robust` (eval/hpatches.py:146-152: poselib / OpenCV RANSAC,
-external CPU libraries absent from this image) and with them `H_error_ransac@*`; figures.  Everything that is here keeps
-the reference's names, so a results table lines up key by key.
+The robust estimator is this package's own (csrc/ransac.hip), not OpenCV's or PoseLib's (randomised CPU libraries,
+absent here): the `H_error_ransac*` numbers are NOT pinned against either.  What is NOT here: figures.  Everything that
+is here keeps the reference's names, so a results table lines up key by key.
 """
 import argparse
 import json
@@ -50,11 +54,46 @@ def cal_error_auc(errors, thresholds):
     return aucs
 
 
+ROBUST_KEYS = ("H_error_ransac", "ransac_inl", "ransac_inl%")
+
+
+def med_mean_summaries(results):
+    """`med_<key>` / `mean_<key>` (3 decimals) of every numeric per-pair list."""
+    summaries = {}
+    for k, v in results.items():
+        arr = np.array(v)
+        if not np.issubdtype(arr.dtype, np.number):
+            continue
+        summaries[f"med_{k}"] = round(float(np.median(arr)), 3)
+        summaries[f"mean_{k}"] = round(float(np.mean(arr)), 3)
+    return summaries
+
+
+def robust_summaries(per_threshold, auc_ths=(1, 3, 5), key="H_error_ransac", unit="px"):
+    """{threshold: {key: per-pair list}} -> (summaries, best threshold).  The threshold reported is the one whose AUCs
+    of `key` have the highest mean (the first such on a tie), as the reference's evaluation chooses it
+    (eval/utils.py:305-331); the summaries are `<key>@<t><unit>`, `<key>_mAA` and med_ / mean_ of its lists."""
+    best_th, best_aucs, best_maa = None, None, -1.0
+    for th, lists in per_threshold.items():
+        aucs = cal_error_auc(lists[key], list(auc_ths))
+        if float(np.mean(aucs)) > best_maa:
+            best_th, best_aucs, best_maa = th, aucs, float(np.mean(aucs))
+    summaries = {f"{key}@{t}{unit}": float(a) for t, a in zip(auc_ths, best_aucs)}
+    summaries[f"{key}_mAA"] = best_maa
+    summaries.update(med_mean_summaries(per_threshold[best_th]))
+    return summaries, best_th
+
+
 class HPatchesPipeline:
     export_keys = EXPORT_KEYS
     optional_export_keys = OPTIONAL_EXPORT_KEYS
 
-    def __init__(self, data_conf=None, pair_batch=32, num_workers=2):
+    def __init__(self, data_conf=None, pair_batch=32, num_workers=2, eval_conf=None):
+        self.eval_conf = dict(eval_conf or {})
+        if self.eval_conf.get("estimator") is not None and self.eval_conf["estimator"] not in eval_utils.RANSAC_ESTIMATORS:
+            raise ValueError(f"unknown homography estimator {self.eval_conf['estimator']!r}: available here: "
+                             f"{list(eval_utils.RANSAC_ESTIMATORS)}")
+        self._robust_conf()  # refuses a bad threshold list here, not in the middle of an evaluation
         self.data_conf = {**DEFAULT_DATA_CONF, **dict(data_conf or {})}
         self.pair_batch, self.num_workers = int(pair_batch), int(num_workers)
         self.dataset = hpatches.HPatches(self.data_conf)
@@ -69,7 +108,8 @@ class HPatchesPipeline:
         return pred_file
 
     def run_eval(self, pred_file, device="cuda"):
-        """eval/hpatches.py:112-176 without the robust estimators -> (summaries, results).  The reference walks the list
+        """eval/hpatches.py:112-176 -> (summaries, results); the robust part only with `eval_conf["estimator"]` (then
+        `results["pose_results"][th]` also holds every tested threshold's per-pair lists).  The reference walks the list
         pair by pair (CacheLoader -> eval_matches_homography -> eval_homography_dlt); the same per-pair arithmetic runs
         here for all pairs with equal key-point counts in ONE call of each kernel (one workgroup per pair either way:
         the results do not depend on the grouping), with the cached key points put back into the coordinates of the
@@ -81,6 +121,9 @@ class HPatchesPipeline:
         records = load_predictions(pred_file)
         metas = [self.dataset.meta(i) for i in range(len(self.dataset))]
         per_pair = [None] * len(metas)
+        robust = self._robust_conf()
+        pose_results = {th: {k: [float("inf") if k == "H_error_ransac" else 0.0] * len(metas) for k in ROBUST_KEYS}
+                        for th in (robust["thresholds"] if robust else [])}
         groups = defaultdict(list)
         for i, meta in enumerate(metas):
             rec = records[meta["name"]]
@@ -107,6 +150,16 @@ class HPatchesPipeline:
                     v = metrics[j, c].item()
                     per_pair[i][key] = int(v) if key == "num_matches" else float(v)
                 per_pair[i]["H_error_dlt"] = float(err[j])
+            if robust:  # every threshold of the sweep in ONE call; a pair's random stream is its dataset index
+                rr = eval_utils.homography_ransac(H, kp0, kp1, m0, size0, robust["thresholds"], stream_id=idxs,
+                                                  **robust["options"])
+                r_err, r_inl = rr["error"].cpu(), rr["num_inliers"].cpu()
+                n_match = ((m0 > -1) & (m0 < kp1.shape[1])).sum(1).cpu()
+                for t, th in enumerate(robust["thresholds"]):
+                    for j, i in enumerate(idxs):
+                        pose_results[th]["H_error_ransac"][i] = float(r_err[j, t])
+                        pose_results[th]["ransac_inl"][i] = float(r_inl[j, t])
+                        pose_results[th]["ransac_inl%"][i] = float(r_inl[j, t]) / max(int(n_match[j]), 1)
         results = defaultdict(list)
         for i, meta in enumerate(metas):
             results_i = {k: per_pair[i][k] for k in (*eval_utils.RESULT_KEYS, "H_error_dlt") if k in per_pair[i]}
@@ -115,23 +168,32 @@ class HPatchesPipeline:
             results_i["scenes"] = meta["scene"]
             for k, v in results_i.items():
                 results[k].append(v)
-        summaries = {}
-        for k, v in results.items():
-            arr = np.array(v)
-            if not np.issubdtype(arr.dtype, np.number):
-                continue
-            summaries[f"med_{k}"] = round(float(np.median(arr)), 3)
-            summaries[f"mean_{k}"] = round(float(np.mean(arr)), 3)
+        summaries = med_mean_summaries(results)
         if "H_error_dlt" in results:
             for th, auc in zip([1, 3, 5], cal_error_auc(results["H_error_dlt"], [1, 3, 5])):
                 summaries[f"H_error_dlt@{th}px"] = float(auc)
+        if robust:
+            pose_summaries, best_th = robust_summaries(pose_results)
+            # per-pair lists at the best threshold, as the reference; every threshold's lists under "pose_results"
+            results = {**results, **pose_results[best_th], "pose_results": pose_results}
+            summaries = {**summaries, **pose_summaries}
         return summaries, dict(results)
+
+    def _robust_conf(self):
+        """None without an estimator; else the thresholds (eval/hpatches.py:118-122) and the estimator's options."""
+        if self.eval_conf.get("estimator") is None:
+            return None
+        ths = eval_utils.ransac_thresholds(self.eval_conf.get("ransac_th", -1))
+        return {"thresholds": ths,
+                "options": {k: self.eval_conf[k] for k in ("num_hypotheses", "lo_iters", "seed") if k in self.eval_conf}}
 
     def run_eval_pairwise(self, pred_file, device="cuda"):
         """The reference's own loop shape (one pair at a time through CacheLoader and the drop-in `eval_*` functions):
         kept as the check of `run_eval` (tests/test_hpatches_reader.py)."""
         cache = CacheLoader({"path": str(pred_file), "collate": None, "add_data_path": False, "device": str(device)}).eval()
         results = defaultdict(list)
+        robust = self._robust_conf()
+        pose_results = defaultdict(lambda: defaultdict(list))
         for i in range(len(self.dataset)):
             data = self.dataset.meta(i)
             on_dev = {"name": [data["name"]], "view0": {"scales": data["view0"]["scales"][None].to(device)},
@@ -140,9 +202,17 @@ class HPatchesPipeline:
             ev = {"H_0to1": data["H_0to1"].to(device), "view0": {"image_size": data["view0"]["image_size"].to(device)}}
             results_i = {**eval_utils.eval_matches_homography(ev, pred), **eval_utils.eval_homography_dlt(ev, pred)}
             results_i["names"] = data["name"]
+            for th in (robust["thresholds"] if robust else []):  # the reference's loop: one estimate per threshold
+                rob = eval_utils.eval_homography_robust(ev, pred, {"estimator": self.eval_conf["estimator"], "ransac_th": th,
+                                                                   "stream_id": i, **robust["options"]})
+                for k, v in rob.items():
+                    pose_results[th][k].append(v)
             for k, v in results_i.items():
                 results[k].append(v)
-        return dict(results)
+        results = dict(results)
+        if robust:
+            results["pose_results"] = {th: dict(r) for th, r in pose_results.items()}
+        return results
 
     def run(self, experiment_dir, model, overwrite=False):
         """Predictions (all ranks), then the evaluation on rank 0.  Returns (summaries, results) on rank 0, (None, None)
@@ -190,6 +260,9 @@ def main(argv=None):
     ap.add_argument("--overwrite", action="store_true")
     ap.add_argument("--profile_calls", action="store_true",
                     help="the reference's per-call device synchronisations and timing keys (slower: no host / GPU overlap)")
+    ap.add_argument("--estimator", default=None, choices=[None, *eval_utils.RANSAC_ESTIMATORS],
+                    help="robust homography estimator for H_error_ransac* (default: none, DLT only)")
+    ap.add_argument("--ransac_th", type=float, default=-1.0, help="inlier threshold in pixels; <= 0: the sweep 0.5 .. 3.0")
     ap.add_argument("--gpus", type=int, default=1, help="> 1 without a launcher: this process starts the ranks itself")
     args = ap.parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -207,7 +280,8 @@ def main(argv=None):
     rank, world, local = sharding.init_from_env("nccl") if "WORLD_SIZE" in os.environ else (0, 1, 0)
     torch.cuda.set_device(local)
     pipe = HPatchesPipeline({"data_dir": args.data_dir, "subset": args.subset}, pair_batch=args.pair_batch,
-                            num_workers=args.num_workers)
+                            num_workers=args.num_workers,
+                            eval_conf={"estimator": args.estimator, "ransac_th": args.ransac_th} if args.estimator else None)
     model = build_model(args.extractor_weights, args.matcher_weights, official=not args.open,
                         profile_calls=args.profile_calls).to(f"cuda:{local}")
     summaries, _ = pipe.run(args.experiment_dir, model, overwrite=args.overwrite)

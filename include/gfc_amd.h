@@ -569,6 +569,26 @@ int gfc_eval_homography_dlt(const float* kp0, const float* kp1, const int64_t* m
                             const float* H_gt, const float* image_size0, int B, int M, int N, float* H_out,
                             float* err_out, void* stream);
 
+/* Robust homography from the predicted matches: RANSAC, MSAC-scored at T thresholds in one pass, locally optimised by
+ * the normalised DLT above (DESIGN.md "Robust homography"; the estimator behind eval_homography_robust,
+ * gluefactory/eval/utils.py:225-273 -- there OpenCV / PoseLib: parity with either is unpinned).  kp0 [B,M,2],
+ * kp1 [B,N,2], m0 [B,M] int64 (a match is 0 <= m0[i] < N), stream_id [B] int64 (nullable: 0..B-1) names the random
+ * stream of a pair: with (seed, stream_id) fixed a pair's result does not depend on the batch it is in.  H_gt [B,9] and
+ * image_size0 [B,2] are given together with err_out or all three are NULL.  thresholds: T values in pixels in HOST
+ * memory, 1 <= T <= 8, each positive and finite.  Outputs per (pair, threshold): H_out [B,T,9] fp64 (the model as computed) divided by H[2][2];
+ * inliers [B,T,M] uint8 over key points 0; num_inliers [B,T] int32; success [B,T] uint8; best_hypothesis [B,T] int32
+ * (the winning sample, -1 on failure); H_minimal [B,T,9] fp64 (its model before the local optimisation); err_out [B,T]
+ * the corner error of H_out rounded to fp32, as gfc_eval_homography_dlt.  Fewer than 4 matches or no non-degenerate sample: success 0, H identity,
+ * no inliers, error +inf.  GFC_ERR_INVALID (nothing launched): B <= 0, M < 0, N < 0, T outside 1..8,
+ * num_hypotheses <= 0, lo_iters < 0, a threshold that is not positive and finite, a NULL required pointer. */
+size_t gfc_eval_homography_ransac_workspace_bytes(int B, int M, int T, int num_hypotheses);
+int gfc_eval_homography_ransac(const float* kp0, const float* kp1, const int64_t* m0, const int64_t* stream_id,
+                               const float* H_gt, const float* image_size0, int B, int M, int N,
+                               const float* thresholds, int T, int num_hypotheses, int lo_iters, uint64_t seed,
+                               double* H_out, uint8_t* inliers, int32_t* num_inliers, uint8_t* success,
+                               int32_t* best_hypothesis, double* H_minimal, float* err_out, void* ws, size_t ws_bytes,
+                               void* stream);
+
 /* Image preprocessing ("next" row rank 1): [uint8 -> float /255 ->] antialiased bilinear resize, fused.
  * src: src_is_u8_hwc != 0: B interleaved HxWxC byte images (bgr != 0 reverses the channel order, as read_image does
  * after cv2.imread, utils/image.py:135-145), converted like numpy_image_to_torch (image.py:148-156); else B planar
