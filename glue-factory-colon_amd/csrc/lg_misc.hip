@@ -647,37 +647,41 @@ __global__ __launch_bounds__(256) void nn_top2_cols_kernel(const float* __restri
   }
 }
 
-__device__ __forceinline__ int nn_accept(float s1, float s2, int idx, int ncand, float ratio, float dist_th) {
+// ratio_sq / dist_sq: the SQUARED thresholds as the reference's fp32 comparison sees them -- squared in double and
+// rounded to fp32 once (gfc_nn_match does that on the host).  Squaring the fp32 threshold here instead gives another
+// value (0.9: 0.80999994 against 0.81000000), and the two disagree on a test met with equality, e.g. d1 = 81/64,
+// d2 = 100/64 under ratio_thresh 0.9.  <= 0 disables a test.
+__device__ __forceinline__ int nn_accept(float s1, float s2, int idx, int ncand, float ratio_sq, float dist_sq) {
   // find_nn, nearest_neighbor_matcher.py:15-31
   if (ncand == 0) return -1;
   const float d1 = 2.f * (1.f - s1), d2 = 2.f * (1.f - s2);
   bool ok = true;
-  if (ratio > 0.f && ncand > 1) ok = ok && (d1 <= (ratio * ratio) * d2);
-  if (dist_th > 0.f) ok = ok && (d1 <= dist_th * dist_th);
+  if (ratio_sq > 0.f && ncand > 1) ok = ok && (d1 <= ratio_sq * d2);
+  if (dist_sq > 0.f) ok = ok && (d1 <= dist_sq);
   return ok ? idx : -1;
 }
 
 __global__ void nn_match_kernel(const float* __restrict__ rb, const int* __restrict__ ra, const float* __restrict__ rs,
                                 const float* __restrict__ cb, const int* __restrict__ ca, const float* __restrict__ cs,
-                                int M, int N, float ratio, float dist_th, int mutual, long long* __restrict__ m0,
+                                int M, int N, float ratio_sq, float dist_sq, int mutual, long long* __restrict__ m0,
                                 long long* __restrict__ m1, float* __restrict__ ms0, float* __restrict__ ms1) {
   const int b = blockIdx.y;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   rb += (size_t)b * M; ra += (size_t)b * M; rs += (size_t)b * M;
   cb += (size_t)b * N; ca += (size_t)b * N; cs += (size_t)b * N;
   if (t < M) {
-    int a = nn_accept(rb[t], rs[t], ra[t], N, ratio, dist_th);
+    int a = nn_accept(rb[t], rs[t], ra[t], N, ratio_sq, dist_sq);
     if (mutual && a > -1) {
-      const int back = nn_accept(cb[a], cs[a], ca[a], M, ratio, dist_th);
+      const int back = nn_accept(cb[a], cs[a], ca[a], M, ratio_sq, dist_sq);
       if (back != t) a = -1;
     }
     m0[(size_t)b * M + t] = a;
     ms0[(size_t)b * M + t] = a > -1 ? 1.f : 0.f;
   }
   if (t < N) {
-    int a = nn_accept(cb[t], cs[t], ca[t], M, ratio, dist_th);
+    int a = nn_accept(cb[t], cs[t], ca[t], M, ratio_sq, dist_sq);
     if (mutual && a > -1) {
-      const int back = nn_accept(rb[a], rs[a], ra[a], N, ratio, dist_th);
+      const int back = nn_accept(rb[a], rs[a], ra[a], N, ratio_sq, dist_sq);
       if (back != t) a = -1;
     }
     m1[(size_t)b * N + t] = a;
@@ -708,8 +712,8 @@ extern "C" size_t gfc_nn_workspace_bytes(int B, int M, int N) {
   return gfc_align((size_t)B * (M + N) * 5 * 4);
 }
 
-extern "C" int gfc_nn_match(const float* desc0, const float* desc1, int B, int M, int N, int D, float ratio_thresh,
-                            float distance_thresh, int mutual, int64_t* m0, int64_t* m1, float* ms0, float* ms1,
+extern "C" int gfc_nn_match(const float* desc0, const float* desc1, int B, int M, int N, int D, double ratio_thresh,
+                            double distance_thresh, int mutual, int64_t* m0, int64_t* m1, float* ms0, float* ms1,
                             float* sim, float* log_assignment, void* ws, size_t ws_bytes, void* stream) {
   if (!desc0 || !desc1 || !m0 || !m1 || !ms0 || !ms1 || !sim || !ws || B <= 0 || M <= 0 || N <= 0) return GFC_ERR_INVALID;
   if (D <= 0 || D % 32) return GFC_ERR_UNSUPPORTED;
@@ -728,8 +732,11 @@ extern "C" int gfc_nn_match(const float* desc0, const float* desc1, int B, int M
   hipLaunchKernelGGL(nn_top2_rows_kernel, dim3((M + 3) / 4, B), dim3(256), 0, st, sim, M, N, rb, ra, rs);
   hipLaunchKernelGGL(nn_top2_cols_kernel, dim3((N + 31) / 32, B), dim3(256), 0, st, sim, M, N, cb, ca, cs);
   const int mn = M > N ? M : N;
+  // (ratio_thresh ** 2) * dist and dist <= distance_thresh ** 2 of the reference: a double square, one rounding to fp32
+  const float ratio_sq = ratio_thresh > 0 ? (float)(ratio_thresh * ratio_thresh) : 0.f;
+  const float dist_sq = distance_thresh > 0 ? (float)(distance_thresh * distance_thresh) : 0.f;
   hipLaunchKernelGGL(nn_match_kernel, dim3((mn + 255) / 256, B), dim3(256), 0, st, rb, ra, rs, cb, ca, cs, M, N,
-                     ratio_thresh, distance_thresh, mutual, (long long*)m0, (long long*)m1, ms0, ms1);
+                     ratio_sq, dist_sq, mutual, (long long*)m0, (long long*)m1, ms0, ms1);
   if (log_assignment) {
     float* rmax = stats;
     float* rlog = rmax + (size_t)B * M;
