@@ -41,6 +41,7 @@ _LG_ARRAYS = ["wqkv", "bqkv", "s_out_w", "s_out_b", "s_ffn0_w", "s_ffn0_b", "s_l
 
 
 GFC_LG_FP32, GFC_LG_FP16 = 0, 1
+GFC_LG_ADAPTIVE_LIVE, GFC_LG_ADAPTIVE_STOPPED, GFC_LG_ADAPTIVE_EMPTIED = 0, 1, 2  # report[b][0] of gfc_lg_adaptive_step
 # the fp16 copies of the per-layer matrices (gfc_lg_params.precision = GFC_LG_FP16), in the order of the header
 _LG_ARRAYS_F16 = ["wqkv16", "s_out_w16", "s_ffn0_w16", "s_ffn3_w16", "c_qkv_w16", "c_out_w16", "c_ffn0_w16",
                   "c_ffn3_w16", "final_proj_w16"]
@@ -158,6 +159,10 @@ SIGNATURES = {
     "gfc_lg_forward_ragged": (c_int, [POINTER(LgParams)] + [c_void_p] * 5 + [c_int, POINTER(c_int32), POINTER(c_int32),
                                                                             c_float] + [c_void_p] * 7
                               + [c_size_t, POINTER(Trace), c_void_p]),
+    "gfc_lg_adaptive_step_workspace_bytes": (c_size_t, [c_int] * 2),
+    "gfc_lg_adaptive_step": (c_int, [POINTER(LgParams), c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 3
+                             + [c_int] * 3 + [c_float, c_float, c_double, c_int, c_int] + [c_void_p] * 5 + [c_int]
+                             + [c_void_p] * 6 + [c_size_t, c_void_p]),
 }
 
 

@@ -4,6 +4,7 @@
 #include <climits>
 
 #include "common.h"
+#include "lg_rowdot.h"
 
 // from the other translation units
 int gfc_rgb_to_gray(const float* img, float* out, int B, int H, int W, hipStream_t stream);
@@ -500,7 +501,7 @@ static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* c
 // token confidence / matchability logits: out[row] = (sigmoid?)(x[row,:256] . w + b)   (lightglue.py:69-80,290-291)
 __global__ void sigmoid_inplace_kernel(float* v, int n) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) v[i] = 1.f / (1.f + expf(-v[i]));
+  if (i < n) v[i] = gfc_sigmoid(v[i]);
 }
 extern "C" int gfc_lg_rowdot(const float* x, int ld, int rows, const float* w, const float* b, int apply_sigmoid,
                              float* out, void* stream) {

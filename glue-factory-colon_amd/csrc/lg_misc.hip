@@ -1,6 +1,7 @@
 // LightGlue: positional encoding, LayerNorm+GELU, matchability, dual log-softmax assignment and
 // mutual-argmax match filtering.  HBM-bound row/column reductions on wavefronts.
 #include "common.h"
+#include "lg_rowdot.h"
 
 // ------------------------------------------------------------------------------------------
 // normalize_keypoints + LearnableFourierPositionalEncoding (lightglue.py:28-40,53-66).
@@ -106,9 +107,8 @@ __global__ __launch_bounds__(256) void rowdot256_kernel(const float* __restrict_
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float4 a = *reinterpret_cast<const float4*>(x + (size_t)row * ld + lane * 4);
-  const float4 b = *reinterpret_cast<const float4*>(w + lane * 4);
-  float s = wave_sum(a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w);
-  if (lane == 0) z[row] = s + bias[0];
+  const float s = gfc_rowdot256_wave(a, w, bias, lane);
+  if (lane == 0) z[row] = s;
 }
 
 int gfc_rowdot256(const float* x, int ld, int rows, const float* w, const float* bias, float* z, hipStream_t st) {

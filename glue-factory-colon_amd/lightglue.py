@@ -129,6 +129,12 @@ class LightGlue(nn.Module):
         # the row buffer and the assignment's log double soft-max stay fp32 ("fp16 matcher").  "fp32"
         # (default): every contraction in exact fp32.  `mp` keeps the reference class's meaning here (none).
         "matmul_precision": "fp32",
+        # MI355X-specific, opt-in: `forward_pairs` runs its adaptive (depth_confidence / width_confidence) batch-1 items
+        # as ONE pass -- the layers over the live rows of all pairs, the stop / prune decisions and the re-pack between
+        # two layers on the device (gfc_lg_adaptive_step), one small device->host read per layer for the whole batch
+        # instead of several per pair.  Same decisions on the same bits as the pair-by-pair path.  False (default):
+        # adaptive pairs take the single-pair path, as before.  `forward()` is not affected.
+        "adaptive_pair_batch": False,
     }
     required_data_keys = ["keypoints0", "keypoints1", "descriptors0", "descriptors1"]
 
@@ -158,6 +164,7 @@ class LightGlue(nn.Module):
         self._ws = nat.Workspace()
         self.trace = None  # optional nat.KernelTrace (bench.py): per-launch events of the attention kernel
         self._graphs = {}  # (b, m, n, device, has scale/ori) -> captured launch sequence + its static buffers
+        self._report_host = None  # pinned [GFC_LG_MAX_RAGGED_PAIRS, 4] int32: the adaptive step's report lands here
         self.are_weights_initialized = False
 
         w = conf.weights
@@ -201,7 +208,7 @@ class LightGlue(nn.Module):
         for k, v in self.__dict__.items():
             if k == "_graphs":
                 new.__dict__[k] = {}
-            elif k == "_packed":
+            elif k in ("_packed", "_report_host"):
                 new.__dict__[k] = None
             else:
                 new.__dict__[k] = copy.deepcopy(v, memo)
@@ -444,21 +451,25 @@ class LightGlue(nn.Module):
         about image sizes once the key points exist, so pairs with their own key-point counts run together through
         gfc_lg_forward_ragged: the layers over all rows at once, the assignment head per group of equal-shape pairs.
         Same arithmetic per pair; results are returned per pair in the order given.  Pairs without key points in one
-        view, adaptive depth / width and batch sizes other than 1 take the single-pair path."""
+        view and batch sizes other than 1 take the single-pair path; so does adaptive depth / width unless
+        `adaptive_pair_batch` is set, which sends those pairs through `_forward_adaptive_pairs` together."""
         conf = self.conf
         adaptive = conf.depth_confidence > 0 or conf.width_confidence > 0
+        batched = self._forward_ragged
+        if adaptive:
+            batched = self._forward_adaptive_pairs if conf.adaptive_pair_batch else None
         outs = [None] * len(items)
         rag = []
         for i, data in enumerate(items):
             self._check_ready(data)
             k0, k1 = data["keypoints0"], data["keypoints1"]
-            if adaptive or k0.shape[0] != 1 or k0.shape[1] == 0 or k1.shape[1] == 0 or self.training:
+            if batched is None or k0.shape[0] != 1 or k0.shape[1] == 0 or k1.shape[1] == 0 or self.training:
                 outs[i] = self(data)
             else:
                 rag.append(i)
         for c in range(0, len(rag), nat.GFC_LG_MAX_RAGGED_PAIRS):
             chunk = rag[c:c + nat.GFC_LG_MAX_RAGGED_PAIRS]
-            for i, out in zip(chunk, self._forward_ragged([items[i] for i in chunk])):
+            for i, out in zip(chunk, batched([items[i] for i in chunk])):
                 outs[i] = out
         return outs
 
@@ -634,6 +645,182 @@ class LightGlue(nn.Module):
         out = self._result(m0, m1, ms0, ms1, x[None, None, :cm], x[None, None, cm:], scores, prune0, prune1)
         out["stop_layer"] = torch.full((1,), last + 1, device=device, dtype=torch.long)
         return out
+
+    # -- adaptive depth / width over SEVERAL pairs in one pass (conf.adaptive_pair_batch) -----------------
+    def _forward_adaptive_pairs(self, items):
+        """`[self(d) for d in items]` for adaptive batch-1 items with key points in both views (at most
+        GFC_LG_MAX_RAGGED_PAIRS of them), as one pass: every layer runs once over the live rows of all pairs, and what
+        `_forward_adaptive` does between two layers on the host -- token confidences, matchabilities, the stop ratio,
+        the keep masks, the re-pack -- is one call of gfc_lg_adaptive_step for all pairs, on the device, between two
+        sets of row buffers.  The host reads the step's report (4 ints per pair, through a pinned buffer) once per
+        layer; it tells which pairs finished and where every pair's rows went.  A pair that finishes at a layer gets that
+        layer's assignment head on its rows, which the step has put behind the live region.  Results per pair as
+        `_forward_adaptive` builds them."""
+        conf, lib = self.conf, nat.lib()
+        device = items[0]["keypoints0"].device
+        nat.require_cuda(items[0]["keypoints0"], "data['keypoints0']")
+        params = self.ensure_packed(device)[0]
+        st = nat.stream_ptr(device)
+        d, din, nb = conf.descriptor_dim, conf.input_dim, len(items)
+        assert 0 < nb <= nat.GFC_LG_MAX_RAGGED_PAIRS
+        do_stop, do_prune = conf.depth_confidence > 0, conf.width_confidence > 0
+        ms = [int(it["keypoints0"].shape[1]) for it in items]
+        ns = [int(it["keypoints1"].shape[1]) for it in items]
+        total = sum(ms) + sum(ns)
+        # packed rows, pair after pair: side 0 then side 1 (what gfc_lg_assign(B = 1) reads as x0, x1)
+        kp_parts, de_parts, so_parts, sizes = [], [], [], []
+        for it in items:
+            for side in ("0", "1"):
+                kp_parts.append(it["keypoints" + side][0].float())
+                de = it["descriptors" + side][0].float()
+                assert de.shape[-1] == din
+                de_parts.append(de)
+                if conf.add_scale_ori:
+                    sc, ori = it["scales" + side][0], it["oris" + side][0]
+                    so_parts.append(torch.stack([sc.reshape(-1), ori.reshape(-1)], -1).float())
+                size = _image_size(it, side)
+                sizes.append(torch.as_tensor(size, device=device, dtype=torch.float32).reshape(-1, 2)[:1])
+        kp = torch.cat(kp_parts, 0).contiguous()
+        so = torch.cat(so_parts, 0).contiguous() if so_parts else None
+        sizes = torch.cat(sizes, 0).contiguous()
+        xa = torch.empty((total, d), device=device)
+        xb = torch.empty((total, d), device=device)
+        if din == d:
+            torch.cat(de_parts, 0, out=xa)
+        else:
+            xin = torch.cat(de_parts, 0).contiguous()
+            if params.precision == nat.GFC_LG_FP16:
+                nat.check(lib.gfc_linear_f16(nat.ptr(xin), 0, din, din, None, 0, 0, 0, params.input_proj_w16, din,
+                                             params.input_proj_b, 1.0, None, None, None, None, 0, nat.ptr(xa), 0, d,
+                                             total, d, st), "input_proj")
+            else:
+                nat.check(lib.gfc_linear(nat.ptr(xin), din, din, None, 0, 0, params.input_proj_w, din,
+                                         params.input_proj_b, None, None, 1.0, None, None, None, 0, nat.ptr(xa), d,
+                                         total, d, st), "input_proj")
+        # host tables of the first layer, one upload: segments, pairs, prune offsets, problems, un-pruned indices
+        seg, pairs, self_p, cross_p, ind_parts = [], [], [], [], []
+        r = 0
+        for j, (m, n) in enumerate(zip(ms, ns)):
+            seg += [r, m, r + m, n]
+            pairs += [m + n, j]
+            self_p += [r, m, r, m, r + m, n, r + m, n]
+            cross_p += [r, m, r + m, n, r + m, n, r, m]
+            ind_parts += [torch.arange(m, dtype=torch.int32), torch.arange(n, dtype=torch.int32)]
+            r += m + n
+        # two sets of tables (the step writes the next layer's): rows seg [4 nb] | pairs [2 nb] | self | cross [8 nb]
+        host = torch.zeros((4, 8 * nb), dtype=torch.int32)
+        for k, t in enumerate((seg, pairs, self_p, cross_p)):
+            host[k, :len(t)] = torch.tensor(t, dtype=torch.int32)
+        tabs = torch.empty((2, 4, 8 * nb), dtype=torch.int32, device=device)
+        tabs[0].copy_(host)
+
+        def tables(k):
+            return tabs[k, 0, :4 * nb], tabs[k, 1, :2 * nb], tabs[k, 2], tabs[k, 3]
+
+        # the segment table of layer 0 = where each image's rows start = its offsets in the prune counters
+        img = tabs[0, 0, :4 * nb].view(2 * nb, 2)
+        prune_off = img[:, 0].clone()
+        row0, cnt = prune_off, img[:, 1].contiguous()
+        inda = torch.cat(ind_parts).to(device)
+        indb = torch.empty_like(inda)
+        cosa, sina = torch.empty((total, 64), device=device), torch.empty((total, 64), device=device)
+        cosb, sinb = torch.empty_like(cosa), torch.empty_like(sina)
+        nat.check(lib.gfc_lg_posenc(nat.ptr(kp), nat.ptr(so), nat.ptr(sizes), nat.ptr(row0), nat.ptr(cnt), 2 * nb,
+                                    max(ms + ns), params.posenc_wr, 4 if so is not None else 2, nat.ptr(cosa),
+                                    nat.ptr(sina), st), "gfc_lg_posenc")
+        prune = torch.ones((total,), dtype=torch.int32, device=device) if do_prune else None
+        report = torch.empty((nb, 4), dtype=torch.int32, device=device)
+        if self._report_host is None:
+            self._report_host = torch.empty((nat.GFC_LG_MAX_RAGGED_PAIRS, 4), dtype=torch.int32).pin_memory()
+        report_host = self._report_host
+        thresholds = self.confidence_thresholds.tolist()
+        keep_thr = float(1 - conf.width_confidence)
+        step_ws_bytes = lib.gfc_lg_adaptive_step_workspace_bytes(nb, total)
+        bufs = [(xa, cosa, sina, inda), (xb, cosb, sinb, indb)]
+        cur = 0
+        # live pairs in buffer order: (slot, first row, rows of side 0, rows of side 1)
+        live, r = [], 0
+        for j, (m, n) in enumerate(zip(ms, ns)):
+            live.append((j, r, m, n))
+            r += m + n
+        outs = [None] * nb
+        stream = torch.cuda.current_stream(device)
+
+        def finish(slot, layer, x, ind, r0, cm, cn):
+            """The assignment head of `layer` on rows [r0, r0 + cm + cn) of x and the result dict of pair `slot`."""
+            m, n = ms[slot], ns[slot]
+            rows = x[r0:r0 + cm + cn].clone()  # ref_descriptors0/1: the row buffers go on being re-used
+            m0 = torch.full((1, m), -1, device=device, dtype=torch.long)
+            m1 = torch.full((1, n), -1, device=device, dtype=torch.long)
+            ms0 = torch.zeros((1, m), device=device)
+            ms1 = torch.zeros((1, n), device=device)
+            scores = torch.zeros((1, cm + 1, cn + 1), device=device)
+            if cm > 0 and cn > 0:
+                pm0 = torch.empty((1, cm), device=device, dtype=torch.long)
+                pm1 = torch.empty((1, cn), device=device, dtype=torch.long)
+                ps0, ps1 = torch.empty((1, cm), device=device), torch.empty((1, cn), device=device)
+                ws = self._ws.get(lib.gfc_lg_assign_workspace_bytes(1, cm, cn), device)
+                nat.check(lib.gfc_lg_assign(ctypes.byref(params), layer, nat.ptr(rows),
+                                            ctypes.c_void_p(rows[cm:].data_ptr()), 1, cm, cn,
+                                            float(conf.filter_threshold), nat.ptr(pm0), nat.ptr(pm1), nat.ptr(ps0),
+                                            nat.ptr(ps1), nat.ptr(scores), nat.ptr(ws), ws.numel(), st), "gfc_lg_assign")
+                if do_prune:  # scatter back to the un-pruned indexing (lightglue.py:527-536)
+                    ind0, ind1 = ind[r0:r0 + cm].long(), ind[r0 + cm:r0 + cm + cn].long()
+                    m0[:, ind0] = torch.where(pm0 == -1, -1, ind1[pm0.clamp(min=0)])
+                    m1[:, ind1] = torch.where(pm1 == -1, -1, ind0[pm1.clamp(min=0)])
+                    ms0[:, ind0], ms1[:, ind1] = ps0, ps1
+                else:
+                    m0, m1, ms0, ms1 = pm0, pm1, ps0, ps1
+            prune0 = prune1 = None  # without pruning every point ran through all n_layers
+            if do_prune:
+                o = sum(ms[:slot]) + sum(ns[:slot])
+                prune0, prune1 = prune[o:o + m].long()[None], prune[o + m:o + m + n].long()[None]
+            out = self._result(m0, m1, ms0, ms1, rows[None, None, :cm], rows[None, None, cm:], scores, prune0, prune1)
+            out["stop_layer"] = torch.full((1,), layer + 1, device=device, dtype=torch.long)
+            outs[slot] = out
+
+        for i in range(conf.n_layers):
+            x, cos, sin, ind = bufs[cur]
+            _, _, self_t, cross_t = tables(cur)
+            rows = sum(cm + cn for _, _, cm, cn in live)
+            max_n = max(max(cm, cn) for _, _, cm, cn in live)
+            ws = self._ws.get(max(lib.gfc_lg_layer_workspace_bytes(rows), step_ws_bytes), device)
+            nat.check(lib.gfc_lg_layer(ctypes.byref(params), i, nat.ptr(x), nat.ptr(cos), nat.ptr(sin), rows,
+                                       nat.ptr(self_t), nat.ptr(cross_t), 2 * len(live), max_n, nat.ptr(ws), ws.numel(),
+                                       st), "gfc_lg_layer")
+            if i == conf.n_layers - 1:
+                break
+            seg_t, pairs_t, _, _ = tables(cur)
+            seg_o, pairs_o, self_o, cross_o = tables(1 - cur)
+            xo, coso, sino, indo = bufs[1 - cur]
+            nat.check(lib.gfc_lg_adaptive_step(
+                ctypes.byref(params), i, nat.ptr(x), nat.ptr(cos), nat.ptr(sin), nat.ptr(ind), rows, nat.ptr(seg_t),
+                nat.ptr(pairs_t), nat.ptr(prune_off), nb, len(live), max_n, thresholds[i], keep_thr,
+                float(conf.depth_confidence), int(do_stop), int(do_prune), nat.ptr(xo), nat.ptr(coso), nat.ptr(sino),
+                nat.ptr(indo), nat.ptr(prune), total, nat.ptr(self_o), nat.ptr(cross_o), nat.ptr(seg_o),
+                nat.ptr(pairs_o), nat.ptr(report), nat.ptr(ws), ws.numel(), st), "gfc_lg_adaptive_step")
+            report_host[:len(live)].copy_(report[:len(live)], non_blocking=True)
+            stream.synchronize()  # the one device->host read of the layer
+            rep = report_host[:len(live)].tolist()
+            # the step's output order: the pairs that go on, then the pairs that finished, each group in input order
+            order = [k for k, q in enumerate(rep) if q[0] == nat.GFC_LG_ADAPTIVE_LIVE]
+            n_live = len(order)
+            order += [k for k, q in enumerate(rep) if q[0] != nat.GFC_LG_ADAPTIVE_LIVE]
+            nxt, r = [], 0
+            for pos, k in enumerate(order):
+                _, cm, cn, _ = rep[k]
+                if pos < n_live:
+                    nxt.append((live[k][0], r, cm, cn))
+                else:
+                    finish(live[k][0], i, xo, indo, r, cm, cn)
+                r += cm + cn
+            live, cur = nxt, 1 - cur
+            if not live:
+                break
+        x, _, _, ind = bufs[cur]
+        for slot, r0, cm, cn in live:  # went through every layer: the last layer's head
+            finish(slot, conf.n_layers - 1, x, ind, r0, cm, cn)
+        return outs
 
     def loss(self, pred, data):
         raise NotImplementedError("training loss (lightglue.py:588-637) is out of scope")

@@ -18,7 +18,9 @@ class LightGlue(BaseModel):
     default_conf = {"features": "superpoint", "depth_confidence": -1, "width_confidence": -1,
                     "filter_threshold": 0.1, "weights": None,
                     # MI355X-specific (lightglue.LightGlue): "fp32" or the opt-in fp16 matcher "fp16"
-                    "matmul_precision": "fp32"}
+                    "matmul_precision": "fp32",
+                    # MI355X-specific (lightglue.LightGlue): forward_pairs runs adaptive pairs as one batched pass
+                    "adaptive_pair_batch": False}
     required_data_keys = ["view0", "keypoints0", "descriptors0", "view1", "keypoints1", "descriptors1"]
 
     def _init(self, conf):
@@ -35,6 +37,7 @@ class LightGlue(BaseModel):
             "filter_threshold": conf_get(conf, "filter_threshold"),
             "weights": conf_get(conf, "weights"),
             "matmul_precision": conf_get(conf, "matmul_precision"),
+            "adaptive_pair_batch": conf_get(conf, "adaptive_pair_batch"),
         })
         if self.net.are_weights_initialized:
             self.set_initialized()

@@ -514,6 +514,45 @@ int gfc_lg_forward_ragged(const gfc_lg_params* p, const float* kpts, const float
                           float threshold, int64_t* m0, int64_t* m1, float* ms0, float* ms1, float* log_assignment,
                           float* rows, void* ws, size_t ws_bytes, gfc_trace* attention_trace, void* stream);
 
+/* Adaptive depth / width for a BATCH of pairs: the step between layer `layer` and the next one
+ * (lightglue.py:500-521,555-580) for B <= GFC_LG_MAX_RAGGED_PAIRS live pairs, on the device.
+ *
+ * In: the live rows x [rows,256] with cos_tab / sin_tab [rows,64] and ind [rows] (each row's index in its image's
+ * un-pruned key-point list); seg [2B][2] = {row0, n} of side 0 (entry 2b) and side 1 (entry 2b + 1) of pair b; pairs
+ * [B][2] = {un-pruned m + n (the denominator of check_if_stop's ratio), slot}; prune_off [n_slots][2] = where image
+ * `side` of slot `slot` starts in the prune counters (static; the slot is the pair's position in the caller's list and
+ * travels with the pair through every step).  All tables live on the device, 16-byte aligned, like the row buffers.
+ *
+ * Decide.  Per row tok = sigmoid(x . token_w[layer] + token_b[layer]) and sc = sigmoid(x . matchability_w[layer] +
+ * matchability_b[layer]) from one read of the row, bit for bit what gfc_lg_rowdot(apply_sigmoid = 1) returns.  Per pair
+ * cnt = #(tok < thr) and stop = (double)(1.0f - (float)cnt / (float)(m + n)) > depth_confidence (do_stop).  Per row of a
+ * pair that goes on: keep = sc > keep_thr || tok <= thr (do_prune; the second term only with do_stop), where keep_thr is
+ * (float)(1 - width_confidence).  At least one of do_stop / do_prune must be set.
+ *
+ * Re-pack (a copy: x_out, cos_out, sin_out, ind_out are a second set of buffers of `rows` rows, never the inputs).  The
+ * pairs that stay live come first, in their order, each as its kept side-0 rows followed by its kept side-1 rows
+ * (stable); the pairs that finish at this step follow, in their order and in the same form: a pair that stopped with
+ * all its rows, a pair one side of which emptied with the rows it kept.  prune [prune_len] (int32) gets + 1 at
+ * prune_off[slot][side] + ind for every kept row of a pair that did not stop.  Rows behind the last pair are not written.
+ *
+ * Tables of the next layer: self_problems / cross_problems [2 * live][4] as gfc_lg_layer takes them, seg_out [2B][2]
+ * and pairs_out [B][2] in the output order (never the input tables).
+ *
+ * report [B][4] = {state, cm, cn, cnt} of input pair b (cm, cn: its rows in the output; cnt 0 without do_stop): all the
+ * host needs to know where everything went, and the only thing it has to read.  max_n >= every segment's n sizes the
+ * grid (longer segments are still packed completely).  No allocation, no synchronisation. */
+#define GFC_LG_ADAPTIVE_LIVE 0
+#define GFC_LG_ADAPTIVE_STOPPED 1
+#define GFC_LG_ADAPTIVE_EMPTIED 2
+size_t gfc_lg_adaptive_step_workspace_bytes(int B, int rows);
+int gfc_lg_adaptive_step(const gfc_lg_params* p, int layer, const float* x, const float* cos_tab, const float* sin_tab,
+                         const int32_t* ind, int rows, const int32_t* seg, const int32_t* pairs,
+                         const int32_t* prune_off, int n_slots, int B, int max_n, float thr, float keep_thr,
+                         double depth_confidence, int do_stop, int do_prune, float* x_out, float* cos_out,
+                         float* sin_out, int32_t* ind_out, int32_t* prune, int prune_len, int32_t* self_problems,
+                         int32_t* cross_problems, int32_t* seg_out, int32_t* pairs_out, int32_t* report, void* ws,
+                         size_t ws_bytes, void* stream);
+
 /* Nearest-neighbour matcher ("next" row; the matcher of the reference's superpoint+NN configurations):
  * sim = desc0 . desc1^T, top-2 per row / column, ratio test d1 <= ratio^2 d2 and distance test d1 <= th^2 on
  * d = 2(1 - sim) (thresholds <= 0 disable a test; they are doubles because the reference squares the configured
