@@ -353,67 +353,42 @@ extern "C" int gfc_lg_layer(const gfc_lg_params* p, int l, float* x, const float
   return lg_layer_impl(p, l, x, cosb, sinb, nullptr, R, self_p, cross_p, n_problems, maxn, ws, ws_bytes, stream);
 }
 
-// ---- the fp16 layer (precision GFC_LG_FP16): the launch sequence of the fp32 layer below on the fp16 kernels
-// (lg_fp16.hip).  Same workspace slots: qkv, ctx and msg hold fp16 operands (half of their fp32 size), hbuf stays fp32
-// (ffn[0] output, LayerNorm + GELU in place, then rounded to fp16 as ffn[3]'s operand), the rows x stay fp32.
+// ---- the two precisions of the matcher (gfc_lg_params.precision).  What a stage needs to know about one: the element
+// type T of its matrix-product operands between two kernels (qkv, ctx, msg, mdesc; the rows x, hbuf and every output
+// stay fp32), which matrix of a pair (w, w16) is read, and the GEMM / attention entry points in ONE argument order.
+// linear(): a0 / y are T where a0_t / y_t say so and fp32 otherwise (to fp32 both are the same thing), a1 is always T.
+struct LgF32 {  // GFC_LG_FP32: every contraction on the fp32 MFMA (gemm.hip, attention.hip)
+  using T = float;
+  static constexpr bool fp32 = true;
+  static const void* w(const float* w32, const void*) { return w32; }
+  static int linear(const void* a0, bool, int lda0, int k0, const T* a1, int lda1, int k1, const void* w, int ldw,
+                    const float* bias, float alpha, const float* resid, const float*, const float* rot_cos,
+                    const float* rot_sin, int rot_cols, void* y, bool, int ldy, int M, int N, hipStream_t st) {
+    return gfc_linear((const float*)a0, lda0, k0, a1, lda1, k1, (const float*)w, ldw, bias, nullptr, nullptr, alpha,
+                      resid, rot_cos, rot_sin, rot_cols, (float*)y, ldy, M, N, st);
+  }
+  static constexpr auto attention = gfc_attention;
+  static constexpr auto batched_nt = gfc_batched_nt;
+};
+struct LgF16 {  // GFC_LG_FP16: fp16 operands (half of their fp32 slot in the workspace), fp32 sums (lg_fp16.hip)
+  using T = _Float16;
+  static constexpr bool fp32 = false;
+  static const void* w(const float*, const void* w16) { return w16; }
+  static int linear(const void* a0, bool a0_t, int lda0, int k0, const T* a1, int lda1, int k1, const void* w, int ldw,
+                    const float* bias, float alpha, const float* resid, const float* rot_cs, const float* rot_cos,
+                    const float* rot_sin, int rot_cols, void* y, bool y_t, int ldy, int M, int N, hipStream_t st) {
+    return gfc_linear_f16(a0, a0_t, lda0, k0, a1, a1 != nullptr, lda1, k1, w, ldw, bias, alpha, resid, rot_cs, rot_cos,
+                          rot_sin, rot_cols, y, y_t, ldy, M, N, st);
+  }
+  static constexpr auto attention = gfc_attention_f16;
+  static constexpr auto batched_nt = gfc_batched_nt_f16;
+};
+
 static bool lg_f16_layer_ok(const gfc_lg_params* p, int l) {
   if (!p->wqkv16[l] || !p->s_ffn0_w16[l] || !p->s_ffn3_w16[l] || !p->c_qkv_w16[l] || !p->c_ffn0_w16[l] ||
       !p->c_ffn3_w16[l])
     return false;
   return (!p->s_out_w[l] || p->s_out_w16[l]) && (!p->c_out_w[l] || p->c_out_w16[l]);
-}
-
-static int lg_layer_f16(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, const float* csb,
-                        int R, const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, char* base,
-                        hipStream_t st, const float* x_in, gfc_trace* tr) {
-  const int D = 256;
-  _Float16* qkv = (_Float16*)base;
-  _Float16* ctx = (_Float16*)(base + gfc_align((size_t)R * 768 * 4));
-  _Float16* msg = (_Float16*)((char*)ctx + gfc_align((size_t)R * 256 * 4));
-  float* hbuf = (float*)((char*)msg + gfc_align((size_t)R * 256 * 4));
-  void* att_ws = (char*)hbuf + gfc_align((size_t)R * 512 * 4);
-  const size_t att_ws_bytes = lg_attn_scratch_bytes(R);
-  auto attn = [&](const _Float16* q, int ldq, const _Float16* k, int ldk, const _Float16* v, int ldv,
-                  const int32_t* probs) -> int {
-    const bool rec = trace_begin(tr, st);
-    const int s = gfc_attention_f16(q, ldq, k, ldk, v, ldv, ctx, D, probs, n_problems, maxn, 4, 0.125f, att_ws,
-                                    att_ws_bytes, st);
-    trace_end(tr, st, rec);
-    return s;
-  };
-  // [x | a1] . W0^T + b0 -> LayerNorm -> GELU (fp32 hbuf) -> . W3^T + b3 + resid -> x
-  auto ffn = [&](const float* a0, const _Float16* a1, const void* w0, const float* b0, const float* ln_g,
-                 const float* ln_b, const void* w3, const float* b3, const float* resid) -> int {
-    GFC_TRY(gfc_linear_f16(a0, 0, D, D, a1, 1, D, D, w0, 512, b0, 1.f, nullptr, nullptr, nullptr, nullptr, 0, hbuf, 0,
-                           512, R, 512, st));
-    GFC_TRY(gfc_layernorm_gelu(hbuf, 512, R, 512, ln_g, ln_b, st));
-    return gfc_linear_f16(hbuf, 0, 512, 512, nullptr, 0, 0, 0, w3, 512, b3, 1.f, resid, nullptr, nullptr, nullptr, 0, x,
-                          0, D, R, D, st);
-  };
-  const float* xs = x_in ? x_in : x;
-  // ---- self block (lightglue.py:151-164) ----
-  GFC_TRY(gfc_linear_f16(xs, 0, D, D, nullptr, 0, 0, 0, p->wqkv16[l], D, p->bqkv[l], 1.f, nullptr, csb,
-                         csb ? nullptr : cosb, csb ? nullptr : sinb, 512, qkv, 1, 768, R, 768, st));
-  GFC_TRY(attn(qkv, 768, qkv + 256, 768, qkv + 512, 768, self_p));
-  const _Float16* a1s = ctx;
-  if (p->s_out_w[l]) {
-    GFC_TRY(gfc_linear_f16(ctx, 1, D, D, nullptr, 0, 0, 0, p->s_out_w16[l], D, p->s_out_b[l], 1.f, nullptr, nullptr,
-                           nullptr, nullptr, 0, msg, 1, D, R, D, st));
-    a1s = msg;
-  }
-  GFC_TRY(ffn(xs, a1s, p->s_ffn0_w16[l], p->s_ffn0_b[l], p->s_ln_g[l], p->s_ln_b[l], p->s_ffn3_w16[l], p->s_ffn3_b[l],
-              xs));
-  // ---- cross block (lightglue.py:193-222) ----
-  GFC_TRY(gfc_linear_f16(x, 0, D, D, nullptr, 0, 0, 0, p->c_qkv_w16[l], D, p->c_qkv_b[l], 1.f, nullptr, nullptr, nullptr,
-                         nullptr, 0, qkv, 1, 512, R, 512, st));
-  GFC_TRY(attn(qkv, 512, qkv, 512, qkv + 256, 512, cross_p));
-  const _Float16* a1c = ctx;
-  if (p->c_out_w[l]) {
-    GFC_TRY(gfc_linear_f16(ctx, 1, D, D, nullptr, 0, 0, 0, p->c_out_w16[l], D, p->c_out_b[l], 1.f, nullptr, nullptr,
-                           nullptr, nullptr, 0, msg, 1, D, R, D, st));
-    a1c = msg;
-  }
-  return ffn(x, a1c, p->c_ffn0_w16[l], p->c_ffn0_b[l], p->c_ln_g[l], p->c_ln_b[l], p->c_ffn3_w16[l], p->c_ffn3_b[l], x);
 }
 
 // csb (optional): the rotary table packed for the QKV epilogue (one float4 per four channels instead of two)
@@ -430,72 +405,80 @@ static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* c
   if (p->precision == GFC_LG_FP16 && !lg_f16_layer_ok(p, l)) return GFC_ERR_INVALID;
   if (ws_bytes < gfc_lg_layer_workspace_bytes(R)) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  if (p->precision == GFC_LG_FP16)
-    return lg_layer_f16(p, l, x, cosb, sinb, csb, R, self_p, cross_p, n_problems, maxn, (char*)ws, st, x_in, tr);
   const int D = 256;
-  char* base = (char*)ws;
-  float* qkv = (float*)base;
-  float* ctx = (float*)(base + gfc_align((size_t)R * 768 * 4));
-  float* msg = (float*)((char*)ctx + gfc_align((size_t)R * 256 * 4));
-  float* hbuf = (float*)((char*)msg + gfc_align((size_t)R * 256 * 4));
+  // the slots of gfc_lg_layer_workspace_bytes, sized for fp32 in either precision
+  char* qkv_slot = (char*)ws;
+  char* ctx_slot = qkv_slot + gfc_align((size_t)R * 768 * 4);
+  char* msg_slot = ctx_slot + gfc_align((size_t)R * 256 * 4);
+  float* hbuf = (float*)(msg_slot + gfc_align((size_t)R * 256 * 4));
   void* att_ws = (char*)hbuf + gfc_align((size_t)R * 512 * 4);
   // scratch is indexed [problem][head][max_n queries][split]: with n_problems * maxn <= R (uniform packed rows) it holds
   // the full 8-way key split; for ragged problem sets gfc_attention lowers the split until it fits
   const size_t att_ws_bytes = lg_attn_scratch_bytes(R);
-  // attention on fp32 MFMA (with its key split for small problem sets)
-  auto attn = [&](const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* probs) -> int {
-    const bool rec = trace_begin(tr, st);
-    const int s = gfc_attention(q, ldq, k, ldk, v, ldv, ctx, D, probs, n_problems, maxn, 4, 0.125f, att_ws, att_ws_bytes, st);
-    trace_end(tr, st, rec);
-    return s;
-  };
-  auto lin = [&](const float* a0, int lda0, int k0, const float* a1, int lda1, int k1, const float* w, int ldw,
-                 const float* bias, const float* resid, const float* rc, const float* rs, int rot_cols, float* y, int ldy,
-                 int n) -> int {
-    return gfc_linear(a0, lda0, k0, a1, lda1, k1, w, ldw, bias, nullptr, nullptr, 1.f, resid, rc, rs, rot_cols, y, ldy, R,
-                      n, st);
-  };
-  // the whole FFN (ffn[0] -> LayerNorm -> GELU -> ffn[3] + residual, lightglue.py:143-148) in one row-owning kernel once
-  // there are enough 128-row tiles to cover the chip (>= 128: batch >= 8 pairs of 1024 points), else GEMM into hbuf +
-  // in-place LayerNorm / GELU pass + GEMM
-  const bool ffn_fused = R >= 128 * 128;
-  auto ffn = [&](const float* a0, const float* a1, const float* w0, const float* b0, const float* ln_g, const float* ln_b,
-                 const float* w3, const float* b3, const float* resid) -> int {
-    if (ffn_fused) return gfc_ffn_fused(a0, D, D, a1, D, D, w0, 512, b0, ln_g, ln_b, w3, 512, b3, resid, x, D, R, st);
-    GFC_TRY(lin(a0, D, D, a1, D, D, w0, 512, b0, nullptr, nullptr, nullptr, 0, hbuf, 512, 512));
-    GFC_TRY(gfc_layernorm_gelu(hbuf, 512, R, 512, ln_g, ln_b, st));
-    return lin(hbuf, 512, 512, nullptr, 0, 0, w3, 512, b3, resid, nullptr, nullptr, 0, x, D, D);
-  };
   const float* xs = x_in ? x_in : x;  // what the self block reads
-  {
 
+  auto layer = [&](auto prec) -> int {
+    using P = decltype(prec);
+    using T = typename P::T;
+    T* qkv = (T*)qkv_slot;
+    T* ctx = (T*)ctx_slot;
+    T* msg = (T*)msg_slot;
+    // attention (with its key split for small problem sets)
+    auto attn = [&](const T* q, int ldq, const T* k, int ldk, const T* v, int ldv, const int32_t* probs) -> int {
+      const bool rec = trace_begin(tr, st);
+      const int s = P::attention(q, ldq, k, ldk, v, ldv, ctx, D, probs, n_problems, maxn, 4, 0.125f, att_ws, att_ws_bytes, st);
+      trace_end(tr, st, rec);
+      return s;
+    };
+    // y[R,n] (T) = a[R,256] . W^T + bias, rotated on the columns < rot_cols
+    auto proj = [&](const void* a, bool a_t, const void* w, const float* bias, const float* rot_cs, const float* rot_cos,
+                    const float* rot_sin, int rot_cols, T* y, int n) -> int {
+      return P::linear(a, a_t, D, D, nullptr, 0, 0, w, D, bias, 1.f, nullptr, rot_cs, rot_cos, rot_sin, rot_cols, y, true, n,
+                       R, n, st);
+    };
+    // the FFN (lightglue.py:143-148): [a0 | a1] . W0^T + b0 -> LayerNorm -> GELU (in place in the fp32 hbuf) ->
+    // . W3^T + b3 + resid -> x.  fp32 only: the whole of it in one row-owning kernel once there are enough 128-row tiles
+    // to cover the chip (>= 128: batch >= 8 pairs of 1024 points)
+    auto ffn = [&](const float* a0, const T* a1, const void* w0, const float* b0, const float* ln_g, const float* ln_b,
+                   const void* w3, const float* b3, const float* resid) -> int {
+      if constexpr (P::fp32)
+        if (R >= 128 * 128)
+          return gfc_ffn_fused(a0, D, D, a1, D, D, (const float*)w0, 512, b0, ln_g, ln_b, (const float*)w3, 512, b3,
+                               resid, x, D, R, st);
+      GFC_TRY(P::linear(a0, false, D, D, a1, D, D, w0, 512, b0, 1.f, nullptr, nullptr, nullptr, nullptr, 0, hbuf, false,
+                        512, R, 512, st));
+      GFC_TRY(gfc_layernorm_gelu(hbuf, 512, R, 512, ln_g, ln_b, st));
+      return P::linear(hbuf, false, 512, 512, nullptr, 0, 0, w3, 512, b3, 1.f, resid, nullptr, nullptr, nullptr, 0, x,
+                       false, D, R, D, st);
+    };
     // ---- self block (lightglue.py:151-164) ----
-    if (csb)
-      GFC_TRY(gfc_linear_rot_packed(xs, D, D, p->wqkv[l], D, p->bqkv[l], csb, 512, qkv, 768, R, 768, st));
+    if (P::fp32 && csb)  // fp32 only: a GEMM of its own whose epilogue reads the packed rotary table
+      GFC_TRY(gfc_linear_rot_packed(xs, D, D, p->wqkv[l], D, p->bqkv[l], csb, 512, (float*)qkv, 768, R, 768, st));
     else
-      GFC_TRY(lin(xs, D, D, nullptr, 0, 0, p->wqkv[l], D, p->bqkv[l], nullptr, cosb, sinb, 512, qkv, 768, 768));
+      GFC_TRY(proj(xs, false, P::w(p->wqkv[l], p->wqkv16[l]), p->bqkv[l], csb, csb ? nullptr : cosb,
+                   csb ? nullptr : sinb, 512, qkv, 768));
     GFC_TRY(attn(qkv, 768, qkv + 256, 768, qkv + 512, 768, self_p));
     // out_proj is either a GEMM of its own, or (s_out_w == NULL) already folded into ffn0's second
     // K block at load time: [x | ctx] . [W0a | W0b.Wo]^T + (b0 + W0b.bo)
-    const float* a1s = ctx;
+    const T* a1s = ctx;
     if (p->s_out_w[l]) {
-      GFC_TRY(gfc_linear(ctx, D, D, nullptr, 0, 0, p->s_out_w[l], D, p->s_out_b[l], nullptr, nullptr, 1.f, nullptr,
-                         nullptr, nullptr, 0, msg, D, R, D, st));
+      GFC_TRY(proj(ctx, true, P::w(p->s_out_w[l], p->s_out_w16[l]), p->s_out_b[l], nullptr, nullptr, nullptr, 0, msg, D));
       a1s = msg;
     }
-    GFC_TRY(ffn(xs, a1s, p->s_ffn0_w[l], p->s_ffn0_b[l], p->s_ln_g[l], p->s_ln_b[l], p->s_ffn3_w[l], p->s_ffn3_b[l], xs));
+    GFC_TRY(ffn(xs, a1s, P::w(p->s_ffn0_w[l], p->s_ffn0_w16[l]), p->s_ffn0_b[l], p->s_ln_g[l], p->s_ln_b[l],
+                P::w(p->s_ffn3_w[l], p->s_ffn3_w16[l]), p->s_ffn3_b[l], xs));
     // ---- cross block (lightglue.py:193-222) ----
-    GFC_TRY(lin(x, D, D, nullptr, 0, 0, p->c_qkv_w[l], D, p->c_qkv_b[l], nullptr, nullptr, nullptr, 0, qkv, 512, 512));
+    GFC_TRY(proj(x, false, P::w(p->c_qkv_w[l], p->c_qkv_w16[l]), p->c_qkv_b[l], nullptr, nullptr, nullptr, 0, qkv, 512));
     GFC_TRY(attn(qkv, 512, qkv, 512, qkv + 256, 512, cross_p));
-    const float* a1c = ctx;
+    const T* a1c = ctx;
     if (p->c_out_w[l]) {
-      GFC_TRY(gfc_linear(ctx, D, D, nullptr, 0, 0, p->c_out_w[l], D, p->c_out_b[l], nullptr, nullptr, 1.f, nullptr,
-                         nullptr, nullptr, 0, msg, D, R, D, st));
+      GFC_TRY(proj(ctx, true, P::w(p->c_out_w[l], p->c_out_w16[l]), p->c_out_b[l], nullptr, nullptr, nullptr, 0, msg, D));
       a1c = msg;
     }
-    GFC_TRY(ffn(x, a1c, p->c_ffn0_w[l], p->c_ffn0_b[l], p->c_ln_g[l], p->c_ln_b[l], p->c_ffn3_w[l], p->c_ffn3_b[l], x));
-    }
-  return GFC_OK;
+    return ffn(x, a1c, P::w(p->c_ffn0_w[l], p->c_ffn0_w16[l]), p->c_ffn0_b[l], p->c_ln_g[l], p->c_ln_b[l],
+               P::w(p->c_ffn3_w[l], p->c_ffn3_w16[l]), p->c_ffn3_b[l], x);
+  };
+  return p->precision == GFC_LG_FP16 ? layer(LgF16{}) : layer(LgF32{});
 }
 
 // token confidence / matchability logits: out[row] = (sigmoid?)(x[row,:256] . w + b)   (lightglue.py:69-80,290-291)
@@ -540,31 +523,35 @@ extern "C" int gfc_lg_assign(const gfc_lg_params* p, int l, const float* x0, con
   float* z = (float*)(base + gfc_align(R * 256 * 4));
   float* stats = (float*)((char*)z + gfc_align(R * 4));
   void* tail = (char*)stats + gfc_align(2 * R * 4);
-  float* md1 = md + (size_t)R0 * D;
-  if (p->precision == GFC_LG_FP16) {
-    // mdesc (fp16 operand, in the front half of its fp32 slot) and the similarity on the fp16 MFMA; sim is fp32
-    _Float16* h0 = (_Float16*)md;
-    _Float16* h1 = h0 + (size_t)R0 * D;
-    GFC_TRY(gfc_linear_f16(x0, 0, D, D, nullptr, 0, 0, 0, p->final_proj_w16[l], D, p->final_proj_b[l], 0.25f, nullptr,
-                           nullptr, nullptr, nullptr, 0, h0, 1, D, R0, D, st));
-    GFC_TRY(gfc_linear_f16(x1, 0, D, D, nullptr, 0, 0, 0, p->final_proj_w16[l], D, p->final_proj_b[l], 0.25f, nullptr,
-                           nullptr, nullptr, nullptr, 0, h1, 1, D, R1, D, st));
+  auto head = [&](auto prec) -> int {
+    using P = decltype(prec);
+    // mdesc (T: fp16 fills the front half of the fp32 slot) and the similarity on this precision's MFMA; sim is fp32
+    typename P::T* md0 = (typename P::T*)md;
+    typename P::T* md1 = md0 + (size_t)R0 * D;
+    const void* w = P::w(p->final_proj_w[l], p->final_proj_w16[l]);
+    GFC_TRY(P::linear(x0, false, D, D, nullptr, 0, 0, w, D, p->final_proj_b[l], 0.25f, nullptr, nullptr, nullptr, nullptr,
+                      0, md0, true, D, R0, D, st));
+    GFC_TRY(P::linear(x1, false, D, D, nullptr, 0, 0, w, D, p->final_proj_b[l], 0.25f, nullptr, nullptr, nullptr, nullptr,
+                      0, md1, true, D, R1, D, st));
     GFC_TRY(gfc_rowdot256(x0, D, R0, p->matchability_w[l], p->matchability_b[l], z, st));
     GFC_TRY(gfc_rowdot256(x1, D, R1, p->matchability_w[l], p->matchability_b[l], z + R0, st));
-    GFC_TRY(gfc_batched_nt_f16(h0, D, (long long)M * D, h1, D, (long long)N * D, log_assignment, N + 1,
-                               (long long)(M + 1) * (N + 1), M, N, D, B, st));
+    GFC_TRY(P::batched_nt(md0, D, (long long)M * D, md1, D, (long long)N * D, log_assignment, N + 1,
+                          (long long)(M + 1) * (N + 1), M, N, D, B, st));
+    // statistics in one sweep, final scores + arg-max in a second one
     return gfc_assign_filter_fused(log_assignment, z, z + R0, B, M, N, threshold, m0, m1, ms0, ms1, stats, tail, st);
-  }
-  GFC_TRY(gfc_linear(x0, D, D, nullptr, 0, 0, p->final_proj_w[l], D, p->final_proj_b[l], nullptr, nullptr, 0.25f,
-                     nullptr, nullptr, nullptr, 0, md, D, R0, D, st));
-  GFC_TRY(gfc_linear(x1, D, D, nullptr, 0, 0, p->final_proj_w[l], D, p->final_proj_b[l], nullptr, nullptr, 0.25f,
-                     nullptr, nullptr, nullptr, 0, md1, D, R1, D, st));
-  GFC_TRY(gfc_rowdot256(x0, D, R0, p->matchability_w[l], p->matchability_b[l], z, st));
-  GFC_TRY(gfc_rowdot256(x1, D, R1, p->matchability_w[l], p->matchability_b[l], z + R0, st));
-  GFC_TRY(gfc_batched_nt(md, D, (long long)M * D, md1, D, (long long)N * D, log_assignment, N + 1,
-                         (long long)(M + 1) * (N + 1), M, N, D, B, st));
-  // statistics in one sweep, final scores + arg-max in a second one
-  return gfc_assign_filter_fused(log_assignment, z, z + R0, B, M, N, threshold, m0, m1, ms0, ms1, stats, tail, st);
+  };
+  return p->precision == GFC_LG_FP16 ? head(LgF16{}) : head(LgF32{});
+}
+
+// descriptors [R, input_dim] -> rows x [R,256] (input_proj, lightglue.py:352-355,464-465)
+static int lg_input_proj(const gfc_lg_params* p, const float* desc, float* x, int R, hipStream_t st) {
+  const int Din = p->input_dim;
+  auto run = [&](auto prec) -> int {
+    using P = decltype(prec);
+    return P::linear(desc, false, Din, Din, nullptr, 0, 0, P::w(p->input_proj_w, p->input_proj_w16), Din, p->input_proj_b,
+                     1.f, nullptr, nullptr, nullptr, nullptr, 0, x, false, 256, R, 256, st);
+  };
+  return p->precision == GFC_LG_FP16 ? run(LgF16{}) : run(LgF32{});
 }
 
 // The matcher over a batch: tables -> rotary tables -> input_proj -> n_layers x layer -> one assignment head + filter
@@ -595,13 +582,7 @@ static int lg_forward_core(const gfc_lg_params* p, const LgBatch& bt, const floa
   // otherwise input_proj writes the rows (lightglue.py:352-355,464-465)
   const float* x_in = desc;
   if (p->input_dim != D) {
-    const int Din = p->input_dim;
-    if (p->precision == GFC_LG_FP16)
-      GFC_TRY(gfc_linear_f16(desc, 0, Din, Din, nullptr, 0, 0, 0, p->input_proj_w16, Din, p->input_proj_b, 1.f, nullptr,
-                             nullptr, nullptr, nullptr, 0, x, 0, D, R, D, st));
-    else
-      GFC_TRY(gfc_linear(desc, Din, Din, nullptr, 0, 0, p->input_proj_w, Din, p->input_proj_b, nullptr, nullptr, 1.f,
-                         nullptr, nullptr, nullptr, 0, x, D, R, D, st));
+    GFC_TRY(lg_input_proj(p, desc, x, R, st));
     x_in = nullptr;
   }
   for (int l = 0; l < p->n_layers; ++l)
@@ -633,6 +614,18 @@ static bool lg_params_ok(const gfc_lg_params* p, bool has_so) {
   return p->final_proj_w16[p->n_layers - 1] != nullptr;
 }
 
+// gfc_lg_forward_packed / gfc_lg_forward_ragged behind their pointer checks, on the batch either of them laid out
+static int lg_forward_rows(const gfc_lg_params* p, const LgBatch& bt, const float* kpts, const float* desc,
+                           const float* size0, const float* size1, const float* scale_ori, float threshold, int64_t* m0,
+                           int64_t* m1, float* ms0, float* ms1, float* log_assignment, float* rows, void* ws,
+                           size_t ws_bytes, gfc_trace* attention_trace, void* stream) {
+  if (!lg_params_ok(p, scale_ori != nullptr)) return GFC_ERR_INVALID;
+  if (rows == desc) return GFC_ERR_INVALID;  // the caller's descriptors are read-only
+  if (ws_bytes < bt.total) return GFC_ERR_WORKSPACE;
+  return lg_forward_core(p, bt, kpts, scale_ori, desc, size0, size1, threshold, m0, m1, ms0, ms1, log_assignment, rows,
+                         (char*)ws, attention_trace, (hipStream_t)stream);
+}
+
 extern "C" int gfc_lg_forward_packed(const gfc_lg_params* p, const float* kpts, const float* desc, const float* size0,
                                      const float* size1, const float* scale_ori, int B, int M, int N, float threshold,
                                      int64_t* m0, int64_t* m1, float* ms0, float* ms1, float* log_assignment, float* rows,
@@ -640,11 +633,9 @@ extern "C" int gfc_lg_forward_packed(const gfc_lg_params* p, const float* kpts, 
   if (!p || !kpts || !desc || !size0 || !size1 || !m0 || !m1 || !ms0 || !ms1 || !log_assignment || !rows || !ws)
     return GFC_ERR_INVALID;
   LgBatch bt;
-  if (!lg_params_ok(p, scale_ori != nullptr) || !lg_uniform(B, M, N, bt)) return GFC_ERR_INVALID;
-  if (rows == desc) return GFC_ERR_INVALID;  // the caller's descriptors are read-only
-  if (ws_bytes < bt.total) return GFC_ERR_WORKSPACE;
-  return lg_forward_core(p, bt, kpts, scale_ori, desc, size0, size1, threshold, m0, m1, ms0, ms1, log_assignment, rows,
-                         (char*)ws, attention_trace, (hipStream_t)stream);
+  if (!lg_uniform(B, M, N, bt)) return GFC_ERR_INVALID;
+  return lg_forward_rows(p, bt, kpts, desc, size0, size1, scale_ori, threshold, m0, m1, ms0, ms1, log_assignment, rows, ws,
+                         ws_bytes, attention_trace, stream);
 }
 
 extern "C" int gfc_lg_forward_ragged(const gfc_lg_params* p, const float* kpts, const float* desc, const float* size0,
@@ -655,11 +646,9 @@ extern "C" int gfc_lg_forward_ragged(const gfc_lg_params* p, const float* kpts, 
   if (!p || !kpts || !desc || !size0 || !size1 || !m0 || !m1 || !ms0 || !ms1 || !log_assignment || !rows || !ws)
     return GFC_ERR_INVALID;
   LgBatch bt;
-  if (!lg_ragged(B, m, n, bt) || !lg_params_ok(p, scale_ori != nullptr)) return GFC_ERR_INVALID;
-  if (rows == desc) return GFC_ERR_INVALID;  // the caller's descriptors are read-only
-  if (ws_bytes < bt.total) return GFC_ERR_WORKSPACE;
-  return lg_forward_core(p, bt, kpts, scale_ori, desc, size0, size1, threshold, m0, m1, ms0, ms1, log_assignment, rows,
-                         (char*)ws, attention_trace, (hipStream_t)stream);
+  if (!lg_ragged(B, m, n, bt)) return GFC_ERR_INVALID;
+  return lg_forward_rows(p, bt, kpts, desc, size0, size1, scale_ori, threshold, m0, m1, ms0, ms1, log_assignment, rows, ws,
+                         ws_bytes, attention_trace, stream);
 }
 
 extern "C" int gfc_lg_forward(const gfc_lg_params* p, const float* kpts0, const float* kpts1, const float* desc0,

@@ -386,6 +386,8 @@ class LightGlue(nn.Module):
         b, m, _ = kpts0.shape
         b, n, _ = kpts1.shape
         device = kpts0.device
+        if (conf.depth_confidence > 0 or conf.width_confidence > 0) and m > 0 and n > 0:
+            return self._forward_adaptive(data)
         size0, size1 = _image_size(data, "0"), _image_size(data, "1")
         desc0 = data["descriptors0"].contiguous().float()
         desc1 = data["descriptors1"].contiguous().float()
@@ -398,8 +400,6 @@ class LightGlue(nn.Module):
                 ori = ori if ori.dim() == 3 else ori[..., None]
                 return torch.cat([sc, ori], -1).to(device=device, dtype=torch.float32).contiguous()
             so0, so1 = pack(data["scales0"], data["oris0"]), pack(data["scales1"], data["oris1"])
-        if (conf.depth_confidence > 0 or conf.width_confidence > 0) and m > 0 and n > 0:
-            return self._forward_adaptive(kpts0, kpts1, desc0, desc1, size0, size1, so0, so1)
         d = conf.descriptor_dim
         if m > 0 and n > 0:
             self.ensure_packed(device)
@@ -443,6 +443,41 @@ class LightGlue(nn.Module):
             rows = torch.zeros((b * (m + n), d), device=device)
         return self._result(m0, m1, ms0, ms1, rows[: b * m].view(b, 1, m, d), rows[b * m:].view(b, 1, n, d), scores)
 
+    # -- one view of a batch-1 item, rows of several views, the rows' way into the matcher --------
+    def _side(self, item, side, device):
+        """View `side` ("0" / "1") of a batch-1 input of `forward` as the library reads it, all float32: key points
+        [m,2], descriptors [m,input_dim], (scale, orientation) [m,2] (None without add_scale_ori, lightglue.py:436-453)
+        and the image size [1,2]."""
+        kp = item["keypoints" + side][0].float()
+        de = item["descriptors" + side][0].float()
+        assert de.shape[-1] == self.conf.input_dim
+        so = None
+        if self.conf.add_scale_ori:
+            sc, ori = item["scales" + side][0], item["oris" + side][0]
+            so = torch.stack([sc.reshape(-1), ori.reshape(-1)], -1).float()
+        size = torch.as_tensor(_image_size(item, side), device=device, dtype=torch.float32).reshape(-1, 2)[:1]
+        return kp, de, so, size
+
+    def _pack_views(self, views):
+        """The rows of several `_side` views behind each other: key points, descriptors (a tensor of its own), scales /
+        orientations (or None)."""
+        kp = torch.cat([v[0] for v in views], 0).contiguous()
+        de = torch.cat([v[1] for v in views], 0).contiguous()
+        so = torch.cat([v[2] for v in views], 0).contiguous() if self.conf.add_scale_ori else None
+        return kp, de, so
+
+    def _input_proj(self, params, xin, out, rows, stream):
+        """out [rows,256] = input_proj(xin [rows,input_dim]) in the matcher's precision (lightglue.py:352-355,464-465)."""
+        lib, din, d = nat.lib(), self.conf.input_dim, self.conf.descriptor_dim
+        if params.precision == nat.GFC_LG_FP16:
+            status = lib.gfc_linear_f16(nat.ptr(xin), 0, din, din, None, 0, 0, 0, params.input_proj_w16, din,
+                                        params.input_proj_b, 1.0, None, None, None, None, 0, nat.ptr(out), 0, d, rows, d,
+                                        stream)
+        else:
+            status = lib.gfc_linear(nat.ptr(xin), din, din, None, 0, 0, params.input_proj_w, din, params.input_proj_b,
+                                    None, None, 1.0, None, None, None, 0, nat.ptr(out), d, rows, d, stream)
+        nat.check(status, "input_proj")
+
     # -- several pairs of DIFFERENT sizes through one launch sequence -----------------------------
     def forward_pairs(self, items: list) -> list:
         """MI355X addition: `[self(d) for d in items]` (each `d` a batch-1 input of `forward`) as ONE matcher pass.
@@ -478,32 +513,15 @@ class LightGlue(nn.Module):
         device = items[0]["keypoints0"].device
         nat.require_cuda(items[0]["keypoints0"], "data['keypoints0']")
         self.ensure_packed(device)
-        d, din = conf.descriptor_dim, conf.input_dim
+        d = conf.descriptor_dim
         # equal shapes next to each other (stable): every run of equal (m, n) is one batched assignment head
         shapes = [(int(it["keypoints0"].shape[1]), int(it["keypoints1"].shape[1])) for it in items]
         order = sorted(range(len(items)), key=lambda i: shapes[i])
         groups = [(m, n, list(idx)) for (m, n), idx in itertools.groupby(order, key=lambda i: shapes[i])]
-        kp_parts, de_parts, so_parts, s0, s1 = [], [], [], [], []
-        for _, _, idx in groups:
-            for side in ("0", "1"):
-                for i in idx:
-                    it = items[i]
-                    kp = it["keypoints" + side][0].float()
-                    de = it["descriptors" + side][0].float()
-                    assert de.shape[-1] == din
-                    kp_parts.append(kp)
-                    de_parts.append(de)
-                    if conf.add_scale_ori:
-                        sc, ori = it["scales" + side][0], it["oris" + side][0]
-                        so_parts.append(torch.stack([sc.reshape(-1), ori.reshape(-1)], -1).float())
-            for i in idx:
-                for side, acc in (("0", s0), ("1", s1)):
-                    size = _image_size(items[i], side)
-                    acc.append(torch.as_tensor(size, device=device, dtype=torch.float32).reshape(-1, 2)[:1])
-        kp = torch.cat(kp_parts, 0).contiguous()
-        de = torch.cat(de_parts, 0).contiguous()
-        so = torch.cat(so_parts, 0).contiguous() if so_parts else None
-        size0, size1 = torch.cat(s0, 0).contiguous(), torch.cat(s1, 0).contiguous()
+        view = {(i, side): self._side(items[i], side, device) for i in order for side in ("0", "1")}
+        kp, de, so = self._pack_views([view[i, side] for _, _, idx in groups for side in ("0", "1") for i in idx])
+        size0 = torch.cat([view[i, "0"][3] for i in order], 0).contiguous()
+        size1 = torch.cat([view[i, "1"][3] for i in order], 0).contiguous()
         b = len(order)
         ms = [shapes[i][0] for i in order]
         ns = [shapes[i][1] for i in order]
@@ -536,44 +554,32 @@ class LightGlue(nn.Module):
         return outs
 
     # -- adaptive depth / width (lightglue.py:500-521,555-580) -----------------------------------
-    def _forward_adaptive(self, kpts0, kpts1, desc0, desc1, size0, size1, so0=None, so1=None):
+    def _forward_adaptive(self, data):
         """Early stopping (`depth_confidence`) and point pruning (`width_confidence`); batch size 1 like the
         reference (`assert b == 1`, lightglue.py:501,507).  The host drives `gfc_lg_layer` layer by layer, takes
         the stop / prune decisions on the token confidences and matchabilities computed by `gfc_lg_rowdot`
         (one small device->host read per layer, as `check_if_stop` does in the reference) and re-packs the
         surviving rows between layers (index_select: plumbing)."""
         conf, lib = self.conf, nat.lib()
-        b, m, _ = kpts0.shape
-        n = kpts1.shape[1]
+        b, m, _ = data["keypoints0"].shape
+        n = data["keypoints1"].shape[1]
         assert b == 1
-        device = kpts0.device
+        device = data["keypoints0"].device
         params = self.ensure_packed(device)[0]
         st = nat.stream_ptr(device)
         d = conf.descriptor_dim
         do_early_stop, do_prune = conf.depth_confidence > 0, conf.width_confidence > 0
         # packed rows: image 0 first
-        kp = torch.cat([kpts0[0], kpts1[0]], 0).float().contiguous()
-        x = torch.empty((m + n, d), device=device, dtype=torch.float32)
-        if conf.input_dim == d:
-            x[:m], x[m:] = desc0[0], desc1[0]
-        else:
-            din = conf.input_dim
-            xin = torch.cat([desc0[0], desc1[0]], 0).contiguous()
-            if params.precision == nat.GFC_LG_FP16:
-                nat.check(lib.gfc_linear_f16(nat.ptr(xin), 0, din, din, None, 0, 0, 0, params.input_proj_w16, din,
-                                             params.input_proj_b, 1.0, None, None, None, None, 0, nat.ptr(x), 0, d,
-                                             m + n, d, st), "input_proj")
-            else:
-                nat.check(lib.gfc_linear(nat.ptr(xin), din, din, None, 0, 0, params.input_proj_w, din,
-                                         params.input_proj_b, None, None, 1.0, None, None, None, 0, nat.ptr(x), d,
-                                         m + n, d, st), "input_proj")
-        sizes = torch.stack([torch.as_tensor(size0, device=device, dtype=torch.float32).reshape(-1, 2)[0],
-                             torch.as_tensor(size1, device=device, dtype=torch.float32).reshape(-1, 2)[0]]).contiguous()
+        views = [self._side(data, "0", device), self._side(data, "1", device)]
+        kp, x, so = self._pack_views(views)
+        if conf.input_dim != d:
+            xin, x = x, torch.empty((m + n, d), device=device, dtype=torch.float32)
+            self._input_proj(params, xin, x, m + n, st)
+        sizes = torch.cat([v[3] for v in views], 0).contiguous()
         row0 = torch.tensor([0, m], dtype=torch.int32, device=device)
         cnt = torch.tensor([m, n], dtype=torch.int32, device=device)
         cos = torch.empty((m + n, 64), device=device)
         sin = torch.empty((m + n, 64), device=device)
-        so = torch.cat([so0[0], so1[0]], 0).contiguous() if so0 is not None else None
         nat.check(lib.gfc_lg_posenc(nat.ptr(kp), nat.ptr(so), nat.ptr(sizes), nat.ptr(row0), nat.ptr(cnt), 2, max(m, n),
                                     params.posenc_wr, 4 if so is not None else 2, nat.ptr(cos), nat.ptr(sin), st),
                   "gfc_lg_posenc")
@@ -620,6 +626,16 @@ class LightGlue(nn.Module):
                 cm, cn = int(keep0.numel()), int(keep1.numel())
                 if cm == 0 or cn == 0:
                     break
+        if not do_prune:
+            ind0 = ind1 = prune0 = prune1 = None  # every point ran through all n_layers
+        return self._finish_adaptive(params, last, x, cm, cn, m, n, ind0, ind1, prune0, prune1, st)
+
+    def _finish_adaptive(self, params, layer, x, cm, cn, m, n, ind0, ind1, prune0, prune1, st):
+        """The end of both adaptive paths for one pair of m and n points: the assignment head of `layer` on its surviving
+        rows x [cm + cn, 256] (side 0 first), matches and scores scattered back through ind0 / ind1 (the survivors'
+        un-pruned indices, int64; None when nothing is pruned), and the result dict with prune0/1 [1,m] / [1,n] (None:
+        every point ran through all layers).  ref_descriptors0/1 are views of x."""
+        conf, lib, device = self.conf, nat.lib(), x.device
         m0 = torch.full((1, m), -1, device=device, dtype=torch.long)
         m1 = torch.full((1, n), -1, device=device, dtype=torch.long)
         ms0 = torch.zeros((1, m), device=device)
@@ -630,20 +646,17 @@ class LightGlue(nn.Module):
             pm1 = torch.empty((1, cn), device=device, dtype=torch.long)
             ps0, ps1 = torch.empty((1, cm), device=device), torch.empty((1, cn), device=device)
             ws = self._ws.get(lib.gfc_lg_assign_workspace_bytes(1, cm, cn), device)
-            x1 = x[cm:]
-            nat.check(lib.gfc_lg_assign(ctypes.byref(params), last, nat.ptr(x), ctypes.c_void_p(x1.data_ptr()), 1, cm,
-                                        cn, float(conf.filter_threshold), nat.ptr(pm0), nat.ptr(pm1), nat.ptr(ps0),
+            nat.check(lib.gfc_lg_assign(ctypes.byref(params), layer, nat.ptr(x), ctypes.c_void_p(x[cm:].data_ptr()), 1,
+                                        cm, cn, float(conf.filter_threshold), nat.ptr(pm0), nat.ptr(pm1), nat.ptr(ps0),
                                         nat.ptr(ps1), nat.ptr(scores), nat.ptr(ws), ws.numel(), st), "gfc_lg_assign")
-            if do_prune:  # scatter back to the un-pruned indexing (lightglue.py:527-536)
+            if ind0 is not None:  # scatter back to the un-pruned indexing (lightglue.py:527-536)
                 m0[:, ind0] = torch.where(pm0 == -1, -1, ind1[pm0.clamp(min=0)])
                 m1[:, ind1] = torch.where(pm1 == -1, -1, ind0[pm1.clamp(min=0)])
                 ms0[:, ind0], ms1[:, ind1] = ps0, ps1
             else:
                 m0, m1, ms0, ms1 = pm0, pm1, ps0, ps1
-        if not do_prune:
-            prune0 = prune1 = None  # every point ran through all n_layers
         out = self._result(m0, m1, ms0, ms1, x[None, None, :cm], x[None, None, cm:], scores, prune0, prune1)
-        out["stop_layer"] = torch.full((1,), last + 1, device=device, dtype=torch.long)
+        out["stop_layer"] = torch.full((1,), layer + 1, device=device, dtype=torch.long)
         return out
 
     # -- adaptive depth / width over SEVERAL pairs in one pass (conf.adaptive_pair_batch) -----------------
@@ -654,8 +667,8 @@ class LightGlue(nn.Module):
         the keep masks, the re-pack -- is one call of gfc_lg_adaptive_step for all pairs, on the device, between two
         sets of row buffers.  The host reads the step's report (4 ints per pair, through a pinned buffer) once per
         layer; it tells which pairs finished and where every pair's rows went.  A pair that finishes at a layer gets that
-        layer's assignment head on its rows, which the step has put behind the live region.  Results per pair as
-        `_forward_adaptive` builds them."""
+        layer's assignment head on its rows, which the step has put behind the live region; both paths end a pair in
+        `_finish_adaptive`."""
         conf, lib = self.conf, nat.lib()
         device = items[0]["keypoints0"].device
         nat.require_cuda(items[0]["keypoints0"], "data['keypoints0']")
@@ -668,35 +681,13 @@ class LightGlue(nn.Module):
         ns = [int(it["keypoints1"].shape[1]) for it in items]
         total = sum(ms) + sum(ns)
         # packed rows, pair after pair: side 0 then side 1 (what gfc_lg_assign(B = 1) reads as x0, x1)
-        kp_parts, de_parts, so_parts, sizes = [], [], [], []
-        for it in items:
-            for side in ("0", "1"):
-                kp_parts.append(it["keypoints" + side][0].float())
-                de = it["descriptors" + side][0].float()
-                assert de.shape[-1] == din
-                de_parts.append(de)
-                if conf.add_scale_ori:
-                    sc, ori = it["scales" + side][0], it["oris" + side][0]
-                    so_parts.append(torch.stack([sc.reshape(-1), ori.reshape(-1)], -1).float())
-                size = _image_size(it, side)
-                sizes.append(torch.as_tensor(size, device=device, dtype=torch.float32).reshape(-1, 2)[:1])
-        kp = torch.cat(kp_parts, 0).contiguous()
-        so = torch.cat(so_parts, 0).contiguous() if so_parts else None
-        sizes = torch.cat(sizes, 0).contiguous()
-        xa = torch.empty((total, d), device=device)
+        views = [self._side(it, side, device) for it in items for side in ("0", "1")]
+        kp, xa, so = self._pack_views(views)
+        sizes = torch.cat([v[3] for v in views], 0).contiguous()
+        if din != d:
+            xin, xa = xa, torch.empty((total, d), device=device)
+            self._input_proj(params, xin, xa, total, st)
         xb = torch.empty((total, d), device=device)
-        if din == d:
-            torch.cat(de_parts, 0, out=xa)
-        else:
-            xin = torch.cat(de_parts, 0).contiguous()
-            if params.precision == nat.GFC_LG_FP16:
-                nat.check(lib.gfc_linear_f16(nat.ptr(xin), 0, din, din, None, 0, 0, 0, params.input_proj_w16, din,
-                                             params.input_proj_b, 1.0, None, None, None, None, 0, nat.ptr(xa), 0, d,
-                                             total, d, st), "input_proj")
-            else:
-                nat.check(lib.gfc_linear(nat.ptr(xin), din, din, None, 0, 0, params.input_proj_w, din,
-                                         params.input_proj_b, None, None, 1.0, None, None, None, 0, nat.ptr(xa), d,
-                                         total, d, st), "input_proj")
         # host tables of the first layer, one upload: segments, pairs, prune offsets, problems, un-pruned indices
         seg, pairs, self_p, cross_p, ind_parts = [], [], [], [], []
         r = 0
@@ -747,37 +738,15 @@ class LightGlue(nn.Module):
         stream = torch.cuda.current_stream(device)
 
         def finish(slot, layer, x, ind, r0, cm, cn):
-            """The assignment head of `layer` on rows [r0, r0 + cm + cn) of x and the result dict of pair `slot`."""
+            """Pair `slot` ends at `layer` with rows [r0, r0 + cm + cn) of x."""
             m, n = ms[slot], ns[slot]
             rows = x[r0:r0 + cm + cn].clone()  # ref_descriptors0/1: the row buffers go on being re-used
-            m0 = torch.full((1, m), -1, device=device, dtype=torch.long)
-            m1 = torch.full((1, n), -1, device=device, dtype=torch.long)
-            ms0 = torch.zeros((1, m), device=device)
-            ms1 = torch.zeros((1, n), device=device)
-            scores = torch.zeros((1, cm + 1, cn + 1), device=device)
-            if cm > 0 and cn > 0:
-                pm0 = torch.empty((1, cm), device=device, dtype=torch.long)
-                pm1 = torch.empty((1, cn), device=device, dtype=torch.long)
-                ps0, ps1 = torch.empty((1, cm), device=device), torch.empty((1, cn), device=device)
-                ws = self._ws.get(lib.gfc_lg_assign_workspace_bytes(1, cm, cn), device)
-                nat.check(lib.gfc_lg_assign(ctypes.byref(params), layer, nat.ptr(rows),
-                                            ctypes.c_void_p(rows[cm:].data_ptr()), 1, cm, cn,
-                                            float(conf.filter_threshold), nat.ptr(pm0), nat.ptr(pm1), nat.ptr(ps0),
-                                            nat.ptr(ps1), nat.ptr(scores), nat.ptr(ws), ws.numel(), st), "gfc_lg_assign")
-                if do_prune:  # scatter back to the un-pruned indexing (lightglue.py:527-536)
-                    ind0, ind1 = ind[r0:r0 + cm].long(), ind[r0 + cm:r0 + cm + cn].long()
-                    m0[:, ind0] = torch.where(pm0 == -1, -1, ind1[pm0.clamp(min=0)])
-                    m1[:, ind1] = torch.where(pm1 == -1, -1, ind0[pm1.clamp(min=0)])
-                    ms0[:, ind0], ms1[:, ind1] = ps0, ps1
-                else:
-                    m0, m1, ms0, ms1 = pm0, pm1, ps0, ps1
-            prune0 = prune1 = None  # without pruning every point ran through all n_layers
+            ind0 = ind1 = prune0 = prune1 = None  # without pruning every point ran through all n_layers
             if do_prune:
+                ind0, ind1 = ind[r0:r0 + cm].long(), ind[r0 + cm:r0 + cm + cn].long()
                 o = sum(ms[:slot]) + sum(ns[:slot])
                 prune0, prune1 = prune[o:o + m].long()[None], prune[o + m:o + m + n].long()[None]
-            out = self._result(m0, m1, ms0, ms1, rows[None, None, :cm], rows[None, None, cm:], scores, prune0, prune1)
-            out["stop_layer"] = torch.full((1,), layer + 1, device=device, dtype=torch.long)
-            outs[slot] = out
+            outs[slot] = self._finish_adaptive(params, layer, rows, cm, cn, m, n, ind0, ind1, prune0, prune1, st)
 
         for i in range(conf.n_layers):
             x, cos, sin, ind = bufs[cur]

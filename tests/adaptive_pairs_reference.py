@@ -52,3 +52,70 @@ def traced(depth, width, prune_z):
                                        filter_threshold=ar.FILTER_THRESHOLD)
         out.append((layers, final, ar.bands(layers, depth, width)))
     return out
+
+
+# ---- 128-d inputs (the input projection of both adaptive paths) --------------------------------------------------
+PAIRS_128 = (2, 1)        # the two smallest shapes: (65, 64) and (190, 333)
+CONFIG_128 = (0.9, 0.9)   # (depth_confidence, width_confidence) on the prune_z of CONFIGS[0]
+
+
+@functools.lru_cache(maxsize=1)
+def inputs128():
+    """The pairs PAIRS_128 of inputs() with every descriptor cut to its first 128 channels and re-normalised."""
+    out = []
+    for p in PAIRS_128:
+        d = dict(inputs()[p])
+        for side in (0, 1):
+            de = d[f"descriptors{side}"][..., :128]
+            d[f"descriptors{side}"] = torch.nn.functional.normalize(de, dim=-1).contiguous()
+        out.append(d)
+    return out
+
+
+def state_dict128():
+    from glue_factory_colon_amd import weights
+
+    return weights.lightglue_adaptive_state_dict(0, prune_z=CONFIGS[0][2], input_dim=128)
+
+
+@functools.lru_cache(maxsize=1)
+def traced128():
+    """Per pair of inputs128() (layers, final, bands) of the oracle under CONFIG_128, weights with an input_proj."""
+    depth, width = CONFIG_128
+    sd = state_dict128()
+    out = []
+    for d in inputs128():
+        layers, final, _, _ = ar.trace(sd, d["keypoints0"], d["keypoints1"], d["descriptors0"], d["descriptors1"],
+                                       d["size"], d["size"], depth_confidence=depth, width_confidence=width,
+                                       filter_threshold=ar.FILTER_THRESHOLD)
+        out.append((layers, final, ar.bands(layers, depth, width)))
+    return out
+
+
+# ---- add_scale_ori: nothing pruned, nothing stopped, so that oracle.lightglue.match is the reference ----------------
+SCALE_ORI_SHAPE = (65, 64)
+SCALE_ORI_WIDTH = 1 - 1e-3   # keep threshold 1e-3: far below every matchability of these inputs (checked on the host)
+
+
+@functools.lru_cache(maxsize=1)
+def scale_ori_case():
+    """(inputs, oracle output with its per-layer rows): pair 0 of tests/golden/scale_ori.npz cut to SCALE_ORI_SHAPE
+    points, through oracle.lightglue.match with scale_ori0/1 on weights.lightglue_state_dict(0, add_scale_ori=True)."""
+    import os
+
+    import numpy as np
+
+    from glue_factory_colon_amd import weights
+    from oracle import lightglue as olg
+
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "scale_ori.npz"))
+    d = {"size": torch.from_numpy(z["image_size"][:1])}
+    for side, cut in ((0, SCALE_ORI_SHAPE[0]), (1, SCALE_ORI_SHAPE[1])):
+        for k in ("keypoints", "descriptors", "scales", "oris"):
+            d[f"{k}{side}"] = torch.from_numpy(z[f"{k}{side}"][:1, :cut]).contiguous()
+        d[f"scale_ori{side}"] = torch.stack([d[f"scales{side}"].reshape(1, cut), d[f"oris{side}"].reshape(1, cut)], -1)
+    sd = weights.lightglue_state_dict(0, add_scale_ori=True)
+    ref = olg.match(sd, d["keypoints0"], d["keypoints1"], d["descriptors0"], d["descriptors1"], d["size"], d["size"],
+                    filter_threshold=ar.FILTER_THRESHOLD, return_layers=True, scale_ori0=d["scale_ori0"],
+                    scale_ori1=d["scale_ori1"])
+    return d, sd, ref

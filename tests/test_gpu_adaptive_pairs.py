@@ -335,6 +335,43 @@ def _first_divergence(pred, final, layers, bands, prune):
     return desc
 
 
+def _compare_pair(cfg, p, pred, run, shape, prune):
+    """One GPU pair against its oracle trace `run` = (layers, final, bands): the comparison the docstring of
+    test_forward_pairs_adaptive_batched describes.  A pair that took the band exit is recorded in _EXCUSED."""
+    layers, final, bands = run
+    m, n = shape
+    parted = _first_divergence(pred, final, layers, bands, prune)
+    if parted is not None:
+        _EXCUSED.append((cfg, p))
+        print(f"config {cfg} pair {p}: parts from the oracle inside the band, (layer, side, point, matchability, "
+              f"token confidence - threshold): {parted}; stop layer {int(pred['stop_layer'])} / {final['stop_layer']}")
+        return
+    assert int(pred["stop_layer"]) == final["stop_layer"]
+    assert pred["log_assignment"].shape == final["log_assignment"].shape
+    assert pred["ref_descriptors0"].shape == final["ref_descriptors0"].shape
+    assert pred["ref_descriptors1"].shape == final["ref_descriptors1"].shape
+    assert pred["matches0"].shape == (1, m) and pred["matches1"].shape == (1, n)
+    e_la = relerr(pred["log_assignment"], final["log_assignment"])
+    e_s = max(maxerr(pred["matching_scores0"], final["matching_scores0"]),
+              maxerr(pred["matching_scores1"], final["matching_scores1"]))
+    e_x = max(maxerr(pred["ref_descriptors0"], final["ref_descriptors0"]),
+              maxerr(pred["ref_descriptors1"], final["ref_descriptors1"]))
+    print(f"config {cfg} pair {p}: stop {final['stop_layer']}, survivors {tuple(final['log_assignment'].shape[1:])}, "
+          f"log_assignment rel {e_la:.2e}, scores {e_s:.2e}, rows {e_x:.2e}")
+    assert e_la < 1e-4, (p, e_la)
+    assert e_s < TOL and e_x < TOL, (p, e_s, e_x)
+    skip0, skip1 = ar.near_tie_rows(final["log_assignment"])
+    full0, full1 = torch.zeros(m, dtype=torch.bool), torch.zeros(n, dtype=torch.bool)
+    if prune:
+        full0[final["ind0"]], full1[final["ind1"]] = skip0, skip1
+    else:
+        full0, full1 = skip0, skip1
+    for side, (got, ref, skip) in enumerate(((pred["matches0"], final["matches0"], full0),
+                                             (pred["matches1"], final["matches1"], full1))):
+        bad = (got.cpu().flatten() != ref.flatten()) & ~skip
+        assert not bool(bad.any()), (p, side, bad.nonzero().flatten().tolist()[:10])
+
+
 @pytest.mark.parametrize("cfg", range(len(apr.CONFIGS)))
 def test_forward_pairs_adaptive_batched(cfg):
     """forward_pairs(adaptive_pair_batch=True) on the four shared pairs against the oracle trace of each pair.  A pair
@@ -358,43 +395,27 @@ def test_forward_pairs_adaptive_batched(cfg):
         for k in a:
             assert torch.equal(a[k], b[k]), k
             assert c[k].dtype == a[k].dtype and c[k].dim() == a[k].dim(), k
-    prune = width > 0
-    for p, (pred, (layers, final, bands)) in enumerate(zip(preds, runs)):
-        m, n = apr.SHAPES[p]
-        parted = _first_divergence(pred, final, layers, bands, prune)
-        if parted is not None:
-            _EXCUSED.append((cfg, p))
-            print(f"config {cfg} pair {p}: parts from the oracle inside the band, (layer, side, point, matchability, "
-                  f"token confidence - threshold): {parted}; stop layer {int(pred['stop_layer'])} / {final['stop_layer']}")
-            continue
-        assert int(pred["stop_layer"]) == final["stop_layer"]
-        assert pred["log_assignment"].shape == final["log_assignment"].shape
-        assert pred["ref_descriptors0"].shape == final["ref_descriptors0"].shape
-        assert pred["ref_descriptors1"].shape == final["ref_descriptors1"].shape
-        assert pred["matches0"].shape == (1, m) and pred["matches1"].shape == (1, n)
-        e_la = relerr(pred["log_assignment"], final["log_assignment"])
-        e_s = max(maxerr(pred["matching_scores0"], final["matching_scores0"]),
-                  maxerr(pred["matching_scores1"], final["matching_scores1"]))
-        e_x = max(maxerr(pred["ref_descriptors0"], final["ref_descriptors0"]),
-                  maxerr(pred["ref_descriptors1"], final["ref_descriptors1"]))
-        print(f"config {cfg} pair {p}: stop {final['stop_layer']}, survivors {tuple(final['log_assignment'].shape[1:])}, "
-              f"log_assignment rel {e_la:.2e}, scores {e_s:.2e}, rows {e_x:.2e}")
-        assert e_la < 1e-4, (p, e_la)
-        assert e_s < TOL and e_x < TOL, (p, e_s, e_x)
-        skip0, skip1 = ar.near_tie_rows(final["log_assignment"])
-        full0, full1 = torch.zeros(m, dtype=torch.bool), torch.zeros(n, dtype=torch.bool)
-        if prune:
-            full0[final["ind0"]], full1[final["ind1"]] = skip0, skip1
-        else:
-            full0, full1 = skip0, skip1
-        for side, (got, ref, skip) in enumerate(((pred["matches0"], final["matches0"], full0),
-                                                 (pred["matches1"], final["matches1"], full1))):
-            bad = (got.cpu().flatten() != ref.flatten()) & ~skip
-            assert not bool(bad.any()), (p, side, bad.nonzero().flatten().tolist()[:10])
+    for p, (pred, run) in enumerate(zip(preds, runs)):
+        _compare_pair(cfg, p, pred, run, apr.SHAPES[p], width > 0)
     assert len(_EXCUSED) <= MAX_EXCUSED, _EXCUSED
 
 
 # ============================================================================================ D. fp16, chunking
+def _fp16_batched_matches_sequential(a_all, b_all):
+    """Two fp16 launch sets on the same pairs: stop layers equal, matches agreeing on 99 % of the points, floats within
+    2e-2 (1 + |x|)."""
+    for i, (a, b) in enumerate(zip(a_all, b_all)):
+        print(f"fp16 pair {i}: stop {int(a['stop_layer'])} / {int(b['stop_layer'])}, log_assignment "
+              f"{tuple(a['log_assignment'].shape)} / {tuple(b['log_assignment'].shape)}")
+        assert int(a["stop_layer"]) == int(b["stop_layer"]), i
+        for k in ("matches0", "matches1"):
+            agree = float((a[k] == b[k]).double().mean())
+            assert agree >= 0.99, (i, k, agree)
+        for k in ("matching_scores0", "matching_scores1", "log_assignment"):
+            assert a[k].shape == b[k].shape, (i, k, a[k].shape, b[k].shape)
+            assert ((a[k] - b[k]).abs() <= 2e-2 * (1 + a[k].abs())).all(), (i, k)
+
+
 def test_adaptive_batched_fp16_and_chunking():
     """matmul_precision fp16: the batched path against the sequential fp16 path on the shared pairs -- stop layers equal,
     matches agreeing on 99 % of the points and floats within 2e-2 (1 + |x|), the tolerance
@@ -407,16 +428,7 @@ def test_adaptive_batched_fp16_and_chunking():
     with torch.no_grad():
         a_all = [seq(d) for d in items]
         b_all = bat.forward_pairs(items)
-    for i, (a, b) in enumerate(zip(a_all, b_all)):
-        print(f"fp16 pair {i}: stop {int(a['stop_layer'])} / {int(b['stop_layer'])}, log_assignment "
-              f"{tuple(a['log_assignment'].shape)} / {tuple(b['log_assignment'].shape)}")
-        assert int(a["stop_layer"]) == int(b["stop_layer"]), i
-        for k in ("matches0", "matches1"):
-            agree = float((a[k] == b[k]).double().mean())
-            assert agree >= 0.99, (i, k, agree)
-        for k in ("matching_scores0", "matching_scores1", "log_assignment"):
-            assert a[k].shape == b[k].shape, (i, k, a[k].shape, b[k].shape)
-            assert ((a[k] - b[k]).abs() <= 2e-2 * (1 + a[k].abs())).all(), (i, k)
+    _fp16_batched_matches_sequential(a_all, b_all)
 
     src = apr.inputs()
     tiny = []
@@ -449,3 +461,88 @@ def test_adaptive_batched_fp16_and_chunking():
     agree = torch.cat([(a[k] == b[k]).flatten() for a, b in zip(a_all, b_all) for k in ("matches0", "matches1")])
     assert float(agree.double().mean()) >= 0.99
     print(f"130 tiny pairs: stop layers seen {sorted(stops)}")
+
+
+# ============================================================================================ E. input_proj, scale / ori
+def _items128():
+    out = []
+    for d in apr.inputs128():
+        size = d["size"].to(DEV)
+        out.append({"keypoints0": d["keypoints0"].to(DEV), "keypoints1": d["keypoints1"].to(DEV),
+                    "descriptors0": d["descriptors0"].to(DEV), "descriptors1": d["descriptors1"].to(DEV),
+                    "view0": {"image_size": size}, "view1": {"image_size": size}})
+    return out
+
+
+def _model128(**kw):
+    from glue_factory_colon_amd import lightglue
+
+    depth, width = apr.CONFIG_128
+    m = lightglue.LightGlue({"filter_threshold": ar.FILTER_THRESHOLD, "input_dim": 128, "depth_confidence": depth,
+                             "width_confidence": width, **kw}).eval()
+    m.load_state_dict(apr.state_dict128(), strict=False)
+    return m.to(DEV)
+
+
+def test_adaptive_input_dim_128():
+    """input_dim 128 (the input projection in front of both adaptive paths), fp32: the pairs (65, 64) and (190, 333) with
+    128-d descriptors, `model(d)` pair by pair and forward_pairs(adaptive_pair_batch=True), each against the oracle's
+    match_adaptive trace with the comparisons and the cap of test_forward_pairs_adaptive_batched.  On the oracle both
+    pairs prune at four layers, stop after the fifth and have no band row (tests/test_adaptive_fold_host.py)."""
+    runs = apr.traced128()
+    items = _items128()
+    with torch.no_grad():
+        seq = _model128()
+        single = [seq(d) for d in items]
+        batched = _model128(adaptive_pair_batch=True).forward_pairs(items)
+    for tag, preds in (("128-d single", single), ("128-d batched", batched)):
+        for p, (pred, run) in enumerate(zip(preds, runs)):
+            _compare_pair(tag, p, pred, run, apr.SHAPES[apr.PAIRS_128[p]], True)
+    assert len(_EXCUSED) <= MAX_EXCUSED, _EXCUSED
+
+
+def test_adaptive_input_dim_128_fp16():
+    """The same two 128-d pairs with matmul_precision fp16 (input projection on the fp16 MFMA): the batched path against
+    the sequential one, as the first half of test_adaptive_batched_fp16_and_chunking."""
+    items = _items128()
+    with torch.no_grad():
+        seq = _model128(matmul_precision="fp16")
+        a_all = [seq(d) for d in items]
+        b_all = _model128(matmul_precision="fp16", adaptive_pair_batch=True).forward_pairs(items)
+    _fp16_batched_matches_sequential(a_all, b_all)
+
+
+def test_adaptive_add_scale_ori():
+    """add_scale_ori through both adaptive paths.  The oracle's match_adaptive takes no scales / orientations, so the
+    configuration prunes and stops nothing (depth_confidence -1, keep threshold 1e-3 against matchabilities above 0.7:
+    tests/test_adaptive_fold_host.py) and oracle.lightglue.match(scale_ori0=, scale_ori1=) is the reference: matches
+    equal outside near-tie rows, scores and rows within the tolerances of test_lightglue_add_scale_ori_golden, every
+    point through all layers."""
+    from glue_factory_colon_amd import lightglue
+
+    d, sd, ref = apr.scale_ori_case()
+    m, n = apr.SCALE_ORI_SHAPE
+    data = {k: d[k].to(DEV) for k in ("keypoints0", "keypoints1", "descriptors0", "descriptors1", "scales0", "scales1",
+                                      "oris0", "oris1")}
+    data["view0"] = data["view1"] = {"image_size": d["size"].to(DEV)}
+    conf = {"weights": None, "filter_threshold": ar.FILTER_THRESHOLD, "add_scale_ori": True, "depth_confidence": -1,
+            "width_confidence": apr.SCALE_ORI_WIDTH}
+    skip = ar.near_tie_rows(ref["log_assignment"])
+    for tag, extra in (("single", {}), ("batched", {"adaptive_pair_batch": True})):
+        model = lightglue.LightGlue({**conf, **extra}).eval()
+        model.load_state_dict(sd, strict=False)
+        model = model.to(DEV)
+        with torch.no_grad():
+            out = model(data) if tag == "single" else model.forward_pairs([data])[0]
+        e_s = max(maxerr(out["matching_scores0"], ref["matching_scores0"]),
+                  maxerr(out["matching_scores1"], ref["matching_scores1"]))
+        e_x = max(maxerr(out["ref_descriptors0"], ref["ref_descriptors0"]),
+                  maxerr(out["ref_descriptors1"], ref["ref_descriptors1"]))
+        print(f"add_scale_ori {tag}: scores {e_s:.2e}, rows {e_x:.2e}")
+        for side, cnt in ((0, m), (1, n)):
+            bad = (out[f"matches{side}"].cpu().flatten() != ref[f"matches{side}"].flatten()) & ~skip[side]
+            assert not bool(bad.any()), (tag, side, bad.nonzero().flatten().tolist()[:10])
+            assert out[f"prune{side}"].shape == (1, cnt) and bool((out[f"prune{side}"] == model.conf.n_layers).all()), tag
+        assert e_s < TOL and e_x < 1e-4, (tag, e_s, e_x)
+        assert out["log_assignment"].shape == (1, m + 1, n + 1)
+        assert int(out["stop_layer"]) == model.conf.n_layers, tag
