@@ -1,6 +1,7 @@
 // Host-side orchestration behind the C ABI: which kernels run, in which order, on which slices of
 // the caller's workspace.  No allocation, no synchronisation: everything is enqueued on the
 // caller's stream (graph-capturable).
+#include <algorithm>
 #include <climits>
 
 #include "common.h"
@@ -13,8 +14,7 @@ int gfc_det_head_softmax_d2s(const float* hidden, int lda, const float* wp, cons
 int gfc_rowdot256(const float* x, int ld, int rows, const float* w, const float* bias, float* z, hipStream_t st);
 size_t gfc_assign_tail_bytes(int B, int M, int N);
 int gfc_assign_filter_fused(float* scores, const float* z0, const float* z1, int B, int M, int N, float threshold,
-                            int64_t* m0, int64_t* m1, float* ms0, float* ms1, float* stats, void* tail,
-                            hipStream_t st);
+                            int64_t* m0, int64_t* m1, float* ms0, float* ms1, void* tail, hipStream_t st);
 
 // GFC_SOURCE_HASH: content hash of the whole source set, passed by csrc/build.py when it compiles this unit
 #ifndef GFC_SOURCE_HASH
@@ -33,32 +33,26 @@ extern "C" const char* gfc_version(void) { return "gfc_amd 0.6.0 (gfx950, fp32 M
 // ---------------------------------------------------------------------------------------------
 struct SpPlan {
   int H[5], W[5];  // resolution of stage 1..4 (index 1..4)
-  size_t gray, bufA, bufB;
+  size_t gray, bufA, bufB, total;  // workspace slots (gray: empty unless C == 3)
 };
 
 static SpPlan sp_plan(int B, int C, int H, int W) {
   SpPlan p;
   p.H[1] = H; p.W[1] = W;
   for (int i = 2; i <= 4; ++i) { p.H[i] = p.H[i - 1] / 2; p.W[i] = p.W[i - 1] / 2; }
-  p.gray = (C == 3) ? gfc_align((size_t)B * H * W * sizeof(float)) : 0;
   // conv1a never touches HBM (fused into the stem kernel): the largest activation is conv2a's
-  size_t a = (size_t)B * p.H[2] * p.W[2] * 64;
-  size_t a3 = (size_t)B * p.H[3] * p.W[3] * 128, a4 = (size_t)B * p.H[4] * p.W[4] * 512;
-  if (a3 > a) a = a3;
-  if (a4 > a) a = a4;
-  size_t bsz = (size_t)B * p.H[2] * p.W[2] * 64;
-  size_t b3 = (size_t)B * p.H[3] * p.W[3] * 64, b4 = (size_t)B * p.H[4] * p.W[4] * 128;
-  if (b3 > bsz) bsz = b3;
-  if (b4 > bsz) bsz = b4;
-  p.bufA = gfc_align(a * sizeof(float));
-  p.bufB = gfc_align(bsz * sizeof(float));
+  auto px = [&](int i) { return (size_t)B * p.H[i] * p.W[i]; };  // pixels of stage i
+  gfc_slots s;
+  p.gray = s.take(C == 3 ? (size_t)B * H * W * sizeof(float) : 0);
+  p.bufA = s.take(std::max({px(2) * 64, px(3) * 128, px(4) * 512}) * sizeof(float));
+  p.bufB = s.take(std::max({px(2) * 64, px(3) * 64, px(4) * 128}) * sizeof(float));
+  p.total = s.off;
   return p;
 }
 
 extern "C" size_t gfc_sp_workspace_bytes(int B, int C, int H, int W) {
   if (B <= 0 || H < 8 || W < 8) return 0;
-  SpPlan p = sp_plan(B, C, H, W);
-  return p.gray + p.bufA + p.bufB;
+  return sp_plan(B, C, H, W).total;
 }
 
 extern "C" int gfc_event_create(void** event) {
@@ -168,13 +162,12 @@ extern "C" int gfc_sp_dense(const gfc_sp_params* p, const float* image, int B, i
     for (int i = 1; i < 8; ++i)
       if (!p->w_wino[i]) return GFC_ERR_INVALID;
   }
-  if (ws_bytes < gfc_sp_workspace_bytes(B, C, H, W)) return GFC_ERR_WORKSPACE;
+  const SpPlan pl = sp_plan(B, C, H, W);
+  if (ws_bytes < pl.total) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  SpPlan pl = sp_plan(B, C, H, W);
-  char* base = (char*)ws;
-  float* gray = (float*)base;
-  float* A = (float*)(base + pl.gray);
-  float* Bf = (float*)(base + pl.gray + pl.bufA);
+  float* gray = (float*)((char*)ws + pl.gray);
+  float* A = (float*)((char*)ws + pl.bufA);
+  float* Bf = (float*)((char*)ws + pl.bufB);
   const float* x = image;
   if (C == 3) {
     GFC_TRY(gfc_rgb_to_gray(image, gray, B, H, W, st));
@@ -217,8 +210,24 @@ extern "C" int gfc_sp_dense(const gfc_sp_params* p, const float* image, int B, i
 // ---------------------------------------------------------------------------------------------
 // LightGlue forward
 // ---------------------------------------------------------------------------------------------
-extern "C" size_t gfc_lg_layer_workspace_bytes(int rows);
-extern "C" size_t gfc_lg_assign_workspace_bytes(int B, int M, int N);
+// workspace of one layer: qkv [R,768] | ctx [R,256] | msg [R,256] | hbuf [R,512] | attention key-split scratch, every
+// slot sized for fp32.  The scratch is only needed for small row counts and is sized for the full split of the worst
+// case, n_problems * maxn = R query slots (uniform packed rows); gfc_attention lowers the split where that is exceeded.
+struct LgLayerWs { size_t qkv, ctx, msg, hbuf, att, total, att_bytes; };
+static LgLayerWs lg_layer_ws(int rows) {
+  const size_t r = rows, att_bytes = rows <= 8192 ? gfc_att_scratch_bytes(r, 4, GFC_ATT_MAX_SPLIT) : 0;
+  gfc_slots s;
+  return {s.take(r * 768 * 4), s.take(r * 256 * 4), s.take(r * 256 * 4), s.take(r * 512 * 4), s.take(att_bytes), s.off,
+          att_bytes};
+}
+
+// workspace of the assignment head: md [R,256] | z [R] | statistics + two-pass tail scratch (lg_misc.hip)
+struct LgAssignWs { size_t md, z, tail, total; };
+static LgAssignWs lg_assign_ws(int B, int M, int N) {
+  const size_t R = (size_t)B * (M + N);
+  gfc_slots s;
+  return {s.take(R * 256 * 4), s.take(R * 4), s.take(gfc_assign_tail_bytes(B, M, N)), s.off};
+}
 
 // A batch of B pairs in GROUPS = maximal runs of consecutive pairs with equal (m, n).  Rows: group after group, inside
 // a group the side-0 rows of its pairs (pair-major) followed by their side-1 rows.  A uniform batch is one group.
@@ -231,13 +240,14 @@ struct LgGroups {  // by value to the tables kernel: 2.5 KB of kernel arguments
 struct LgBatch {
   int B, groups, R, maxn;
   LgGroups tab;
-  size_t stage;  // one layer's workspace, re-used by every group's assignment head afterwards
-  size_t qkv, cosb, sinb, csb, tables, total;  // workspace slots
+  size_t stage_bytes;  // one layer's workspace, re-used by every group's assignment head afterwards
+  size_t stage, cosb, sinb, csb, tables, total;  // workspace slots
+  size_t x, kp;  // gfc_lg_forward only, in front: the rows x [R,256] | its separate arrays packed, kp [R,2] + so [R,2]
 };
 
 // rows and workspace of the groups in b.tab; false for a non-positive count, or when row offsets x 768 columns would
 // leave the int arithmetic of the kernels
-static bool lg_layout(LgBatch& b) {
+static bool lg_layout(LgBatch& b, bool staged) {
   long long R = 0;
   size_t asg = 0;
   b.maxn = 0;
@@ -249,29 +259,32 @@ static bool lg_layout(LgBatch& b) {
     if (R > INT_MAX / 768) return false;
     if (g.m > b.maxn) b.maxn = g.m;
     if (g.n > b.maxn) b.maxn = g.n;
-    const size_t a = gfc_lg_assign_workspace_bytes(g.count, g.m, g.n);
+    const size_t a = lg_assign_ws(g.count, g.m, g.n).total;
     if (a > asg) asg = a;
   }
   b.R = (int)R;
-  b.stage = gfc_lg_layer_workspace_bytes(b.R);
-  if (asg > b.stage) b.stage = asg;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += gfc_align(bytes); return o; };
-  b.qkv = take(b.stage);
-  b.cosb = take(R * 64 * 4);
-  b.sinb = take(R * 64 * 4);
-  b.csb = take(R * 64 * 4);  // the same values packed (cos, sin) per frequency: what the QKV epilogue reads
-  b.tables = take((size_t)b.B * (2 * 4 * 2 + 2 + 2 + 4) * 4 + 256);
-  b.total = off;
+  b.stage_bytes = lg_layer_ws(b.R).total;
+  if (asg > b.stage_bytes) b.stage_bytes = asg;
+  gfc_slots s;
+  if (staged) {
+    b.x = s.take(R * 256 * 4);
+    b.kp = s.take(R * 4 * 4);
+  }
+  b.stage = s.take(b.stage_bytes);
+  b.cosb = s.take(R * 64 * 4);
+  b.sinb = s.take(R * 64 * 4);
+  b.csb = s.take(R * 64 * 4);  // the same values packed (cos, sin) per frequency: what the QKV epilogue reads
+  b.tables = s.take((size_t)b.B * (2 * 4 * 2 + 2 + 2 + 4) * 4 + 256);
+  b.total = s.off;
   return true;
 }
 
 // B equal pairs: one group, any B
-static bool lg_uniform(int B, int M, int N, LgBatch& b) {
+static bool lg_uniform(int B, int M, int N, LgBatch& b, bool staged = false) {
   b = LgBatch{};
   b.B = B; b.groups = 1;
   b.tab.g[0] = {0, B, M, N, 0};
-  return lg_layout(b);
+  return lg_layout(b, staged);
 }
 
 // B <= GFC_LG_MAX_RAGGED_PAIRS pairs with their own (m[i], n[i])
@@ -285,15 +298,12 @@ static bool lg_ragged(int B, const int32_t* m, const int32_t* n, LgBatch& b) {
     b.tab.g[b.groups++] = {i, j - i, m[i], n[i], 0};
     i = j;
   }
-  return lg_layout(b);
+  return lg_layout(b, false);
 }
-
-// gfc_lg_forward stages its separate arrays in front of the batch's workspace: x [R,256] | kp [R,2] + so [R,2]
-static size_t lg_staging_bytes(const LgBatch& b) { return gfc_align((size_t)b.R * 256 * 4) + gfc_align((size_t)b.R * 4 * 4); }
 
 extern "C" size_t gfc_lg_workspace_bytes(int B, int M, int N) {
   LgBatch b;
-  return lg_uniform(B, M, N, b) ? lg_staging_bytes(b) + b.total : 0;
+  return lg_uniform(B, M, N, b, true) ? b.total : 0;
 }
 extern "C" size_t gfc_lg_packed_workspace_bytes(int B, int M, int N) {
   LgBatch b;
@@ -332,16 +342,7 @@ __global__ void lg_tables_kernel(LgGroups t, int groups, int B, const float* siz
 // ---- stage entry points (gfc_lg_forward is built from them; the adaptive depth / width path of
 // lightglue.py:500-521 drives them layer by layer from the host) ----
 
-// workspace of one layer: qkv [R,768] | ctx [R,256] | msg [R,256] | hbuf [R,512] | attention key-split scratch
-// (the scratch is only needed for small row counts; sized for the worst case 2 problems x R/2 queries)
-static size_t lg_attn_scratch_bytes(int rows) {
-  return rows <= 8192 ? gfc_align((size_t)rows * 4 * 8 * 66 * 4) : 0;
-}
-extern "C" size_t gfc_lg_layer_workspace_bytes(int rows) {
-  if (rows <= 0) return 0;
-  return gfc_align((size_t)rows * 768 * 4) + 2 * gfc_align((size_t)rows * 256 * 4) +
-         gfc_align((size_t)rows * 512 * 4) + lg_attn_scratch_bytes(rows);
-}
+extern "C" size_t gfc_lg_layer_workspace_bytes(int rows) { return rows <= 0 ? 0 : lg_layer_ws(rows).total; }
 
 static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, const float* csb,
                          int R, const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
@@ -403,30 +404,25 @@ static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* c
   if (l < 0 || l >= p->n_layers) return GFC_ERR_INVALID;
   if (p->precision != GFC_LG_FP32 && p->precision != GFC_LG_FP16) return GFC_ERR_INVALID;
   if (p->precision == GFC_LG_FP16 && !lg_f16_layer_ok(p, l)) return GFC_ERR_INVALID;
-  if (ws_bytes < gfc_lg_layer_workspace_bytes(R)) return GFC_ERR_WORKSPACE;
+  const LgLayerWs L = lg_layer_ws(R);
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int D = 256;
-  // the slots of gfc_lg_layer_workspace_bytes, sized for fp32 in either precision
-  char* qkv_slot = (char*)ws;
-  char* ctx_slot = qkv_slot + gfc_align((size_t)R * 768 * 4);
-  char* msg_slot = ctx_slot + gfc_align((size_t)R * 256 * 4);
-  float* hbuf = (float*)(msg_slot + gfc_align((size_t)R * 256 * 4));
-  void* att_ws = (char*)hbuf + gfc_align((size_t)R * 512 * 4);
-  // scratch is indexed [problem][head][max_n queries][split]: with n_problems * maxn <= R (uniform packed rows) it holds
-  // the full 8-way key split; for ragged problem sets gfc_attention lowers the split until it fits
-  const size_t att_ws_bytes = lg_attn_scratch_bytes(R);
+  char* base = (char*)ws;
+  float* hbuf = (float*)(base + L.hbuf);
   const float* xs = x_in ? x_in : x;  // what the self block reads
 
   auto layer = [&](auto prec) -> int {
     using P = decltype(prec);
     using T = typename P::T;
-    T* qkv = (T*)qkv_slot;
-    T* ctx = (T*)ctx_slot;
-    T* msg = (T*)msg_slot;
+    T* qkv = (T*)(base + L.qkv);
+    T* ctx = (T*)(base + L.ctx);
+    T* msg = (T*)(base + L.msg);
     // attention (with its key split for small problem sets)
     auto attn = [&](const T* q, int ldq, const T* k, int ldk, const T* v, int ldv, const int32_t* probs) -> int {
       const bool rec = trace_begin(tr, st);
-      const int s = P::attention(q, ldq, k, ldk, v, ldv, ctx, D, probs, n_problems, maxn, 4, 0.125f, att_ws, att_ws_bytes, st);
+      const int s = P::attention(q, ldq, k, ldk, v, ldv, ctx, D, probs, n_problems, maxn, 4, 0.125f, base + L.att,
+                                 L.att_bytes, st);
       trace_end(tr, st, rec);
       return s;
     };
@@ -498,11 +494,8 @@ extern "C" int gfc_lg_rowdot(const float* x, int ld, int rows, const float* w, c
   return GFC_OK;
 }
 
-// workspace of the assignment head: md [R,256] | z [R] | stats | two-pass tail scratch
 extern "C" size_t gfc_lg_assign_workspace_bytes(int B, int M, int N) {
-  if (B <= 0 || M <= 0 || N <= 0) return 0;
-  const size_t R = (size_t)B * (M + N);
-  return gfc_align(R * 256 * 4) + gfc_align(R * 4) + gfc_align(2 * R * 4) + gfc_assign_tail_bytes(B, M, N);
+  return B <= 0 || M <= 0 || N <= 0 ? 0 : lg_assign_ws(B, M, N).total;
 }
 
 // MatchAssignment of layer l + filter_matches (lightglue.py:279-288,294-319).  x0 [B*M,256], x1 [B*N,256].
@@ -514,15 +507,13 @@ extern "C" int gfc_lg_assign(const gfc_lg_params* p, int l, const float* x0, con
   if (l < 0 || l >= p->n_layers || !p->final_proj_w[l] || !p->matchability_w[l]) return GFC_ERR_INVALID;
   if (p->precision != GFC_LG_FP32 && p->precision != GFC_LG_FP16) return GFC_ERR_INVALID;
   if (p->precision == GFC_LG_FP16 && !p->final_proj_w16[l]) return GFC_ERR_INVALID;
-  if (ws_bytes < gfc_lg_assign_workspace_bytes(B, M, N)) return GFC_ERR_WORKSPACE;
+  const LgAssignWs L = lg_assign_ws(B, M, N);
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int D = 256, R0 = B * M, R1 = B * N;
-  const size_t R = (size_t)R0 + R1;
-  char* base = (char*)ws;
-  float* md = (float*)base;
-  float* z = (float*)(base + gfc_align(R * 256 * 4));
-  float* stats = (float*)((char*)z + gfc_align(R * 4));
-  void* tail = (char*)stats + gfc_align(2 * R * 4);
+  float* md = (float*)((char*)ws + L.md);
+  float* z = (float*)((char*)ws + L.z);
+  void* tail = (char*)ws + L.tail;
   auto head = [&](auto prec) -> int {
     using P = decltype(prec);
     // mdesc (T: fp16 fills the front half of the fp32 slot) and the similarity on this precision's MFMA; sim is fp32
@@ -538,7 +529,7 @@ extern "C" int gfc_lg_assign(const gfc_lg_params* p, int l, const float* x0, con
     GFC_TRY(P::batched_nt(md0, D, (long long)M * D, md1, D, (long long)N * D, log_assignment, N + 1,
                           (long long)(M + 1) * (N + 1), M, N, D, B, st));
     // statistics in one sweep, final scores + arg-max in a second one
-    return gfc_assign_filter_fused(log_assignment, z, z + R0, B, M, N, threshold, m0, m1, ms0, ms1, stats, tail, st);
+    return gfc_assign_filter_fused(log_assignment, z, z + R0, B, M, N, threshold, m0, m1, ms0, ms1, tail, st);
   };
   return p->precision == GFC_LG_FP16 ? head(LgF16{}) : head(LgF32{});
 }
@@ -586,7 +577,7 @@ static int lg_forward_core(const gfc_lg_params* p, const LgBatch& bt, const floa
     x_in = nullptr;
   }
   for (int l = 0; l < p->n_layers; ++l)
-    GFC_TRY(lg_layer_impl(p, l, x, cosb, sinb, csb, R, self_p, cross_p, 2 * B, bt.maxn, base + bt.qkv, bt.stage, st,
+    GFC_TRY(lg_layer_impl(p, l, x, cosb, sinb, csb, R, self_p, cross_p, 2 * B, bt.maxn, base + bt.stage, bt.stage_bytes, st,
                           l == 0 ? x_in : nullptr, tr));
 
   // ---- assignment (lightglue.py:279-288) + filter (lightglue.py:294-319), one batched call per group ----
@@ -596,7 +587,7 @@ static int lg_forward_core(const gfc_lg_params* p, const LgBatch& bt, const floa
     const float* x0 = x + (size_t)g.row0 * D;
     const float* x1 = x0 + (size_t)g.count * g.m * D;
     GFC_TRY(gfc_lg_assign(p, p->n_layers - 1, x0, x1, g.count, g.m, g.n, threshold, m0 + o0, m1 + o1, ms0 + o0,
-                          ms1 + o1, log_assignment + os, base + bt.qkv, bt.stage, st));
+                          ms1 + o1, log_assignment + os, base + bt.stage, bt.stage_bytes, st));
     o0 += (size_t)g.count * g.m; o1 += (size_t)g.count * g.n; os += (size_t)g.count * (g.m + 1) * (g.n + 1);
   }
   return GFC_OK;
@@ -661,17 +652,19 @@ extern "C" int gfc_lg_forward(const gfc_lg_params* p, const float* kpts0, const 
       !log_assignment || !ws)
     return GFC_ERR_INVALID;
   LgBatch bt;
-  if (!lg_params_ok(p, scale_ori0 != nullptr && scale_ori1 != nullptr) || !lg_uniform(B, M, N, bt))
+  if (!lg_params_ok(p, scale_ori0 != nullptr && scale_ori1 != nullptr) || !lg_uniform(B, M, N, bt, true))
     return GFC_ERR_INVALID;
   if ((scale_ori0 != nullptr) != (scale_ori1 != nullptr)) return GFC_ERR_INVALID;
-  const size_t staging = lg_staging_bytes(bt);
-  if (ws_bytes < staging + bt.total) return GFC_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  float* x = (float*)ws;
-  float* kp = (float*)((char*)ws + gfc_align((size_t)bt.R * 256 * 4));
-  char* base = (char*)ws + staging;  // the batch's own workspace
   const int R0 = B * M, R1 = B * N;
   const int Din = p->input_dim;
+  const bool adjacent = desc1 == desc0 + (size_t)R0 * Din;
+  // descriptors of an input_dim != 256 model that are not adjacent are packed into the layer scratch: they must fit
+  if (!adjacent && Din != 256 && (size_t)bt.R * Din * 4 > bt.stage_bytes) return GFC_ERR_INVALID;
+  if (ws_bytes < bt.total) return GFC_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)ws;
+  float* x = (float*)(base + bt.x);
+  float* kp = (float*)(base + bt.kp);
   auto d2d = [&](void* dst, const void* src, size_t bytes) {
     return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
   };
@@ -686,8 +679,8 @@ extern "C" int gfc_lg_forward(const gfc_lg_params* p, const float* kpts0, const 
   // descriptors: packed into the row buffer (input_dim == 256), or -- when the two arrays happen to be adjacent in
   // memory -- read in place; with an input projection the packed copy lives in the (not yet used) layer scratch
   const float* desc = desc0;
-  if (desc1 != desc0 + (size_t)R0 * Din) {
-    float* stage = Din == 256 ? x : (float*)(base + bt.qkv);
+  if (!adjacent) {
+    float* stage = Din == 256 ? x : (float*)(base + bt.stage);
     if (!d2d(stage, desc0, (size_t)R0 * Din * 4) || !d2d(stage + (size_t)R0 * Din, desc1, (size_t)R1 * Din * 4))
       return GFC_ERR_LAUNCH;
     desc = stage;

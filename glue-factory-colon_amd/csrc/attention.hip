@@ -236,12 +236,12 @@ __global__ __launch_bounds__(64 * AW, 2) void attention_kernel(const float* __re
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
       if (q[t] < nq) {
-        float* pp = part + ((((size_t)bz * gridDim.y + head) * max_nq + q[t]) * ksplit + ks) * 66;
+        float* pp = part + ((((size_t)bz * gridDim.y + head) * max_nq + q[t]) * ksplit + ks) * GFC_ATT_PART;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            float* dst = pp + db * 32 + 8 * g + 4 * h;  // 8-byte aligned (66 floats per record)
+            float* dst = pp + db * 32 + 8 * g + 4 * h;  // 8-byte aligned (GFC_ATT_PART is even)
             dst[0] = o[t][db][4 * g]; dst[1] = o[t][db][4 * g + 1];
             dst[2] = o[t][db][4 * g + 2]; dst[3] = o[t][db][4 * g + 3];
           }
@@ -285,15 +285,15 @@ __global__ __launch_bounds__(256) void attention_merge_kernel(const float* __res
   const int4 pb = problems[blockIdx.z];
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6), head = blockIdx.y, lane = threadIdx.x & 63;
   if (q >= pb.y) return;
-  const float* pp = part + (((size_t)blockIdx.z * gridDim.y + head) * max_nq + q) * ksplit * 66;
+  const float* pp = part + (((size_t)blockIdx.z * gridDim.y + head) * max_nq + q) * ksplit * GFC_ATT_PART;
   float m = -INFINITY;
-  for (int s = 0; s < ksplit; ++s) m = fmaxf(m, pp[s * 66 + 64]);
+  for (int s = 0; s < ksplit; ++s) m = fmaxf(m, pp[s * GFC_ATT_PART + 64]);
   float acc = 0.f, l = 0.f;
   for (int s = 0; s < ksplit; ++s) {
-    const float ms = pp[s * 66 + 64];
+    const float ms = pp[s * GFC_ATT_PART + 64];
     const float w = (ms == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(ms - m);  // (partials carry the maximum in log2 units)
-    acc += w * pp[s * 66 + lane];
-    l += w * pp[s * 66 + 65];
+    acc += w * pp[s * GFC_ATT_PART + lane];
+    l += w * pp[s * GFC_ATT_PART + 65];
   }
   O[(size_t)(pb.x + q) * ldo + head * AD + lane] = acc / l;
 }
@@ -303,7 +303,7 @@ extern "C" size_t gfc_attention_workspace_bytes(int n_problems, int max_nq, int 
   if (n_problems <= 0 || max_nq <= 0 || heads <= 0) return 0;
   const long long wgs128 = (long long)((max_nq + 127) / 128) * heads * n_problems;
   if (wgs128 >= 256) return 0;
-  return gfc_align((size_t)n_problems * heads * max_nq * 8 * 66 * sizeof(float));
+  return gfc_align(gfc_att_scratch_bytes((size_t)n_problems * max_nq, heads, GFC_ATT_MAX_SPLIT));
 }
 
 extern "C" int gfc_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O,
@@ -320,16 +320,9 @@ extern "C" int gfc_attention(const float* Q, int ldq, const float* K, int ldk, c
   const float sl2 = scale * 1.4426950408889634f;
   hipStream_t st = (hipStream_t)stream;
   const int4* pt = reinterpret_cast<const int4*>(problems);
-  // key split for small problem sets (batch 1..2): few 128-query blocks cannot fill 1024 SIMDs, so each block's
-  // keys are shared out over up to 8 workgroups and a tiny merge kernel combines the partial soft-maxes
-  int ksplit = 1;
-  if (cfg == 2 && ws != nullptr) {
-    const long long w = wgs(128);
-    int want = w >= 256 ? 1 : (int)((511 + w) / w);
-    if (want > 8) want = 8;
-    while (want > 1 && ws_bytes < (size_t)n_problems * heads * max_nq * want * 66 * sizeof(float)) --want;
-    ksplit = want < 1 ? 1 : want;
-  }
+  // key split for small problem sets (batch 1..2, gfc_att_split); a tiny merge kernel combines the partial soft-maxes
+  const int ksplit =
+      cfg == 2 && ws != nullptr ? gfc_att_split(wgs(128), (size_t)n_problems * max_nq, heads, ws_bytes) : 1;
   if (cfg == 1) {
     hipLaunchKernelGGL(attention_kernel<2>, dim3((max_nq + 255) / 256, heads, n_problems), dim3(256), 0, st, Q, ldq, K,
                        ldk, V, ldv, O, ldo, pt, sl2, 1, (float*)nullptr, max_nq, 1);

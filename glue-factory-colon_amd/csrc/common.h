@@ -111,4 +111,30 @@ int gfc_lg_posenc_packed(const float* kpts, const float* scale_ori, const float*
 int gfc_linear_rot_packed(const float* A0, int lda0, int K0, const float* W, int ldw, const float* bias, const float* rot_cs,
                           int rot_cols, float* Y, int ldy, int M, int N, void* stream);
 
+// ---- workspaces.  Every (ws, ws_bytes) workspace has ONE layout function beside its entry point: it returns a struct
+// of byte offsets plus `total`, built with gfc_slots.  The *_workspace_bytes export returns that total; the entry point
+// compares ws_bytes with it and forms every pointer as (T*)((char*)ws + L.slot).  No slot size is written twice.
 static inline size_t gfc_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// (a layout is written as one braced list `{s.take(a), s.take(b), ..., s.off}`: its elements are evaluated in order)
+struct gfc_slots {
+  size_t off = 0;  // after the last take: the total
+  size_t take(size_t bytes) { const size_t o = off; off += gfc_align(bytes); return o; }
+};
+
+// Attention key-split partials (attention.hip, lg_fp16.hip): [problem][head][max_nq queries][split] records of
+// GFC_ATT_PART floats (64 O | running max | running sum), split <= GFC_ATT_MAX_SPLIT.
+constexpr int GFC_ATT_PART = 66;
+constexpr int GFC_ATT_MAX_SPLIT = 8;
+// bytes of the partials of `queries` = n_problems * max_nq query slots
+static inline size_t gfc_att_scratch_bytes(size_t queries, int heads, int split) {
+  return queries * heads * split * GFC_ATT_PART * sizeof(float);
+}
+// The split for wgs128 workgroups of 128 queries: few of them cannot fill 1024 SIMDs, so each one's keys are shared
+// out over enough workgroups to reach 512, at most GFC_ATT_MAX_SPLIT, and no more than fit in ws_bytes (1: no split).
+static inline int gfc_att_split(long long wgs128, size_t queries, int heads, size_t ws_bytes) {
+  if (wgs128 >= 256) return 1;
+  int want = (int)((511 + wgs128) / wgs128);
+  if (want > GFC_ATT_MAX_SPLIT) want = GFC_ATT_MAX_SPLIT;
+  while (want > 1 && ws_bytes < gfc_att_scratch_bytes(queries, heads, want)) --want;
+  return want;
+}

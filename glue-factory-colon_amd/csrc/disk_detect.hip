@@ -202,9 +202,15 @@ __global__ __launch_bounds__(1024) void disk_select_kernel(const float* __restri
   if (tid == 0) counts[b] = min(s_base, lim);
 }
 
+// survivor map [B,H,W] | survivor list: index [B,H*W] | score [B,H*W]
+struct disk_select_layout { size_t cand, list_idx, list_sc, total; };
+static disk_select_layout disk_select_plan(int B, int H, int W) {
+  const size_t plane = (size_t)B * H * W * sizeof(float);
+  gfc_slots s;
+  return {s.take(plane), s.take(plane), s.take(plane), s.off};
+}
 extern "C" size_t gfc_disk_select_workspace_bytes(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return 3 * gfc_align((size_t)B * H * W * sizeof(float));  // survivor map, survivor list (index, score)
+  return B <= 0 || H <= 0 || W <= 0 ? 0 : disk_select_plan(B, H, W).total;
 }
 
 extern "C" int gfc_disk_nms_select(const float* heatmap, int B, int H, int W, int window, float cutoff, int n, int cap,
@@ -214,9 +220,10 @@ extern "C" int gfc_disk_nms_select(const float* heatmap, int B, int H, int W, in
   if (window % 2 != 1 || window < 1) return GFC_ERR_INVALID;  // kornia raises for even windows
   if (n >= 0 && cap < n) return GFC_ERR_INVALID;
   if (n < 0 && cap < H * W) return GFC_ERR_INVALID;
-  if (ws_bytes < gfc_disk_select_workspace_bytes(B, H, W)) return GFC_ERR_WORKSPACE;
+  const disk_select_layout L = disk_select_plan(B, H, W);
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  float* cand = (float*)ws;
+  float* cand = (float*)((char*)ws + L.cand);
   dim3 grid((W + DK_T - 1) / DK_T, (H + DK_T - 1) / DK_T, B);
   switch (window) {
     case 1: hipLaunchKernelGGL(disk_nms_kernel<0>, grid, dim3(256), 0, st, heatmap, H, W, cutoff, cand); break;
@@ -226,9 +233,8 @@ extern "C" int gfc_disk_nms_select(const float* heatmap, int B, int H, int W, in
     case 9: hipLaunchKernelGGL(disk_nms_kernel<4>, grid, dim3(256), 0, st, heatmap, H, W, cutoff, cand); break;
     default: return GFC_ERR_UNSUPPORTED;
   }
-  const size_t plane = gfc_align((size_t)B * H * W * sizeof(float));
-  int* list_idx = reinterpret_cast<int*>((char*)ws + plane);
-  float* list_sc = reinterpret_cast<float*>((char*)ws + 2 * plane);
+  int* list_idx = (int*)((char*)ws + L.list_idx);
+  float* list_sc = (float*)((char*)ws + L.list_sc);
   hipLaunchKernelGGL(disk_select_kernel, dim3(B), dim3(1024), 0, st, cand, H, W, n, cap, kpts, kscores, counts, list_idx,
                      list_sc);
   GFC_LAUNCH_CHECK();

@@ -236,14 +236,18 @@ __global__ __launch_bounds__(256) void adaptive_pack_kernel(
   }
 }
 
-size_t flags_bytes(int rows) { return gfc_align((size_t)rows * 4); }
-size_t segcnt_bytes(int B) { return gfc_align((size_t)B * 4 * 4); }
+// flags [rows] | segcnt [2B][2] | plan [B][4]
+struct step_layout { size_t flags, segcnt, plan, total; };
+step_layout step_plan(int B, int rows) {
+  gfc_slots s;
+  return {s.take((size_t)rows * 4), s.take((size_t)B * 4 * 4), s.take((size_t)B * 4 * 4), s.off};
+}
 
 }  // namespace
 
 extern "C" size_t gfc_lg_adaptive_step_workspace_bytes(int B, int rows) {
   if (B <= 0 || B > GFC_LG_MAX_RAGGED_PAIRS || rows <= 0 || rows > INT_MAX / 768) return 0;
-  return flags_bytes(rows) + 2 * segcnt_bytes(B);  // flags [rows] | segcnt [2B][2] | plan [B][4]
+  return step_plan(B, rows).total;
 }
 
 extern "C" int gfc_lg_adaptive_step(const gfc_lg_params* p, int layer, const float* x, const float* cos_tab,
@@ -272,11 +276,12 @@ extern "C" int gfc_lg_adaptive_step(const gfc_lg_params* p, int layer, const flo
   // the re-pack is a copy between two sets of buffers, and pack reads the tables plan has replaced
   if (x_out == x || cos_out == cos_tab || sin_out == sin_tab || ind_out == ind || seg_out == seg || pairs_out == pairs)
     return GFC_ERR_INVALID;
-  if (ws_bytes < gfc_lg_adaptive_step_workspace_bytes(B, rows)) return GFC_ERR_WORKSPACE;
+  const step_layout L = step_plan(B, rows);
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  int32_t* flags = (int32_t*)ws;
-  int32_t* segcnt = (int32_t*)((char*)ws + flags_bytes(rows));
-  int32_t* plan = (int32_t*)((char*)segcnt + segcnt_bytes(B));
+  int32_t* flags = (int32_t*)((char*)ws + L.flags);
+  int32_t* segcnt = (int32_t*)((char*)ws + L.segcnt);
+  int32_t* plan = (int32_t*)((char*)ws + L.plan);
   hipLaunchKernelGGL(adaptive_decide_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, rows,
                      do_stop ? p->token_w[layer] : nullptr, do_stop ? p->token_b[layer] : nullptr,
                      do_prune ? p->matchability_w[layer] : nullptr, do_prune ? p->matchability_b[layer] : nullptr, thr,

@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void attention_f16_kernel(const _Float16* _
   // lane holds O[q][32 dt + 8 g + 4 h + (0..3)] in registers 4g..4g+3 of o[dt]
   if (q >= nq) return;
   if (part != nullptr) {
-    float* pp = part + ((((size_t)bz * gridDim.y + head) * max_nq + q) * ksplit + ks) * 66;
+    float* pp = part + ((((size_t)bz * gridDim.y + head) * max_nq + q) * ksplit + ks) * GFC_ATT_PART;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -383,15 +383,15 @@ __global__ __launch_bounds__(256) void attention_f16_merge_kernel(const float* _
   const int4 pb = problems[blockIdx.z];
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6), head = blockIdx.y, lane = threadIdx.x & 63;
   if (q >= pb.y) return;
-  const float* pp = part + (((size_t)blockIdx.z * gridDim.y + head) * max_nq + q) * ksplit * 66;
+  const float* pp = part + (((size_t)blockIdx.z * gridDim.y + head) * max_nq + q) * ksplit * GFC_ATT_PART;
   float m = -INFINITY;
-  for (int s = 0; s < ksplit; ++s) m = fmaxf(m, pp[s * 66 + 64]);
+  for (int s = 0; s < ksplit; ++s) m = fmaxf(m, pp[s * GFC_ATT_PART + 64]);
   float acc = 0.f, l = 0.f;
   for (int s = 0; s < ksplit; ++s) {
-    const float ms = pp[s * 66 + 64];
+    const float ms = pp[s * GFC_ATT_PART + 64];
     const float w = (ms == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(ms - m);
-    acc += w * pp[s * 66 + lane];
-    l += w * pp[s * 66 + 65];
+    acc += w * pp[s * GFC_ATT_PART + lane];
+    l += w * pp[s * GFC_ATT_PART + 65];
   }
   O[(size_t)(pb.x + q) * ldo + head * 64 + lane] = (_Float16)(acc / l);
 }
@@ -406,16 +406,9 @@ extern "C" int gfc_attention_f16(const void* Q, int ldq, const void* K, int ldk,
   hipStream_t st = (hipStream_t)stream;
   const int4* pt = reinterpret_cast<const int4*>(problems);
   const float sl2 = scale * 1.4426950408889634f;
-  // the key split of gfc_attention: few 128-query blocks cannot fill the chip, so each block's keys are shared out
-  // over up to 8 workgroups (as far as the scratch allows) and merged
+  // the key split of gfc_attention (gfc_att_split), merged below
   const long long wgs = (long long)((max_nq + 127) / 128) * heads * n_problems;
-  int ksplit = 1;
-  if (ws != nullptr && wgs < 256) {
-    int want = (int)((511 + wgs) / wgs);
-    if (want > 8) want = 8;
-    while (want > 1 && ws_bytes < (size_t)n_problems * heads * max_nq * want * 66 * sizeof(float)) --want;
-    ksplit = want;
-  }
+  const int ksplit = ws != nullptr ? gfc_att_split(wgs, (size_t)n_problems * max_nq, heads, ws_bytes) : 1;
   float* part = ksplit > 1 ? (float*)ws : nullptr;
   hipLaunchKernelGGL(attention_f16_kernel, dim3(((max_nq + 127) / 128) * ksplit, heads, n_problems), dim3(256), 0, st,
                      (const _Float16*)Q, ldq, (const _Float16*)K, ldk, (const _Float16*)V, ldv, (_Float16*)O, ldo, pt, sl2,

@@ -444,35 +444,45 @@ __global__ void assign_colarg_merge_kernel(const float* __restrict__ cpart_v, co
   col_arg[(size_t)b * N + j] = ix;
 }
 
-// scratch of the two-pass tail behind `stats`: column partials of both passes, row / column arg-max
-size_t gfc_assign_tail_bytes(int B, int M, int N) {
-  const size_t nb = (size_t)(M + AS_RB - 1) / AS_RB;
-  return gfc_align((size_t)B * nb * N * 2 * 4) + 2 * gfc_align((size_t)B * nb * N * 4) + gfc_align((size_t)B * M * 8) +
-         gfc_align((size_t)B * N * 4);
+// soft-max statistics rmax [B,M] | rlog [B,M] | cmax [B,N] | clog [B,N], packed: lse_bytes() at `slot` of whoever
+// holds them
+struct lse_stats { float *rmax, *rlog, *cmax, *clog; };
+static size_t lse_bytes(int B, int M, int N) { return (size_t)2 * B * (M + N) * sizeof(float); }
+static lse_stats lse_at(void* slot, int B, int M, int N) {
+  float* p = (float*)slot;
+  return {p, p + (size_t)B * M, p + (size_t)2 * B * M, p + (size_t)2 * B * M + (size_t)B * N};
 }
 
+// scratch of the two-pass tail: the statistics, column partials of both passes, row / column arg-max
+struct tail_layout { size_t stats, cpart, cpv, cpi, rbest, carg, total; };
+static tail_layout tail_plan(int B, int M, int N) {
+  const size_t nb = (size_t)(M + AS_RB - 1) / AS_RB, col = (size_t)B * nb * N * 4;
+  gfc_slots s;  // (rbest [B,M] | rarg [B,M] share a slot)
+  return {s.take(lse_bytes(B, M, N)), s.take(2 * col), s.take(col), s.take(col), s.take((size_t)B * M * 8),
+          s.take((size_t)B * N * 4), s.off};
+}
+size_t gfc_assign_tail_bytes(int B, int M, int N) { return tail_plan(B, M, N).total; }
+
 // sim (inner block of scores, ld = N+1) -> final scores in place + filter_matches, two sweeps over the matrix.
-// stats: 2*B*(M+N) floats; tail: gfc_assign_tail_bytes().
+// tail: gfc_assign_tail_bytes().
 int gfc_assign_filter_fused(float* scores, const float* z0, const float* z1, int B, int M, int N, float threshold,
-                            int64_t* m0, int64_t* m1, float* ms0, float* ms1, float* stats, void* tail,
-                            hipStream_t st) {
-  float* rmax = stats;
-  float* rlog = rmax + (size_t)B * M;
-  float* cmax = rlog + (size_t)B * M;
-  float* clog = cmax + (size_t)B * N;
-  const int nb = (M + AS_RB - 1) / AS_RB;
+                            int64_t* m0, int64_t* m1, float* ms0, float* ms1, void* tail, hipStream_t st) {
+  const tail_layout L = tail_plan(B, M, N);
   char* t = (char*)tail;
-  float* cpart = (float*)t;                t += gfc_align((size_t)B * nb * N * 2 * 4);
-  float* cpv = (float*)t;                  t += gfc_align((size_t)B * nb * N * 4);
-  int* cpi = (int*)t;                      t += gfc_align((size_t)B * nb * N * 4);
-  float* rbest = (float*)t;
-  int* rarg = (int*)(rbest + (size_t)B * M); t += gfc_align((size_t)B * M * 8);
-  int* carg = (int*)t;
+  const lse_stats S = lse_at(t + L.stats, B, M, N);
+  const int nb = (M + AS_RB - 1) / AS_RB;
+  float* cpart = (float*)(t + L.cpart);
+  float* cpv = (float*)(t + L.cpv);
+  int* cpi = (int*)(t + L.cpi);
+  float* rbest = (float*)(t + L.rbest);
+  int* rarg = (int*)(rbest + (size_t)B * M);
+  int* carg = (int*)(t + L.carg);
   const long long sb = (long long)(M + 1) * (N + 1);
-  hipLaunchKernelGGL(assign_stats_kernel, dim3(nb, B), dim3(256), 0, st, scores, sb, N + 1, M, N, rmax, rlog, cpart);
-  hipLaunchKernelGGL(assign_colmerge_kernel, dim3((N + 255) / 256, B), dim3(256), 0, st, cpart, nb, N, cmax, clog);
-  hipLaunchKernelGGL(assign_finalize_argmax_kernel, dim3(nb, B), dim3(256), 0, st, scores, M, N, z0, z1, rmax, rlog,
-                     cmax, clog, rbest, rarg, cpv, cpi);
+  hipLaunchKernelGGL(assign_stats_kernel, dim3(nb, B), dim3(256), 0, st, scores, sb, N + 1, M, N, S.rmax, S.rlog,
+                     cpart);
+  hipLaunchKernelGGL(assign_colmerge_kernel, dim3((N + 255) / 256, B), dim3(256), 0, st, cpart, nb, N, S.cmax, S.clog);
+  hipLaunchKernelGGL(assign_finalize_argmax_kernel, dim3(nb, B), dim3(256), 0, st, scores, M, N, z0, z1, S.rmax, S.rlog,
+                     S.cmax, S.clog, rbest, rarg, cpv, cpi);
   hipLaunchKernelGGL(assign_colarg_merge_kernel, dim3((N + 255) / 256, B), dim3(256), 0, st, cpv, cpi, nb, N, carg);
   const int mn = M > N ? M : N;
   hipLaunchKernelGGL(mutual_kernel, dim3((mn + 255) / 256, B), dim3(256), 0, st, rbest, rarg, carg, M, N, threshold,
@@ -484,17 +494,14 @@ int gfc_assign_filter_fused(float* scores, const float* z0, const float* z1, int
 extern "C" int gfc_lg_log_assignment(const float* sim, const float* z0, const float* z1, int B, int M, int N,
                                      float* out, void* ws, size_t ws_bytes, void* stream) {
   if (!sim || !z0 || !z1 || !out || !ws || B <= 0 || M <= 0 || N <= 0) return GFC_ERR_INVALID;
-  if (ws_bytes < (size_t)2 * B * (M + N) * sizeof(float)) return GFC_ERR_WORKSPACE;
+  if (ws_bytes < lse_bytes(B, M, N)) return GFC_ERR_WORKSPACE;  // the statistics are the whole workspace, to the byte
   hipStream_t st = (hipStream_t)stream;
-  float* rmax = (float*)ws;
-  float* rlog = rmax + (size_t)B * M;
-  float* cmax = rlog + (size_t)B * M;
-  float* clog = cmax + (size_t)B * N;
+  const lse_stats S = lse_at(ws, B, M, N);
   const long long sb = (long long)M * N;
-  hipLaunchKernelGGL(lse_rows_kernel, dim3((M + 3) / 4, B), dim3(256), 0, st, sim, sb, N, M, N, rmax, rlog);
-  hipLaunchKernelGGL(lse_cols_kernel, dim3((N + 31) / 32, B), dim3(256), 0, st, sim, sb, N, M, N, cmax, clog);
+  hipLaunchKernelGGL(lse_rows_kernel, dim3((M + 3) / 4, B), dim3(256), 0, st, sim, sb, N, M, N, S.rmax, S.rlog);
+  hipLaunchKernelGGL(lse_cols_kernel, dim3((N + 31) / 32, B), dim3(256), 0, st, sim, sb, N, M, N, S.cmax, S.clog);
   hipLaunchKernelGGL(assign_finalize_kernel, dim3((N + 1 + 255) / 256, M + 1, B), dim3(256), 0, st, sim, sb, N, z0, z1,
-                     M, N, rmax, rlog, cmax, clog, out);
+                     M, N, S.rmax, S.rlog, S.cmax, S.clog, out);
   GFC_LAUNCH_CHECK();
   return GFC_OK;
 }
@@ -576,14 +583,22 @@ __global__ void mutual_kernel(const float* __restrict__ max0, const int* __restr
   }
 }
 
+// max0 [B,M] | i0 [B,M] | i1 [B,N], packed; the ABI asks for 8 bytes per key point of either side
+struct filter_layout { size_t max0, i0, i1, total; };
+static filter_layout filter_plan(int B, int M, int N) {
+  const size_t r = (size_t)B * M * 4;
+  return {0, r, 2 * r, (size_t)B * (M + N) * 8};
+}
+
 extern "C" int gfc_lg_filter_matches(const float* scores, int B, int M, int N, float threshold, int64_t* m0,
                                      int64_t* m1, float* ms0, float* ms1, void* ws, size_t ws_bytes, void* stream) {
   if (!scores || !m0 || !m1 || !ms0 || !ms1 || !ws || B <= 0 || M <= 0 || N <= 0) return GFC_ERR_INVALID;
-  if (ws_bytes < (size_t)B * (M + N) * 8) return GFC_ERR_WORKSPACE;
+  const filter_layout L = filter_plan(B, M, N);
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  float* max0 = (float*)ws;
-  int* i0 = (int*)(max0 + (size_t)B * M);
-  int* i1 = i0 + (size_t)B * M;
+  float* max0 = (float*)((char*)ws + L.max0);
+  int* i0 = (int*)((char*)ws + L.i0);
+  int* i1 = (int*)((char*)ws + L.i1);
   hipLaunchKernelGGL(rowargmax_kernel, dim3((M + 3) / 4, B), dim3(256), 0, st, scores, M, N, max0, i0);
   hipLaunchKernelGGL(colargmax_kernel, dim3((N + 31) / 32, B), dim3(256), 0, st, scores, M, N, i1);
   const int mn = M > N ? M : N;
@@ -707,9 +722,14 @@ __global__ __launch_bounds__(256) void nn_log_assignment_kernel(const float* __r
   out[((size_t)b * (M + 1) + i) * (N + 1) + j] = v;
 }
 
+// rb, rs, ra [B,M] | cb, cs, ca [B,N] | soft-max statistics, packed in ONE aligned slot
+struct nn_layout { size_t rb, rs, ra, cb, cs, ca, stats, total; };
+static nn_layout nn_plan(int B, int M, int N) {
+  const size_t r = (size_t)B * M * 4, c = (size_t)B * N * 4, stats = 3 * r + 3 * c;
+  return {0, r, 2 * r, 3 * r, 3 * r + c, 3 * r + 2 * c, stats, gfc_align(stats + lse_bytes(B, M, N))};
+}
 extern "C" size_t gfc_nn_workspace_bytes(int B, int M, int N) {
-  if (B <= 0 || M <= 0 || N <= 0) return 0;
-  return gfc_align((size_t)B * (M + N) * 5 * 4);
+  return B <= 0 || M <= 0 || N <= 0 ? 0 : nn_plan(B, M, N).total;
 }
 
 extern "C" int gfc_nn_match(const float* desc0, const float* desc1, int B, int M, int N, int D, double ratio_thresh,
@@ -717,18 +737,19 @@ extern "C" int gfc_nn_match(const float* desc0, const float* desc1, int B, int M
                             float* sim, float* log_assignment, void* ws, size_t ws_bytes, void* stream) {
   if (!desc0 || !desc1 || !m0 || !m1 || !ms0 || !ms1 || !sim || !ws || B <= 0 || M <= 0 || N <= 0) return GFC_ERR_INVALID;
   if (D <= 0 || D % 32) return GFC_ERR_UNSUPPORTED;
-  if (ws_bytes < gfc_nn_workspace_bytes(B, M, N)) return GFC_ERR_WORKSPACE;
+  const nn_layout L = nn_plan(B, M, N);
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   int s = gfc_batched_nt(desc0, D, (long long)M * D, desc1, D, (long long)N * D, sim, N, (long long)M * N, M, N, D, B,
                          st);
   if (s != GFC_OK) return s;
-  float* rb = (float*)ws;
-  float* rs = rb + (size_t)B * M;
-  int* ra = (int*)(rs + (size_t)B * M);
-  float* cb = (float*)(ra + (size_t)B * M);
-  float* cs = cb + (size_t)B * N;
-  int* ca = (int*)(cs + (size_t)B * N);
-  float* stats = (float*)(ca + (size_t)B * N);  // 2*(M+N) floats per batch entry
+  char* w = (char*)ws;
+  float* rb = (float*)(w + L.rb);
+  float* rs = (float*)(w + L.rs);
+  int* ra = (int*)(w + L.ra);
+  float* cb = (float*)(w + L.cb);
+  float* cs = (float*)(w + L.cs);
+  int* ca = (int*)(w + L.ca);
   hipLaunchKernelGGL(nn_top2_rows_kernel, dim3((M + 3) / 4, B), dim3(256), 0, st, sim, M, N, rb, ra, rs);
   hipLaunchKernelGGL(nn_top2_cols_kernel, dim3((N + 31) / 32, B), dim3(256), 0, st, sim, M, N, cb, ca, cs);
   const int mn = M > N ? M : N;
@@ -738,16 +759,13 @@ extern "C" int gfc_nn_match(const float* desc0, const float* desc1, int B, int M
   hipLaunchKernelGGL(nn_match_kernel, dim3((mn + 255) / 256, B), dim3(256), 0, st, rb, ra, rs, cb, ca, cs, M, N,
                      ratio_sq, dist_sq, mutual, (long long*)m0, (long long*)m1, ms0, ms1);
   if (log_assignment) {
-    float* rmax = stats;
-    float* rlog = rmax + (size_t)B * M;
-    float* cmax = rlog + (size_t)B * M;
-    float* clog = cmax + (size_t)B * N;
-    hipLaunchKernelGGL(lse_rows_kernel, dim3((M + 3) / 4, B), dim3(256), 0, st, sim, (long long)M * N, N, M, N, rmax,
-                       rlog);
-    hipLaunchKernelGGL(lse_cols_kernel, dim3((N + 31) / 32, B), dim3(256), 0, st, sim, (long long)M * N, N, M, N, cmax,
-                       clog);
+    const lse_stats S = lse_at(w + L.stats, B, M, N);
+    hipLaunchKernelGGL(lse_rows_kernel, dim3((M + 3) / 4, B), dim3(256), 0, st, sim, (long long)M * N, N, M, N, S.rmax,
+                       S.rlog);
+    hipLaunchKernelGGL(lse_cols_kernel, dim3((N + 31) / 32, B), dim3(256), 0, st, sim, (long long)M * N, N, M, N, S.cmax,
+                       S.clog);
     hipLaunchKernelGGL(nn_log_assignment_kernel, dim3((N + 1 + 255) / 256, M + 1, B), dim3(256), 0, st, sim, M, N,
-                       rmax, rlog, cmax, clog, log_assignment);
+                       S.rmax, S.rlog, S.cmax, S.clog, log_assignment);
   }
   GFC_LAUNCH_CHECK();
   return GFC_OK;

@@ -417,16 +417,10 @@ static int rs_splits(int B, int NH) {
 
 struct rs_layout { size_t corr, cidx, cnt, pscore, ph, total; };
 static rs_layout rs_plan(int B, int M, int T, int NH) {
-  rs_layout L;
   const size_t S = (size_t)rs_splits(B, NH);
-  size_t off = 0;
-  L.corr = off; off += gfc_align((size_t)B * M * sizeof(float4));
-  L.cidx = off; off += gfc_align((size_t)B * M * sizeof(int));
-  L.cnt = off; off += gfc_align((size_t)B * sizeof(int));
-  L.pscore = off; off += gfc_align((size_t)B * S * T * sizeof(double));
-  L.ph = off; off += gfc_align((size_t)B * S * T * sizeof(int));
-  L.total = off;
-  return L;
+  gfc_slots s;
+  return {s.take((size_t)B * M * sizeof(float4)), s.take((size_t)B * M * sizeof(int)), s.take((size_t)B * sizeof(int)),
+          s.take((size_t)B * S * T * sizeof(double)), s.take((size_t)B * S * T * sizeof(int)), s.off};
 }
 
 extern "C" size_t gfc_eval_homography_ransac_workspace_bytes(int B, int M, int T, int num_hypotheses) {

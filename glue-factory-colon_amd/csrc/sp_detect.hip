@@ -674,9 +674,13 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const float* __rest
   if (tid == 0) counts[b] = k;
 }
 
-extern "C" size_t gfc_sp_select_workspace_bytes(int B, int H, int W) {
-  return gfc_align((size_t)B * H * W * sizeof(unsigned long long));
+// candidate keys [B][H*W], behind the per-image counters [B] of the fused path
+struct select_layout { size_t cnt, cand, total; };
+static select_layout select_plan(int B, int H, int W, bool fused) {
+  gfc_slots s;
+  return {s.take(fused ? (size_t)B * sizeof(int) : 0), s.take((size_t)B * H * W * sizeof(unsigned long long)), s.off};
 }
+extern "C" size_t gfc_sp_select_workspace_bytes(int B, int H, int W) { return select_plan(B, H, W, false).total; }
 
 extern "C" int gfc_sp_select(const float* scores, int B, int H, int W, float threshold, int k, int cap, float* kpts,
                              float* kscores, int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
@@ -684,10 +688,11 @@ extern "C" int gfc_sp_select(const float* scores, int B, int H, int W, float thr
   if (k >= 0 && cap < k) return GFC_ERR_INVALID;
   if (k < 0 && (long long)cap < (long long)H * W) return GFC_ERR_INVALID;
   if (k > SEL_MAXK) return GFC_ERR_UNSUPPORTED;
-  if (ws_bytes < gfc_sp_select_workspace_bytes(B, H, W)) return GFC_ERR_WORKSPACE;
+  const select_layout L = select_plan(B, H, W, false);
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
   if (k == 0) return GFC_ERR_INVALID;
   hipLaunchKernelGGL(select_kernel, dim3(B), dim3(SEL_THREADS), 0, (hipStream_t)stream, scores, H, W, threshold, k, cap,
-                     kpts, kscores, counts, reinterpret_cast<unsigned long long*>(ws), (const int*)nullptr);
+                     kpts, kscores, counts, (unsigned long long*)((char*)ws + L.cand), (const int*)nullptr);
   GFC_LAUNCH_CHECK();
   return GFC_OK;
 }
@@ -695,9 +700,7 @@ extern "C" int gfc_sp_select(const float* scores, int B, int H, int W, float thr
 // Fused NMS + selection: the NMS kernel appends every pixel above the threshold to the per-image key list
 // (one atomic per wave), so the selection kernel skips its scan of the dense map, and the suppressed map itself
 // is only written when the caller asks for it (nms_out != NULL).  Needs a finite k (1..8192).
-extern "C" size_t gfc_sp_nms_select_workspace_bytes(int B, int H, int W) {
-  return gfc_align((size_t)B * sizeof(int)) + gfc_sp_select_workspace_bytes(B, H, W);
-}
+extern "C" size_t gfc_sp_nms_select_workspace_bytes(int B, int H, int W) { return select_plan(B, H, W, true).total; }
 
 extern "C" int gfc_sp_nms_select(const float* heatmap, int B, int H, int W, int radius, int border,
                                  const int32_t* valid_wh, float threshold, int k, int cap, float* nms_out, float* kpts,
@@ -707,10 +710,11 @@ extern "C" int gfc_sp_nms_select(const float* heatmap, int B, int H, int W, int 
   if (k <= 0 || cap < k) return GFC_ERR_INVALID;
   // radius 0 keeps every pixel above the threshold (10^5 candidates per image): use the two-stage path there
   if (radius < 1 || radius > NR_MAX || k > SEL_MAXK) return GFC_ERR_UNSUPPORTED;
-  if (ws_bytes < gfc_sp_nms_select_workspace_bytes(B, H, W)) return GFC_ERR_WORKSPACE;
+  const select_layout L = select_plan(B, H, W, true);
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  int* cnt = (int*)ws;
-  unsigned long long* cand = (unsigned long long*)((char*)ws + gfc_align((size_t)B * sizeof(int)));
+  int* cnt = (int*)((char*)ws + L.cnt);
+  unsigned long long* cand = (unsigned long long*)((char*)ws + L.cand);
   if (hipMemsetAsync(cnt, 0, (size_t)B * sizeof(int), st) != hipSuccess) return GFC_ERR_LAUNCH;
   int s = nms_dispatch(heatmap, B, H, W, radius, border, valid_wh, nms_out, threshold, cand, cnt, st);
   if (s != GFC_OK) return s;
