@@ -122,3 +122,141 @@ __device__ __forceinline__ float corner_error(const float* Hf, const float* Hgt 
   if (!isfinite(err)) err = INFINITY;
   return err;
 }
+
+// ---- cameras, poses and depth sampling (eval_pose.hip) -----------------------------------------------------------------
+// Restated in fp32 and in the operation order of the reference (gluefactory/geometry/wrappers.py:407-481, utils.py:92-248,
+// depth.py:8-59).  A camera is float[10] = w, h, fx, fy, cx, cy, d0..d3; a pose float[12] = R row-major, t.
+struct EpCam { float w, h, fx, fy, cx, cy, d0, d1, d2, d3; };
+struct EpPose { float r[9], t[3]; };
+
+__device__ __forceinline__ EpCam ep_load_cam(const float* p) {
+  return EpCam{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9]};
+}
+__device__ __forceinline__ EpPose ep_load_pose(const float* p) {
+  EpPose T;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) T.r[i] = p[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) T.t[i] = p[9 + i];
+  return T;
+}
+
+// Camera.image2cam: pixel -> point on the z = 1 plane.  Only the KB4 fisheye model removes its distortion: Newton on
+// theta from theta = |p|, 10 rounds, a point frozen once its own |step| < 1e-12 (undistort_points_fisheye_kb4).
+__device__ __forceinline__ void ep_image2cam(const EpCam& c, int model, float x, float y, float& nx, float& ny) {
+  nx = (x - c.cx) / c.fx;
+  ny = (y - c.cy) / c.fy;
+  if (model != GFC_CAM_OPENCV_FISHEYE) return;
+  const float theta_d = sqrtf(nx * nx + ny * ny);
+  float theta = theta_d;
+  bool active = theta_d > 1e-12f;
+  for (int it = 0; it < 10; ++it) {
+    const float t2 = theta * theta, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
+    const float f = theta * (1.0f + c.d0 * t2 + c.d1 * t4 + c.d2 * t6 + c.d3 * t8) - theta_d;
+    const float fp = 1.0f + 3.0f * c.d0 * t2 + 5.0f * c.d1 * t4 + 7.0f * c.d2 * t6 + 9.0f * c.d3 * t8;
+    const float step = f / fp;
+    if (active) theta = theta - step;
+    active = active && (fabsf(step) >= 1e-12f);
+  }
+  const float scale = theta_d > 1e-12f ? tanf(theta) / theta_d : 1.0f;
+  nx *= scale;
+  ny *= scale;
+}
+
+// Camera.cam2image: project (eps 1e-4, clamp), distort with the model's validity, denormalise, 0 <= p <= size - 1.
+__device__ __forceinline__ bool ep_cam2image(const EpCam& c, int model, float X, float Y, float Z, float& px, float& py) {
+  bool ok = Z > 1e-4f;
+  const float z = Z < 1e-4f ? 1e-4f : Z;  // clamp(min) that keeps a NaN
+  float u = X / z, v = Y / z;
+  if (model == GFC_CAM_OPENCV_FISHEYE) {
+    const float r = sqrtf(u * u + v * v);
+    const float th = atanf(r);
+    const float t2 = th * th, t3 = th * t2, t5 = t3 * t2, t7 = t5 * t2, t9 = t7 * t2;
+    const float theta_d = th + c.d0 * t3 + c.d1 * t5 + c.d2 * t7 + c.d3 * t9;
+    const float scale = r > 1e-12f ? theta_d / r : 1.0f;
+    u *= scale;
+    v *= scale;
+    ok = ok && isfinite(u) && isfinite(v);
+  } else if (model != GFC_CAM_PINHOLE) {
+    const float k1 = c.d0, k2 = c.d1;
+    const float r2 = u * u + v * v;
+    const float radial = k1 * r2 + k2 * (r2 * r2);
+    float du = u + u * radial, dv = v + v * radial;
+    // beyond the inflection point of r + k1 r^3 + k2 r^5 the model maps far points back into the image
+    const float disc = 9.f * (k1 * k1) - 20.f * k2;
+    const bool limited = (k2 > 0.f && disc > 0.f) || (k2 <= 0.f && k1 > 0.f);
+    if (limited) {
+      const float limit = fabsf(k2 > 0.f ? (sqrtf(disc) - 3.f * k1) / (10.f * k2) : 1.f / (3.f * k1));
+      ok = ok && (r2 < limit);
+    }
+    if (model == GFC_CAM_OPENCV) {
+      const float p1 = c.d2, p2 = c.d3, uv = u * v;
+      du = du + 2.f * p1 * uv + p2 * (r2 + 2.f * (u * u));
+      dv = dv + 2.f * p2 * uv + p1 * (r2 + 2.f * (v * v));
+    }
+    u = du;
+    v = dv;
+  }
+  px = u * c.fx + c.cx;
+  py = v * c.fy + c.cy;
+  return ok && px >= 0.f && px <= c.w - 1.f && py >= 0.f && py <= c.h - 1.f;
+}
+
+// sample_depth: holes (<= 0) are NaN; bilinear grid_sample(align_corners=False, zero padding) at p / (W, H) * 2 - 1
+// (a corner outside the map adds nothing, a hole inside it makes the sum NaN whatever its weight); where that is NaN,
+// the nearest sample (round half to even, 0 outside).  H, W > 0.
+__device__ __forceinline__ float ep_depth_at(const float* __restrict__ depth, int H, int W, float fx, float fy,
+                                             bool& inside) {
+  inside = fx >= 0.f && fx <= (float)(W - 1) && fy >= 0.f && fy <= (float)(H - 1);
+  if (!inside) return 0.f;
+  const float d = depth[(size_t)(int)fy * W + (int)fx];
+  return d > 0.f ? d : NAN;
+}
+
+__device__ __forceinline__ float ep_sample_depth(const float* __restrict__ depth, int H, int W, float x, float y,
+                                                 bool& valid) {
+  const float gx = x / (float)W * 2.f - 1.f, gy = y / (float)H * 2.f - 1.f;
+  const float ix = ((gx + 1.f) * (float)W - 1.f) / 2.f, iy = ((gy + 1.f) * (float)H - 1.f) / 2.f;
+  const float x0 = floorf(ix), y0 = floorf(iy), x1 = x0 + 1.f, y1 = y0 + 1.f;
+  float lin = 0.f;
+  bool in;
+  float d = ep_depth_at(depth, H, W, x0, y0, in);
+  if (in) lin += d * ((x1 - ix) * (y1 - iy));
+  d = ep_depth_at(depth, H, W, x1, y0, in);
+  if (in) lin += d * ((ix - x0) * (y1 - iy));
+  d = ep_depth_at(depth, H, W, x0, y1, in);
+  if (in) lin += d * ((x1 - ix) * (iy - y0));
+  d = ep_depth_at(depth, H, W, x1, y1, in);
+  if (in) lin += d * ((ix - x0) * (iy - y0));
+  if (isnan(lin)) lin = ep_depth_at(depth, H, W, rintf(ix), rintf(iy), in);  // 0 outside
+  valid = !isnan(lin) && lin > 0.f;
+  return lin;
+}
+
+// sample_depth + project(ccth=None) for one key point of view i: depth, its validity, the pixel in view j, visibility.
+__device__ __forceinline__ void ep_project_point(const float* __restrict__ depth_i, int Hi, int Wi, const EpCam& ci,
+                                                 int model_i, const EpCam& cj, int model_j, const EpPose& T, float x,
+                                                 float y, float& d, bool& valid, float& px, float& py, bool& visible) {
+  d = ep_sample_depth(depth_i, Hi, Wi, x, y, valid);
+  float nx, ny;
+  ep_image2cam(ci, model_i, x, y, nx, ny);
+  const float a = nx * d, b = ny * d, c = 1.0f * d;
+  const float X = a * T.r[0] + b * T.r[1] + c * T.r[2] + T.t[0];
+  const float Y = a * T.r[3] + b * T.r[4] + c * T.r[5] + T.t[1];
+  const float Z = a * T.r[6] + b * T.r[7] + c * T.r[8] + T.t[2];
+  visible = ep_cam2image(cj, model_j, X, Y, Z, px, py) && valid;
+}
+
+// block-wide sums of NV floats per thread (EM_THREADS threads): wave shuffle, then LDS atomics; acc [NV] in LDS holds
+// the totals after the call, visible to every thread
+template <int NV>
+__device__ __forceinline__ void block_sum_f32(const float* v, float* acc, int tid) {
+  if (tid < NV) acc[tid] = 0.f;
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    const float t = wave_sum(v[q]);
+    if ((tid & 63) == 0) atomicAdd(&acc[q], t);
+  }
+  __syncthreads();
+}

@@ -1,0 +1,125 @@
+"""Pose / depth evaluation of cached predictions on the GPU path -- counterpart of the `run_eval` of the reference's
+posed-pair benchmarks (gluefactory/eval/endomapper_dense1500.py:102-183; megadepth1500, scannet1500 and eth3d share its
+shape): per pair the match counts, `eval_matches_epipolar`, `eval_matches_depth` when the item carries depth, and --
+given a relative-pose estimator object -- `eval_relative_pose_robust` per RANSAC threshold with the pose AUCs at the
+best one.
+
+`items` is any iterable of the reference's data dicts, one pair each (`name`, `T_0to1`, `view0/1` = {`camera`
+[, `depth`]}, cameras and poses as geometry.Camera / Pose or the reference's wrappers).  The reference walks them pair
+by pair; here consecutive items of equal shapes (key-point counts, depth-map sizes, camera models) go through ONE call
+of each kernel (one workgroup per pair either way: the numbers do not depend on the grouping).
+
+What is NOT here: the `posed_images` directory reader (tied to the fork's scene-info files and crops), a robust
+relative-pose estimator (five-point RANSAC; the reference delegates it to OpenCV / PoseLib / pycolmap) and figures.
+"""
+from collections import defaultdict
+
+import numpy as np
+import torch
+
+from . import eval_utils, geometry
+from .cache_loader import CacheLoader
+from .eval_hpatches import CONTEXT_KEYS, MEMORY_KEYS, TIMING_KEYS, med_mean_summaries
+
+MIN_MATCHES_FOR_POSE = 5
+
+
+def _name(item):
+    return item["name"][0] if isinstance(item["name"], (list, tuple)) else item["name"]
+
+
+def _stack_holder(holders):
+    first = holders[0]
+    data = torch.cat([h._data.reshape(-1, h._data.shape[-1]) for h in holders], 0)
+    if hasattr(first, "model"):
+        out = geometry.Camera(data, model=first.model)
+    else:
+        out = geometry.Pose(data)
+    return out
+
+
+class PosePairsPipeline:
+    def __init__(self, eval_conf=None, max_group=64):
+        self.eval_conf = {"estimator": None, "ransac_th": 1.0, **dict(eval_conf or {})}
+        self.max_group = int(max_group)
+
+    def thresholds(self):
+        """endomapper_dense1500.py:107-111: a positive number -> that one, a non-positive one -> the sweep."""
+        th = self.eval_conf["ransac_th"]
+        if isinstance(th, (list, tuple, np.ndarray)):
+            return [float(t) for t in th]
+        return [float(th)] if float(th) > 0 else [0.5, 1.0, 1.5, 2.0, 2.5, 3.0]
+
+    def _flush(self, group, device, out):
+        datas, preds = zip(*group)
+
+        def stack(key, dtype):
+            return torch.stack([p[key] for p in preds]).to(device=device, dtype=dtype)
+
+        kp0, kp1, m0 = stack("keypoints0", torch.float32), stack("keypoints1", torch.float32), stack("matches0", torch.long)
+        cam0 = _stack_holder([d["view0"]["camera"] for d in datas])
+        cam1 = _stack_holder([d["view1"]["camera"] for d in datas])
+        T = _stack_holder([d["T_0to1"] for d in datas])
+        epi = eval_utils.pose_epipolar_metrics(kp0, kp1, m0, cam0, cam1, T).cpu()
+        dep = None
+        if "depth" in datas[0]["view0"]:
+            depth0 = torch.cat([d["view0"]["depth"].reshape((-1,) + tuple(d["view0"]["depth"].shape[-2:])) for d in datas])
+            depth1 = torch.cat([d["view1"]["depth"].reshape((-1,) + tuple(d["view1"]["depth"].shape[-2:])) for d in datas])
+            dep = eval_utils.pose_depth_metrics(kp0, kp1, m0, depth0, depth1, cam0, cam1, T).cpu()
+        for j in range(len(group)):
+            row = {key: (int(epi[j, c]) if key == "num_matches" else float(epi[j, c]))
+                   for c, key in enumerate(eval_utils.EPIPOLAR_RESULT_KEYS)}
+            if dep is not None:
+                row.update({key: float(dep[j, c]) for c, key in enumerate(eval_utils.DEPTH_RESULT_KEYS)})
+            out.append(row)
+
+    @staticmethod
+    def _shape_key(data, pred):
+        views = tuple((geometry.model_id(data[v]["camera"]),
+                       tuple(data[v]["depth"].shape[-2:]) if "depth" in data[v] else None) for v in ("view0", "view1"))
+        return (pred["keypoints0"].shape[0], pred["keypoints1"].shape[0], views)
+
+    def run_eval(self, items, pred_file, estimator=None, device="cuda"):
+        """-> (summaries, results): per-pair lists under the reference's keys, `med_*` / `mean_*` of every numeric
+        one; with an estimator also `rel_pose_error@{5,10,20}°`, `rel_pose_error_mAA` and the per-pair pose lists at
+        the best threshold (every tested threshold under results["pose_results"])."""
+        cache = CacheLoader({"path": str(pred_file), "collate": None, "add_data_path": False}).eval()
+        rows, extras, names = [], [], []
+        pose_results = defaultdict(lambda: defaultdict(list))
+        group, key = [], None
+        for data in items:
+            name = _name(data)
+            pred = cache({"name": [name], "view0": {"scales": data["view0"].get("scales", torch.ones(1, 2))},
+                          "view1": {"scales": data["view1"].get("scales", torch.ones(1, 2))}})
+            k = self._shape_key(data, pred)
+            if group and (k != key or len(group) >= self.max_group):
+                self._flush(group, device, rows)
+                group = []
+            key = k
+            group.append((data, pred))
+            names.append(name)
+            extras.append({q: pred[q].item() for q in (*TIMING_KEYS, *MEMORY_KEYS, *CONTEXT_KEYS) if q in pred})
+            if estimator is not None:
+                n_matches = int((pred["matches0"] > -1).sum())
+                for th in self.thresholds():
+                    if n_matches < MIN_MATCHES_FOR_POSE:
+                        res = {q: float("nan") for q in eval_utils.POSE_RESULT_KEYS}
+                    else:
+                        res = eval_utils.eval_relative_pose_robust(
+                            data, pred, {"estimator": self.eval_conf["estimator"], "ransac_th": th}, estimator=estimator)
+                    for q, v in res.items():
+                        pose_results[th][q].append(v)
+        if group:
+            self._flush(group, device, rows)
+        results = defaultdict(list)
+        for row, extra, name in zip(rows, extras, names):
+            for q, v in {**row, **extra, "names": name}.items():
+                results[q].append(v)
+        summaries = med_mean_summaries(results)
+        results = dict(results)
+        if estimator is not None and pose_results:
+            pose_results = {th: dict(r) for th, r in pose_results.items()}
+            pose_summaries, best_th = eval_utils.eval_poses(pose_results, auc_ths=[5, 10, 20], key="rel_pose_error")
+            results = {**results, **pose_results[best_th], "pose_results": pose_results}
+            summaries = {**summaries, **pose_summaries}
+        return summaries, results

@@ -232,3 +232,223 @@ def eval_homography_robust(data: dict, pred: dict, conf: dict) -> dict:
     frac = [a / max(c, 1) for a, c in zip(ninl, nmatch)]
     out = {"H_error_ransac": err, "ransac_inl": ninl, "ransac_inl%": frac}
     return out if batched else {k: v[0] for k, v in out.items()}
+
+
+# ---- pose / depth match metrics (csrc/eval_pose.hip) -------------------------------------------------------------------
+DEPTH_RESULT_KEYS = ("reproj_prec@1px", "reproj_prec@3px", "reproj_prec@5px", "covisible", "covisible_percent",
+                     "gt_match_recall@3px", "gt_match_precision@3px")
+EPIPOLAR_RESULT_KEYS = ("epi_prec@1e-4", "epi_prec@5e-4", "epi_prec@1e-3", "num_matches", "num_keypoints")
+POSE_RESULT_KEYS = ("rel_pose_error", "ransac_inl", "ransac_inl%")
+
+
+def _pair_geometry(camera0, camera1, T_0to1, batch, device):
+    from . import geometry
+
+    cam0, model0 = geometry.camera_args(camera0, batch, device)
+    cam1, model1 = geometry.camera_args(camera1, batch, device)
+    T01, T10 = geometry.pose_args(T_0to1, batch, device)
+    return cam0, model0, cam1, model1, T01, T10
+
+
+def _depth_arg(depth, batch, device):
+    d = depth.to(device=device, dtype=torch.float32)
+    d = d.reshape((-1,) + tuple(d.shape[-2:])).contiguous()
+    assert d.shape[0] == batch, f"{d.shape[0]} depth maps for {batch} pairs"
+    return d
+
+
+def pose_project(kp, depth_i, camera_i, camera_j, T_itoj):
+    """`sample_depth` + `project(ccth=None)` of the reference (geometry/depth.py) for batched device tensors: kp [B,K,2],
+    depth_i [B,H,W], cameras / pose as holders of B items (geometry.Camera / Pose or the reference's wrappers) ->
+    (depth_kp [B,K], valid [B,K] bool, proj [B,K,2], visible [B,K] bool)."""
+    from . import geometry
+
+    nat.require_cuda(kp, "keypoints")
+    dev, (b, k) = kp.device, kp.shape[:2]
+    cam_i, model_i = geometry.camera_args(camera_i, b, dev)
+    cam_j, model_j = geometry.camera_args(camera_j, b, dev)
+    T, _ = geometry.pose_args(T_itoj, b, dev)
+    depth = _depth_arg(depth_i, b, dev)
+    pts = kp.float().contiguous()
+    d = torch.empty((b, k), device=dev, dtype=torch.float32)
+    proj = torch.empty((b, k, 2), device=dev, dtype=torch.float32)
+    valid = torch.empty((b, k), device=dev, dtype=torch.uint8)
+    visible = torch.empty((b, k), device=dev, dtype=torch.uint8)
+    nat.check(nat.lib().gfc_eval_pose_project(nat.ptr(pts), nat.ptr(depth), nat.ptr(cam_i), model_i, nat.ptr(cam_j),
+                                              model_j, nat.ptr(T), b, k, depth.shape[1], depth.shape[2], nat.ptr(d),
+                                              nat.ptr(valid), nat.ptr(proj), nat.ptr(visible), nat.stream_ptr(dev)),
+              "gfc_eval_pose_project")
+    return d, valid.bool(), proj, visible.bool()
+
+
+def pose_depth_metrics(kp0, kp1, matches0, depth0, depth1, camera0, camera1, T_0to1, pos_th=3.0, neg_th=5.0,
+                       return_gt=False):
+    """Batched tensors on the device: kp0 [B,M,2], kp1 [B,N,2], matches0 [B,M], depth0 [B,H0,W0], depth1 [B,H1,W1],
+    cameras and pose as holders of B items -> [B,7] (DEPTH_RESULT_KEYS order) and optionally the ground-truth matches
+    of both views ([B,M], [B,N]; -1 unmatched, -2 ignore)."""
+    nat.require_cuda(kp0, "keypoints0")
+    dev = kp0.device
+    b, m, n = kp0.shape[0], kp0.shape[1], kp1.shape[1]
+    cam0, model0, cam1, model1, T01, T10 = _pair_geometry(camera0, camera1, T_0to1, b, dev)
+    d0, d1 = _depth_arg(depth0, b, dev), _depth_arg(depth1, b, dev)
+    k0, k1 = kp0.float().contiguous(), kp1.float().contiguous()
+    m0 = matches0.to(device=dev, dtype=torch.long).contiguous()
+    out = torch.empty((b, 7), device=dev, dtype=torch.float32)
+    gt0 = torch.empty((b, m), device=dev, dtype=torch.long) if return_gt else None
+    gt1 = torch.empty((b, n), device=dev, dtype=torch.long) if return_gt else None
+    nat.check(nat.lib().gfc_eval_matches_depth(nat.ptr(k0), nat.ptr(k1), nat.ptr(m0), nat.ptr(d0), nat.ptr(d1),
+                                               nat.ptr(cam0), model0, nat.ptr(cam1), model1, nat.ptr(T01), nat.ptr(T10),
+                                               b, m, n, d0.shape[1], d0.shape[2], d1.shape[1], d1.shape[2],
+                                               float(pos_th), float(neg_th), nat.ptr(out), nat.ptr(gt0), nat.ptr(gt1),
+                                               nat.stream_ptr(dev)), "gfc_eval_matches_depth")
+    return (out, gt0, gt1) if return_gt else out
+
+
+def pose_epipolar_metrics(kp0, kp1, matches0, camera0, camera1, T_0to1):
+    """Batched tensors on the device -> [B,5] (EPIPOLAR_RESULT_KEYS order)."""
+    nat.require_cuda(kp0, "keypoints0")
+    dev = kp0.device
+    b, m, n = kp0.shape[0], kp0.shape[1], kp1.shape[1]
+    cam0, model0, cam1, model1, T01, _ = _pair_geometry(camera0, camera1, T_0to1, b, dev)
+    k0, k1 = kp0.float().contiguous(), kp1.float().contiguous()
+    m0 = matches0.to(device=dev, dtype=torch.long).contiguous()
+    out = torch.empty((b, 5), device=dev, dtype=torch.float32)
+    nat.check(nat.lib().gfc_eval_matches_epipolar(nat.ptr(k0), nat.ptr(k1), nat.ptr(m0), nat.ptr(cam0), model0,
+                                                  nat.ptr(cam1), model1, nat.ptr(T01), b, m, n, nat.ptr(out),
+                                                  nat.stream_ptr(dev)), "gfc_eval_matches_epipolar")
+    return out
+
+
+def _pose_inputs(data, pred, need_depth):
+    for key in ("view0", "view1", "T_0to1"):
+        assert key in data, f"Missing key {key} in data"
+    for key in ("keypoints0", "keypoints1", "matches0", "matching_scores0"):
+        assert key in pred, f"Missing key {key} in pred"
+    for view in ("view0", "view1"):
+        for key in (("depth", "camera") if need_depth else ("camera",)):
+            assert key in data[view], f"Missing key {key} in data[{view}]"
+    kp0, kp1, m0 = pred["keypoints0"], pred["keypoints1"], pred["matches0"]
+    batched = kp0.ndim > 2
+    if not batched:  # the reference's loop: a loader item of batch 1 with an un-batched cached record
+        kp0, kp1, m0 = kp0[None], kp1[None], m0[None]
+    return batched, kp0, kp1, m0
+
+
+def _metric_dict(res, keys, batched, integer=()):
+    out = {}
+    for i, key in enumerate(keys):
+        vals = [int(v) if key in integer else float(v) for v in res[:, i].tolist()]
+        out[key] = vals if batched else vals[0]
+    return out
+
+
+def eval_matches_epipolar(data: dict, pred: dict) -> dict:
+    """Drop-in for gluefactory.eval.utils.eval_matches_epipolar (eval/utils.py:45-74), same keys: un-batched key
+    points give scalars, batched ones lists per item."""
+    batched, kp0, kp1, m0 = _pose_inputs(data, pred, need_depth=False)
+    res = pose_epipolar_metrics(kp0, kp1, m0, data["view0"]["camera"], data["view1"]["camera"], data["T_0to1"]).cpu()
+    return _metric_dict(res, EPIPOLAR_RESULT_KEYS, batched, integer=("num_matches",))
+
+
+def eval_matches_depth(data: dict, pred: dict) -> dict:
+    """Drop-in for gluefactory.eval.utils.eval_matches_depth (eval/utils.py:77-138), same keys: un-batched key points
+    give scalars, batched ones lists per item."""
+    batched, kp0, kp1, m0 = _pose_inputs(data, pred, need_depth=True)
+    res = pose_depth_metrics(kp0, kp1, m0, data["view0"]["depth"], data["view1"]["depth"], data["view0"]["camera"],
+                             data["view1"]["camera"], data["T_0to1"]).cpu()
+    return _metric_dict(res, DEPTH_RESULT_KEYS, batched)
+
+
+def gt_matches_from_pose_depth(kp0, kp1, data, pos_th=3, neg_th=5, epi_th=None, cc_th=None):
+    """Counterpart of gluefactory.geometry.gt_generation.gt_matches_from_pose_depth (gt_generation.py:594-727) for
+    batched device key points kp0 [B,M,2], kp1 [B,N,2] and the reference's data dict (`view0/1` = {camera, depth},
+    `T_0to1`): `matches0/1`, `matching_scores0/1`, `depth_keypoints0/1`, `proj_0to1/1to0`, `visible0/1`.
+    `assignment` and `reward` are NOT returned: they are the M x N matrices this path exists to avoid.  `epi_th` and
+    `cc_th` (None wherever the evaluation calls this) are not built."""
+    if epi_th is not None or cc_th is not None:
+        raise NotImplementedError("gt_matches_from_pose_depth: epi_th / cc_th are not built (the evaluation passes None)")
+    cam0, cam1, T = data["view0"]["camera"], data["view1"]["camera"], data["T_0to1"]
+    depth0, depth1 = data["view0"]["depth"], data["view1"]["depth"]
+    b = kp0.shape[0]
+    from . import geometry
+
+    T01, T10 = geometry.pose_args(T, b, kp0.device)
+    d0, _, p01, vis0 = pose_project(kp0, depth0, cam0, cam1, geometry.Pose(T01))
+    d1, _, p10, vis1 = pose_project(kp1, depth1, cam1, cam0, geometry.Pose(T10))
+    if kp0.shape[1] == 0 or kp1.shape[1] == 0:  # the reference returns no visibility for an empty side
+        vis0, vis1 = torch.zeros_like(vis0), torch.zeros_like(vis1)
+    m0 = torch.full(kp0.shape[:2], -1, dtype=torch.long, device=kp0.device)
+    _, g0, g1 = pose_depth_metrics(kp0, kp1, m0, depth0, depth1, cam0, cam1, T, pos_th, neg_th, return_gt=True)
+    return {"matches0": g0, "matches1": g1, "matching_scores0": (g0 > -1).float(), "matching_scores1": (g1 > -1).float(),
+            "depth_keypoints0": d0, "depth_keypoints1": d1, "proj_0to1": p01, "proj_1to0": p10, "visible0": vis0,
+            "visible1": vis1}
+
+
+def relative_pose_error(T_0to1, R, t, ignore_gt_t_thr=0.0):
+    """gluefactory.geometry.epipolar.relative_pose_error (epipolar.py:139-155): (t_err, r_err) in degrees between an
+    estimated (R, t) and the true pose (a pose holder of one item, or a [4,4] tensor).  The translation angle is taken
+    up to sign (an essential matrix fixes t only up to sign).  3 x 3 host work: torch on the CPU, in float64, and each
+    angle as atan2(sine, cosine) -- the reference's float32 acos(cosine) is the same angle with an error of
+    6e-8 / sin(angle) radians, which scores a perfect estimate at up to 0.03 degrees."""
+    if isinstance(T_0to1, torch.Tensor):
+        R_gt, t_gt = T_0to1[:3, :3], T_0to1[:3, 3]
+    else:
+        flat = T_0to1._data.reshape(-1)
+        R_gt, t_gt = flat[:9].reshape(3, 3), flat[9:]
+    R_gt, t_gt = R_gt.detach().cpu().double(), t_gt.detach().cpu().double()
+    R, t = torch.as_tensor(R).detach().cpu().double(), torch.as_tensor(t).detach().cpu().double().reshape(3)
+    t_err = torch.rad2deg(torch.atan2(torch.linalg.cross(t, t_gt).norm(), (t * t_gt).sum()))
+    t_err = torch.minimum(t_err, 180 - t_err)
+    if t_gt.norm() < ignore_gt_t_thr:  # pure rotation: the direction of t means nothing
+        t_err = torch.zeros((), dtype=torch.float64)
+    D = R.T @ R_gt  # the rotation between the two: its angle from the antisymmetric part (sine) and the trace (cosine)
+    axis = torch.stack([D[2, 1] - D[1, 2], D[0, 2] - D[2, 0], D[1, 0] - D[0, 1]])
+    r_err = torch.rad2deg(torch.atan2(axis.norm() / 2, (D.trace() - 1) / 2))
+    return t_err, r_err
+
+
+def eval_relative_pose_robust(data: dict, pred: dict, conf: dict, estimator=None) -> dict:
+    """gluefactory.eval.utils.eval_relative_pose_robust (eval/utils.py:188-222) around an estimator OBJECT of the
+    reference's interface: estimator({"m_kpts0", "m_kpts1", "camera0", "camera1"}) -> {"success", "M_0to1" (a pose
+    holder), "inliers"}.  Returns `rel_pose_error` (the larger of the rotation and translation angles, degrees),
+    `ransac_inl`, `ransac_inl%`.  This package has no robust relative-pose estimator of its own (a five-point RANSAC
+    is the follow-up): without an estimator object this raises NotImplementedError."""
+    if estimator is None:
+        raise NotImplementedError(
+            f"no relative-pose estimator {conf.get('estimator')!r} here: the five-point RANSAC estimator is not built "
+            "(the reference delegates it to OpenCV / PoseLib / pycolmap); pass an estimator object")
+    batched, kp0, kp1, m0 = _pose_inputs(data, pred, need_depth=False)
+    if batched:
+        raise ValueError("eval_relative_pose_robust takes one pair (un-batched key points), as the reference")
+    sel = m0[0] > -1
+    cam0, cam1 = data["view0"]["camera"], data["view1"]["camera"]
+    est = estimator({"m_kpts0": kp0[0][sel], "m_kpts1": kp1[0][m0[0][sel]],
+                     "camera0": cam0[0] if cam0._data.ndim > 1 else cam0,
+                     "camera1": cam1[0] if cam1._data.ndim > 1 else cam1})
+    if not est["success"]:
+        return {"rel_pose_error": float("inf"), "ransac_inl": 0, "ransac_inl%": 0}
+    M = est["M_0to1"]
+    inl = np.asarray(torch.as_tensor(est["inliers"]).cpu())
+    flat = M._data.reshape(-1)
+    t_err, r_err = relative_pose_error(data["T_0to1"], flat[:9].reshape(3, 3), flat[9:])
+    return {"rel_pose_error": float(max(r_err, t_err)), "ransac_inl": float(np.sum(inl)),
+            "ransac_inl%": 0 if inl.size == 0 else float(np.mean(inl))}
+
+
+def eval_poses(pose_results, auc_ths, key, unit="°"):
+    """gluefactory.eval.utils.eval_poses (eval/utils.py:305-331): {threshold: {key: per-pair list, ...}} ->
+    (summaries, best threshold).  The threshold reported is the one with the highest mean AUC of `key` (the first on
+    a tie); summaries hold `<key>@<t><unit>`, `<key>_mAA` and med_ / mean_ of its numeric lists."""
+    from .eval_hpatches import cal_error_auc
+
+    aucs = {th: cal_error_auc(lists[key], list(auc_ths)) for th, lists in pose_results.items()}
+    maas = {th: float(np.mean(a)) for th, a in aucs.items()}
+    best_th = max(maas, key=maas.get)
+    summaries = {f"{key}@{t}{unit}": float(a) for t, a in zip(auc_ths, aucs[best_th])}
+    summaries[f"{key}_mAA"] = maas[best_th]
+    for k, v in pose_results[best_th].items():
+        arr = np.array(v)
+        if np.issubdtype(arr.dtype, np.number):
+            summaries[f"med_{k}"] = round(float(np.median(arr)), 3)
+            summaries[f"mean_{k}"] = round(float(np.mean(arr)), 3)
+    return summaries, best_th

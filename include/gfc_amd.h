@@ -631,6 +631,53 @@ int gfc_eval_homography_ransac(const float* kp0, const float* kp1, const int64_t
                                int32_t* best_hypothesis, double* H_minimal, float* err_out, void* ws, size_t ws_bytes,
                                void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Pose / depth evaluation (csrc/eval_pose.hip): what the reference's pose benchmarks score matches with.
+ * One workgroup per pair, no workspace, no allocation, no synchronisation; everything per pair lives in LDS.
+ *
+ * A camera is float[10] per pair = w, h, fx, fy, cx, cy, d0..d3 (unused coefficients are ignored); `model` is one of
+ * the GFC_CAM_* values below and is shared by all pairs of a call, as a stacked reference Camera shares its model.
+ * PINHOLE: no coefficient; RADIAL: k1 k2; OPENCV: k1 k2 p1 p2; OPENCV_FISHEYE: k1..k4 of the Kannala-Brandt model.
+ * A pose is float[12] per pair = R row-major, then t (x_j = R x_i + t).  Pixel centres are at +0.5.  The arrays of an
+ * empty side (K, M or N of 0) may be NULL; any other NULL required pointer is GFC_ERR_INVALID.  The arithmetic is
+ * fp32 in the reference's operation order (Camera.image2cam / cam2image, gluefactory/geometry/wrappers.py:407-481 with
+ * geometry/utils.py:92-248; sample_depth / project, geometry/depth.py:8-59).
+ * ---------------------------------------------------------------------------------- */
+enum { GFC_CAM_PINHOLE = 0, GFC_CAM_RADIAL = 1, GFC_CAM_OPENCV = 2, GFC_CAM_OPENCV_FISHEYE = 3 };
+
+/* sample_depth + project(ccth=None) for the key points of view i: kp [B,K,2], depth_i [B,Hi,Wi] (<= 0 = hole) ->
+ * depth_kp [B,K] (NaN where the bilinear and the nearest sample are holes, 0 where the nearest falls outside),
+ * valid [B,K] uint8 (finite and > 0), proj [B,K,2] the pixels in view j, visible [B,K] uint8 (valid, in front of
+ * camera j, inside its distortion model's range and inside its image: 0 <= p <= size - 1).  What
+ * gt_matches_from_pose_depth returns as depth_keypoints*, proj_*, visible*. */
+int gfc_eval_pose_project(const float* kp, const float* depth_i, const float* cam_i, int model_i, const float* cam_j,
+                          int model_j, const float* T_itoj, int B, int K, int Hi, int Wi, float* depth_kp,
+                          uint8_t* valid, float* proj, uint8_t* visible, void* stream);
+
+/* eval_matches_depth (gluefactory/eval/utils.py:77-138): kp0 [B,M,2], kp1 [B,N,2], matches0 [B,M] int64 (-1 =
+ * unmatched), depth0 [B,H0,W0], depth1 [B,H1,W1], T_1to0 the inverse of T_0to1 (computed by the caller, as Hinv of
+ * gfc_eval_matches_homography).  out [B,7] = reproj_prec@1px, @3px, @5px (symmetric reprojection error
+ * 0.5 (|p01 - p1| + |p10 - p0|) over the matches whose two points have valid depth, NaN counted as +inf), covisible
+ * (their number), covisible_percent (of all matches), gt_match_recall, gt_match_precision against the ground-truth
+ * matches of gt_matches_from_pose_depth (geometry/gt_generation.py:594-727, epi_th = cc_th = None; the evaluation
+ * calls it with pos_th 3, neg_th 5): dist = max(d0, d1), +inf outside visible0 x visible1; mutual argmin (first index
+ * on ties) and dist < pos_th^2 is a match; -1 where the UNMASKED min of d0 (d1 for view 1) exceeds neg_th^2 and the
+ * point's depth is valid; -2 otherwise.  Means over an empty set are 0.  gt_matches0 [B,M] / gt_matches1 [B,N] int64,
+ * each nullable.  M == 0 or N == 0: all -1.  The M x N matrix is never materialised.  GFC_ERR_UNSUPPORTED (nothing
+ * launched) when the pair does not fit in 160 KB of LDS: (6 M + 7 N) * 4 + 64 bytes. */
+int gfc_eval_matches_depth(const float* kp0, const float* kp1, const int64_t* matches0, const float* depth0,
+                           const float* depth1, const float* cam0, int model0, const float* cam1, int model1,
+                           const float* T_0to1, const float* T_1to0, int B, int M, int N, int H0, int W0, int H1, int W1,
+                           float pos_th, float neg_th, float* out, int64_t* gt_matches0, int64_t* gt_matches1,
+                           void* stream);
+
+/* eval_matches_epipolar (gluefactory/eval/utils.py:45-74): out [B,5] = epi_prec@1e-4, @5e-4, @1e-3, num_matches,
+ * num_keypoints = (M + N) / 2.  The error of a match is sym_epipolar_distance(squared=False) (geometry/epipolar.py:32-56,
+ * both squared norms clamped at 1e-6) of its image2cam points under E = [t]x R. */
+int gfc_eval_matches_epipolar(const float* kp0, const float* kp1, const int64_t* matches0, const float* cam0, int model0,
+                              const float* cam1, int model1, const float* T_0to1, int B, int M, int N, float* out,
+                              void* stream);
+
 /* Image preprocessing ("next" row rank 1): [uint8 -> float /255 ->] antialiased bilinear resize, fused.
  * src: src_is_u8_hwc != 0: B interleaved HxWxC byte images (bgr != 0 reverses the channel order, as read_image does
  * after cv2.imread, utils/image.py:135-145), converted like numpy_image_to_torch (image.py:148-156); else B planar
