@@ -142,6 +142,11 @@ SIGNATURES = {
     "gfc_eval_homography_ransac_workspace_bytes": (c_size_t, [c_int] * 4),
     "gfc_eval_homography_ransac": (c_int, [c_void_p] * 6 + [c_int] * 3 + [POINTER(c_float)] + [c_int] * 3
                                    + [ctypes.c_uint64] + [c_void_p] * 8 + [c_size_t, c_void_p]),
+    "gfc_eval_pose_image2cam": (c_int, [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p, c_void_p]),
+    "gfc_eval_relative_pose_ransac_workspace_bytes": (c_size_t, [c_int] * 4),
+    "gfc_eval_relative_pose_ransac": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int, c_void_p] + [c_int] * 3
+                                      + [POINTER(c_float)] + [c_int] * 3 + [ctypes.c_uint64, ctypes.c_double]
+                                      + [c_void_p] * 12 + [c_size_t, c_void_p]),
     "gfc_eval_pose_project": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p] * 5),
     "gfc_eval_matches_depth": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 7
                                + [c_float] * 2 + [c_void_p] * 4),

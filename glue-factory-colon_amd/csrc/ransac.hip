@@ -14,41 +14,17 @@
 //                          up to lo_iters rounds of {inliers -> DLT -> accept iff the MSAC score drops}, outputs.
 // A hypothesis's score is one lane's serial sum and the winner is chosen by (score, h): the result does not depend on
 // the number of ranges, the batch or the launch shape.
-#include "eval_common.h"
+#include "ransac_common.h"
 
-#define RS_MAX_T 8
-#define RS_LDS_CORR_BYTES (128 * 1024)
 #define RS_DET_EPS 1e-10
 
 struct rs_thresholds { double t2[RS_MAX_T]; };
 
-// ---- sampler: splitmix64 finaliser as a counter-based generator ---------------------------------------------
-__device__ __host__ __forceinline__ unsigned long long rs_mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__device__ __host__ __forceinline__ unsigned long long rs_key(unsigned long long seed, unsigned long long stream) {
-  return rs_mix64(rs_mix64(seed + 0x9E3779B97F4A7C15ull) ^ stream);
-}
-// 4 distinct indices in [0, n), n >= 4: partial Fisher-Yates over a virtual array a[p] = p ("take a[r], move the last
-// live element into the hole"), draws r_j in [0, n - j) by multiply-high of the upper 32 bits.
+// 4 distinct indices in [0, n), n >= 4: rs_sample_k<4> of ransac_common.h
 __device__ __forceinline__ void rs_sample(unsigned long long key, int h, int n, int& i0, int& i1, int& i2, int& i3) {
-  const unsigned long long base = 4ull * (unsigned long long)h;
-  const int r0 = (int)(((rs_mix64(key + 0x9E3779B97F4A7C15ull * (base + 1)) >> 32) * (unsigned long long)n) >> 32);
-  const int r1 = (int)(((rs_mix64(key + 0x9E3779B97F4A7C15ull * (base + 2)) >> 32) * (unsigned long long)(n - 1)) >> 32);
-  const int r2 = (int)(((rs_mix64(key + 0x9E3779B97F4A7C15ull * (base + 3)) >> 32) * (unsigned long long)(n - 2)) >> 32);
-  const int r3 = (int)(((rs_mix64(key + 0x9E3779B97F4A7C15ull * (base + 4)) >> 32) * (unsigned long long)(n - 3)) >> 32);
-  i0 = r0;
-  const int p0 = r0, v0 = n - 1;  // a[r0] <- a[n-1]
-  i1 = (r1 == p0) ? v0 : r1;
-  const int l1 = n - 2;
-  const int p1 = r1, v1 = (l1 == p0) ? v0 : l1;  // a[r1] <- a[n-2]
-  i2 = (r2 == p1) ? v1 : (r2 == p0) ? v0 : r2;
-  const int l2 = n - 3;
-  const int p2 = r2, v2 = (l2 == p1) ? v1 : (l2 == p0) ? v0 : l2;  // a[r2] <- a[n-3]
-  i3 = (r3 == p2) ? v2 : (r3 == p1) ? v1 : (r3 == p0) ? v0 : r3;
+  int idx[4];
+  rs_sample_k<4>(key, h, n, idx);
+  i0 = idx[0]; i1 = idx[1]; i2 = idx[2]; i3 = idx[3];
 }
 
 // ---- minimal solve ---------------------------------------------------------------------------------------

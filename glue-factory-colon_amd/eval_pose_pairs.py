@@ -1,16 +1,17 @@
 """Pose / depth evaluation of cached predictions on the GPU path -- counterpart of the `run_eval` of the reference's
 posed-pair benchmarks (gluefactory/eval/endomapper_dense1500.py:102-183; megadepth1500, scannet1500 and eth3d share its
-shape): per pair the match counts, `eval_matches_epipolar`, `eval_matches_depth` when the item carries depth, and --
-given a relative-pose estimator object -- `eval_relative_pose_robust` per RANSAC threshold with the pose AUCs at the
-best one.
+shape): per pair the match counts, `eval_matches_epipolar`, `eval_matches_depth` when the item carries depth, and the robust
+relative pose per RANSAC threshold with the pose AUCs at the best one: through `eval_relative_pose_robust` given an
+estimator object, or -- `eval_conf = {"estimator": "gfc_amd", ...}` and no object -- through ONE call of the GPU
+five-point RANSAC (`eval_utils.relative_pose_ransac`) per group of pairs for all thresholds.
 
 `items` is any iterable of the reference's data dicts, one pair each (`name`, `T_0to1`, `view0/1` = {`camera`
 [, `depth`]}, cameras and poses as geometry.Camera / Pose or the reference's wrappers).  The reference walks them pair
 by pair; here consecutive items of equal shapes (key-point counts, depth-map sizes, camera models) go through ONE call
 of each kernel (one workgroup per pair either way: the numbers do not depend on the grouping).
 
-What is NOT here: the `posed_images` directory reader (tied to the fork's scene-info files and crops), a robust
-relative-pose estimator (five-point RANSAC; the reference delegates it to OpenCV / PoseLib / pycolmap) and figures.
+What is NOT here: the `posed_images` directory reader (tied to the fork's scene-info files and crops) and figures.
+Parity of the GPU estimator with OpenCV / PoseLib / pycolmap (what the reference delegates to) is unpinned.
 """
 from collections import defaultdict
 
@@ -50,8 +51,8 @@ class PosePairsPipeline:
             return [float(t) for t in th]
         return [float(th)] if float(th) > 0 else [0.5, 1.0, 1.5, 2.0, 2.5, 3.0]
 
-    def _flush(self, group, device, out):
-        datas, preds = zip(*group)
+    def _flush(self, group, device, out, pose_out=None):
+        datas, preds = zip(*[g[:2] for g in group])
 
         def stack(key, dtype):
             return torch.stack([p[key] for p in preds]).to(device=device, dtype=dtype)
@@ -72,6 +73,32 @@ class PosePairsPipeline:
             if dep is not None:
                 row.update({key: float(dep[j, c]) for c, key in enumerate(eval_utils.DEPTH_RESULT_KEYS)})
             out.append(row)
+        if pose_out is not None:
+            self._pose_rows(group, kp0, kp1, m0, cam0, cam1, pose_out)
+
+    def _pose_rows(self, group, kp0, kp1, m0, cam0, cam1, pose_out):
+        """One estimator call for the whole group and all thresholds; stream_id = the pair's position in `items`.
+        Matches are counted as `matches0 > -1`, as `eval_relative_pose_robust` and the reference select them; the
+        kernel additionally wants `matches0 < N`, which every valid prediction satisfies."""
+        ths = self.thresholds()
+        conf = self.eval_conf
+        res = eval_utils.relative_pose_ransac(
+            kp0, kp1, m0, cam0, cam1, ths, num_hypotheses=conf.get("num_hypotheses", 2048),
+            lo_iters=conf.get("lo_iters", 3), seed=conf.get("seed", 0), stream_id=[g[2] for g in group])
+        R, t, succ, ninl = res["R"].cpu(), res["t"].cpu(), res["success"].cpu(), res["num_inliers"].cpu()
+        n_matches = (m0 > -1).sum(1).cpu().tolist()
+        for j, (data, _, _) in enumerate(group):
+            for q, th in enumerate(ths):
+                if n_matches[j] < MIN_MATCHES_FOR_POSE:
+                    row = {k: float("nan") for k in eval_utils.POSE_RESULT_KEYS}
+                elif not bool(succ[j, q]):
+                    row = {"rel_pose_error": float("inf"), "ransac_inl": 0, "ransac_inl%": 0}
+                else:
+                    t_err, r_err = eval_utils.relative_pose_error(data["T_0to1"], R[j, q], t[j, q])
+                    row = {"rel_pose_error": float(max(r_err, t_err)), "ransac_inl": float(ninl[j, q]),
+                           "ransac_inl%": float(ninl[j, q]) / n_matches[j]}
+                for k, v in row.items():
+                    pose_out[th][k].append(v)
 
     @staticmethod
     def _shape_key(data, pred):
@@ -81,8 +108,13 @@ class PosePairsPipeline:
 
     def run_eval(self, items, pred_file, estimator=None, device="cuda"):
         """-> (summaries, results): per-pair lists under the reference's keys, `med_*` / `mean_*` of every numeric
-        one; with an estimator also `rel_pose_error@{5,10,20}°`, `rel_pose_error_mAA` and the per-pair pose lists at
-        the best threshold (every tested threshold under results["pose_results"])."""
+        one; with an estimator (an object, or eval_conf["estimator"] = "gfc_amd") also `rel_pose_error@{5,10,20}°`,
+        `rel_pose_error_mAA` and the per-pair pose lists at the best threshold (every tested threshold under
+        results["pose_results"]).  An eval_conf["estimator"] name this package does not have, with no estimator
+        object, raises NotImplementedError (no pose would be computed)."""
+        named = estimator is None and self.eval_conf["estimator"] is not None
+        if named and self.eval_conf["estimator"] not in eval_utils.RELATIVE_POSE_ESTIMATORS:
+            eval_utils.relative_pose_estimator_from_conf(self.eval_conf)  # raises: no such estimator here
         cache = CacheLoader({"path": str(pred_file), "collate": None, "add_data_path": False}).eval()
         rows, extras, names = [], [], []
         pose_results = defaultdict(lambda: defaultdict(list))
@@ -93,10 +125,10 @@ class PosePairsPipeline:
                           "view1": {"scales": data["view1"].get("scales", torch.ones(1, 2))}})
             k = self._shape_key(data, pred)
             if group and (k != key or len(group) >= self.max_group):
-                self._flush(group, device, rows)
+                self._flush(group, device, rows, pose_results if named else None)
                 group = []
             key = k
-            group.append((data, pred))
+            group.append((data, pred, len(names)))
             names.append(name)
             extras.append({q: pred[q].item() for q in (*TIMING_KEYS, *MEMORY_KEYS, *CONTEXT_KEYS) if q in pred})
             if estimator is not None:
@@ -110,14 +142,14 @@ class PosePairsPipeline:
                     for q, v in res.items():
                         pose_results[th][q].append(v)
         if group:
-            self._flush(group, device, rows)
+            self._flush(group, device, rows, pose_results if named else None)
         results = defaultdict(list)
         for row, extra, name in zip(rows, extras, names):
             for q, v in {**row, **extra, "names": name}.items():
                 results[q].append(v)
         summaries = med_mean_summaries(results)
         results = dict(results)
-        if estimator is not None and pose_results:
+        if (estimator is not None or named) and pose_results:
             pose_results = {th: dict(r) for th, r in pose_results.items()}
             pose_summaries, best_th = eval_utils.eval_poses(pose_results, auc_ths=[5, 10, 20], key="rel_pose_error")
             results = {**results, **pose_results[best_th], "pose_results": pose_results}

@@ -110,33 +110,35 @@ def _mix64(z):
     return z ^ (z >> np.uint64(31))
 
 
-def ransac_sample_indices(seed, stream_id, n, num_hypotheses):
-    """The minimal samples of the GPU estimator, index for index (csrc/ransac.hip: rs_sample; DESIGN.md "Robust
-    homography"): int64 [num_hypotheses, 4], four distinct indices in [0, n) per hypothesis.  Pure integer arithmetic:
-    draw j of hypothesis h is u = mix64(key + GOLDEN * (4 h + j + 1)), key = mix64(mix64(seed + GOLDEN) ^ stream_id),
+def ransac_sample_indices(seed, stream_id, n, num_hypotheses, sample_size=4):
+    """The minimal samples of the GPU estimators, index for index (csrc/ransac_common.h: rs_sample_k; DESIGN.md "Robust
+    homography"): int64 [num_hypotheses, sample_size], distinct indices in [0, n) per hypothesis; sample_size 4 for the
+    homography estimator, 5 for the relative-pose one.  Pure integer arithmetic: draw j of hypothesis h is
+    u = mix64(key + GOLDEN * (sample_size h + j + 1)), key = mix64(mix64(seed + GOLDEN) ^ stream_id),
     r_j = ((u >> 32) * (n - j)) >> 32, and the r_j index a partial Fisher-Yates over the virtual array a[p] = p
     (take a[r_j], then move the last live element a[n - 1 - j] into the hole)."""
-    n = int(n)
-    if n < 4:
-        raise ValueError("a minimal sample needs n >= 4 correspondences")
+    n, k = int(n), int(sample_size)
+    if k < 1:
+        raise ValueError("sample_size >= 1")
+    if n < k:
+        raise ValueError(f"a minimal sample needs n >= {k} correspondences")
     with np.errstate(over="ignore"):
         key = _mix64(_mix64(np.uint64((int(seed) + _GOLDEN) & _M64)) ^ np.uint64(int(stream_id) & _M64))
         h = np.arange(int(num_hypotheses), dtype=np.uint64)
         r = []
-        for j in range(4):
-            u = _mix64(key + np.uint64(_GOLDEN) * (np.uint64(4) * h + np.uint64(j + 1)))
+        for j in range(k):
+            u = _mix64(key + np.uint64(_GOLDEN) * (np.uint64(k) * h + np.uint64(j + 1)))
             r.append((((u >> np.uint64(32)) * np.uint64(n - j)) >> np.uint64(32)).astype(np.int64))
-    r0, r1, r2, r3 = r
-    i0 = r0
-    p0, v0 = r0, n - 1
-    i1 = np.where(r1 == p0, v0, r1)
-    l1 = n - 2
-    p1, v1 = r1, np.where(l1 == p0, v0, l1)
-    i2 = np.where(r2 == p1, v1, np.where(r2 == p0, v0, r2))
-    l2 = n - 3
-    p2, v2 = r2, np.where(l2 == p1, v1, np.where(l2 == p0, v0, l2))
-    i3 = np.where(r3 == p2, v2, np.where(r3 == p1, v1, np.where(r3 == p0, v0, r3)))
-    return np.stack([i0, i1, i2, i3], axis=1).astype(np.int64)
+    holes, vals, out = [], [], []  # hole positions p_q and what was moved into them v_q, looked up latest first
+    for j in range(k):
+        idx, val = r[j], np.full_like(r[j], n - 1 - j)
+        for p, v in zip(holes, vals):  # oldest first: a later hole overrides
+            idx = np.where(r[j] == p, v, idx)
+            val = np.where((n - 1 - j) == p, v, val)
+        out.append(idx)
+        holes.append(r[j])
+        vals.append(val)
+    return np.stack(out, axis=1).astype(np.int64)
 
 
 def ransac_thresholds(ransac_th):
@@ -407,16 +409,108 @@ def relative_pose_error(T_0to1, R, t, ignore_gt_t_thr=0.0):
     return t_err, r_err
 
 
-def eval_relative_pose_robust(data: dict, pred: dict, conf: dict, estimator=None) -> dict:
-    """gluefactory.eval.utils.eval_relative_pose_robust (eval/utils.py:188-222) around an estimator OBJECT of the
-    reference's interface: estimator({"m_kpts0", "m_kpts1", "camera0", "camera1"}) -> {"success", "M_0to1" (a pose
-    holder), "inliers"}.  Returns `rel_pose_error` (the larger of the rotation and translation angles, degrees),
-    `ransac_inl`, `ransac_inl%`.  This package has no robust relative-pose estimator of its own (a five-point RANSAC
-    is the follow-up): without an estimator object this raises NotImplementedError."""
-    if estimator is None:
+RELATIVE_POSE_ESTIMATORS = ("gfc_amd",)
+_relpose_ws = nat.Workspace()
+
+
+def pose_image2cam(kp, camera):
+    """`Camera.image2cam` of the reference for batched device key points kp [B,K,2] (pixels) and a holder of B cameras
+    -> [B,K,2] float32 points on the z = 1 plane (only OPENCV_FISHEYE removes its distortion): the bearings the
+    relative-pose estimator works on, from the same device function."""
+    from . import geometry
+
+    nat.require_cuda(kp, "keypoints")
+    dev, (b, k) = kp.device, kp.shape[:2]
+    cam, model = geometry.camera_args(camera, b, dev)
+    pts = kp.float().contiguous()
+    out = torch.empty((b, k, 2), device=dev, dtype=torch.float32)
+    nat.check(nat.lib().gfc_eval_pose_image2cam(nat.ptr(pts), nat.ptr(cam), model, b, k, nat.ptr(out), nat.stream_ptr(dev)),
+              "gfc_eval_pose_image2cam")
+    return out
+
+
+def relative_pose_ransac(kp0, kp1, matches0, camera0, camera1, ransac_th, T_0to1=None, *, num_hypotheses=2048,
+                         lo_iters=3, seed=0, stream_id=None, ignore_gt_t_thr=0.0):
+    """Five-point RANSAC relative pose for B pairs x T thresholds in one call of `gfc_eval_relative_pose_ransac`
+    (csrc/relpose.hip; DESIGN.md "Robust relative pose").  Batched device tensors: kp0 [B,M,2], kp1 [B,N,2] in pixels,
+    matches0 [B,M]; cameras (and the optional true pose T_0to1) as holders of B items (geometry.Camera / Pose or the
+    reference's wrappers); ransac_th in pixels, a float or a sequence of at most 8 (a pair uses th / mean(fx0, fy0, fx1,
+    fy1)); stream_id None (0..B-1), an int or [B] ints: the random stream of each pair.  Returns a dict of device
+    tensors: R [B,T,3,3], t [B,T,3] (unit), E [B,T,3,3] = [t]x R, E_minimal [B,T,3,3] float64; inliers [B,T,M] bool
+    (key-point-0 indexing); num_inliers, best_hypothesis, best_solution [B,T] int32; success [B,T] bool; thresholds [T];
+    with T_0to1 also r_err, t_err [B,T] float64 degrees (t up to sign).  Convention X1 = R X0 + t."""
+    from . import geometry
+
+    nat.require_cuda(kp0, "keypoints0")
+    nat.require_cuda(kp1, "keypoints1")
+    nat.require_cuda(matches0, "matches0")
+    lib = nat.lib()
+    dev = kp0.device
+    b, m, n = kp0.shape[0], kp0.shape[1], kp1.shape[1]
+    ths = [float(t) for t in ransac_th] if isinstance(ransac_th, (list, tuple, np.ndarray, torch.Tensor)) else [float(ransac_th)]
+    t = len(ths)
+    cam0, model0 = geometry.camera_args(camera0, b, dev)
+    cam1, model1 = geometry.camera_args(camera1, b, dev)
+    k0, k1 = kp0.float().contiguous(), kp1.float().contiguous()
+    m0 = matches0.to(torch.long).contiguous()
+    if stream_id is None:
+        sid = None
+    elif isinstance(stream_id, torch.Tensor):
+        sid = stream_id.to(device=dev, dtype=torch.long).reshape(b).contiguous()
+    else:
+        sid = torch.as_tensor(np.broadcast_to(np.asarray(stream_id, dtype=np.int64), (b,)).copy(), device=dev)
+    T01 = rerr = terr = None
+    if T_0to1 is not None:
+        T01, _ = geometry.pose_args(T_0to1, b, dev)
+        rerr = torch.empty((b, t), device=dev, dtype=torch.float64)
+        terr = torch.empty((b, t), device=dev, dtype=torch.float64)
+    f64 = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float64)
+    i32 = lambda: torch.empty((b, t), device=dev, dtype=torch.int32)
+    R, tv, E, Emin = f64(b, t, 3, 3), f64(b, t, 3), f64(b, t, 3, 3), f64(b, t, 3, 3)
+    inl = torch.empty((b, t, m), device=dev, dtype=torch.uint8)
+    succ = torch.empty((b, t), device=dev, dtype=torch.uint8)
+    ninl, besth, bestk = i32(), i32(), i32()
+    th_host = (ctypes.c_float * max(t, 1))(*ths)
+    nbytes = lib.gfc_eval_relative_pose_ransac_workspace_bytes(b, m, t, int(num_hypotheses))
+    ws = _relpose_ws.get(max(nbytes, 256), dev)
+    nat.check(lib.gfc_eval_relative_pose_ransac(
+        nat.ptr(k0), nat.ptr(k1), nat.ptr(m0), nat.ptr(sid), nat.ptr(cam0), model0, nat.ptr(cam1), model1, nat.ptr(T01),
+        b, m, n, th_host, t, int(num_hypotheses), int(lo_iters), int(seed) & _M64, float(ignore_gt_t_thr), nat.ptr(R),
+        nat.ptr(tv), nat.ptr(E), nat.ptr(Emin), nat.ptr(inl), nat.ptr(ninl), nat.ptr(succ), nat.ptr(besth),
+        nat.ptr(bestk), nat.ptr(rerr), nat.ptr(terr), nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)),
+        "gfc_eval_relative_pose_ransac")
+    out = {"R": R, "t": tv, "E": E, "E_minimal": Emin, "inliers": inl.bool(), "num_inliers": ninl,
+           "success": succ.bool(), "best_hypothesis": besth, "best_solution": bestk,
+           "thresholds": torch.tensor(ths, dtype=torch.float32, device=dev)}
+    if rerr is not None:
+        out["r_err"], out["t_err"] = rerr, terr
+    return out
+
+
+def relative_pose_estimator_from_conf(conf):
+    """The estimator object a conf names: {"estimator": "gfc_amd", "ransac_th": th [, num_hypotheses, lo_iters, seed,
+    stream_id]} -> relative_pose_estimator.GpuRelativePoseEstimator.  Any other name: NotImplementedError."""
+    name = conf.get("estimator")
+    if name not in RELATIVE_POSE_ESTIMATORS:
         raise NotImplementedError(
-            f"no relative-pose estimator {conf.get('estimator')!r} here: the five-point RANSAC estimator is not built "
-            "(the reference delegates it to OpenCV / PoseLib / pycolmap); pass an estimator object")
+            f"no relative-pose estimator {name!r} here: the five-point RANSAC estimator of this package is 'gfc_amd' "
+            "(the reference delegates to OpenCV / PoseLib / pycolmap, CPU libraries this package does not use); "
+            "pass an estimator object")
+    from .relative_pose_estimator import GpuRelativePoseEstimator
+
+    options = {k: conf[k] for k in ("num_hypotheses", "lo_iters", "seed", "stream_id") if conf.get(k) is not None}
+    return GpuRelativePoseEstimator({"ransac_th": float(conf["ransac_th"]), "options": options})
+
+
+def eval_relative_pose_robust(data: dict, pred: dict, conf: dict, estimator=None) -> dict:
+    """gluefactory.eval.utils.eval_relative_pose_robust (eval/utils.py:188-222): `rel_pose_error` (the larger of the
+    rotation and translation angles, degrees), `ransac_inl`, `ransac_inl%` of one pair.  The estimator is an OBJECT of
+    the reference's interface -- estimator({"m_kpts0", "m_kpts1", "camera0", "camera1"}) -> {"success", "M_0to1" (a
+    pose holder), "inliers"} -- or, without one, what conf names: {"estimator": "gfc_amd", "ransac_th": th} is this
+    package's GPU five-point RANSAC (relative_pose_estimator.GpuRelativePoseEstimator); any other name raises
+    NotImplementedError."""
+    if estimator is None:
+        estimator = relative_pose_estimator_from_conf(conf)
     batched, kp0, kp1, m0 = _pose_inputs(data, pred, need_depth=False)
     if batched:
         raise ValueError("eval_relative_pose_robust takes one pair (un-batched key points), as the reference")

@@ -247,3 +247,83 @@ def posed_plane_pairs(n: int, h: int = 96, w: int = 128, seed: int = 0, model: s
                       "matching_scores0": torch.from_numpy((m0 > -1).astype(np.float32)),
                       "matching_scores1": torch.from_numpy((m1 > -1).astype(np.float32))})
     return items, preds
+
+
+POSED_RELIEF_NOISE_PX = (0.0, 0.1, 0.2, 0.1)
+
+
+def posed_relief_pairs(n: int, h: int = 96, w: int = 128, seed: int = 0, model: str = "PINHOLE", num_keypoints=(257, 130),
+                       off_plane_share: float = 0.3):
+    """`n` analytic posed pairs for the robust relative-pose estimator: a dominant tilted plane plus `off_plane_share`
+    of the planted points at other depths (0.5 to 1.5 times the plane's depth along their ray).  A purely planar scene
+    (`posed_plane_pairs`) leaves the relative pose two-fold ambiguous for any estimator; the relief removes that.  No
+    depth maps.  Key points and matches as in `posed_plane_pairs`: about 70 % of the smaller view's points are planted
+    correspondences (the exact image in view 1 through pose and camera model, displaced by 0, 0.1, 0.2 or 0.1 px in
+    turn), the rest unrelated points; view 1's points are shuffled; every tenth planted match points at a wrong
+    partner and every unrelated seventh point is matched at random.
+
+    Returns (items, preds) in the layout of `posed_plane_pairs`, `view0/1` = {`camera`} only.  Seeded, CPU."""
+    import numpy as np
+
+    from .geometry import Camera, Pose
+
+    rng = np.random.default_rng([seed, 31])
+    M, N = num_keypoints
+    coeffs = tuple(POSED_CAMERA_COEFFS[model])
+    items, preds = [], []
+    for i in range(n):
+        cams = []
+        for _ in range(2):
+            f = (0.55 if model == "OPENCV_FISHEYE" else 0.8) * w * rng.uniform(0.95, 1.05)
+            cams.append(np.array([w, h, f, f * rng.uniform(0.98, 1.02), w / 2 + rng.uniform(-2, 2), h / 2 + rng.uniform(-2, 2),
+                                  *coeffs] + [0.0] * (4 - len(coeffs))))
+        normal = np.array([rng.uniform(-0.25, 0.25), rng.uniform(-0.25, 0.25), 1.0])
+        normal /= np.linalg.norm(normal)
+        dist = rng.uniform(2.0, 3.0)
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        ang = np.deg2rad(rng.uniform(2.0, 6.0))
+        Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        R = np.eye(3) + np.sin(ang) * Kx + (1 - np.cos(ang)) * Kx @ Kx
+        t = np.array([rng.uniform(0.1, 0.3) * rng.choice([-1, 1]), rng.uniform(-0.1, 0.1), rng.uniform(-0.08, -0.02)])
+        n_plant = int(0.7 * min(M, N))
+        kp0 = np.stack([rng.uniform(1.0, w - 1.0, 4 * M), rng.uniform(1.0, h - 1.0, 4 * M)], -1)
+        ray = posed_pixel_to_ray(cams[0], model, kp0)
+        depth = dist / (ray @ normal)
+        off = rng.uniform(0, 1, 4 * M) < off_plane_share
+        depth = np.where(off, depth * rng.uniform(0.5, 1.5, 4 * M), depth)
+        X1 = (ray * depth[:, None]) @ R.T + t
+        img = posed_point_to_pixel(cams[1], model, X1)
+        ok = (img[:, 0] > 9) & (img[:, 0] < w - 10) & (img[:, 1] > 9) & (img[:, 1] < h - 10) & (X1[:, 2] > 0.1)
+        keep = np.nonzero(ok)[0][:n_plant]
+        n_plant = len(keep)
+        phi = rng.uniform(0, 2 * np.pi, n_plant)
+        noise = np.asarray(POSED_RELIEF_NOISE_PX)[np.arange(n_plant) % 4][:, None] * np.stack([np.cos(phi), np.sin(phi)], -1)
+        k0 = np.concatenate([kp0[keep], np.stack([rng.uniform(0.5, w - 0.5, M - n_plant),
+                                                  rng.uniform(0.5, h - 0.5, M - n_plant)], -1)])
+        k1 = np.concatenate([img[keep] + noise, np.stack([rng.uniform(0.5, w - 0.5, N - n_plant),
+                                                          rng.uniform(0.5, h - 0.5, N - n_plant)], -1)])
+        perm = rng.permutation(N)  # k1_shuffled[q] = k1[perm[q]]
+        where = np.argsort(perm)   # planted partner j sits at where[j]
+        m0 = np.full(M, -1, dtype=np.int64)
+        m0[:n_plant] = where[:n_plant]
+        wrong = np.arange(0, n_plant, 10)
+        m0[wrong] = where[(wrong + 3) % max(n_plant, 1)]
+        extra = np.arange(n_plant, M, 7)
+        m0[extra] = rng.integers(0, N, len(extra))
+        _, first = np.unique(m0, return_index=True)  # one-to-one: a later duplicate of a partner becomes unmatched
+        dup = np.ones(M, bool)
+        dup[first] = False
+        m0[dup & (m0 > -1)] = -1
+        m1 = np.full(N, -1, dtype=np.int64)
+        m1[m0[m0 > -1]] = np.nonzero(m0 > -1)[0]
+        T = np.concatenate([R.reshape(9), t])
+        items.append({"name": [f"relief_{model.lower()}_{seed}_{i}"],
+                      "T_0to1": Pose(torch.from_numpy(T[None]).float()),
+                      "view0": {"camera": Camera(torch.from_numpy(cams[0][None]).float(), model=model)},
+                      "view1": {"camera": Camera(torch.from_numpy(cams[1][None]).float(), model=model)}})
+        preds.append({"keypoints0": torch.from_numpy(k0).float(), "keypoints1": torch.from_numpy(k1[perm]).float(),
+                      "matches0": torch.from_numpy(m0), "matches1": torch.from_numpy(m1),
+                      "matching_scores0": torch.from_numpy((m0 > -1).astype(np.float32)),
+                      "matching_scores1": torch.from_numpy((m1 > -1).astype(np.float32))})
+    return items, preds

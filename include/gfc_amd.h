@@ -631,6 +631,34 @@ int gfc_eval_homography_ransac(const float* kp0, const float* kp1, const int64_t
                                int32_t* best_hypothesis, double* H_minimal, float* err_out, void* ws, size_t ws_bytes,
                                void* stream);
 
+/* Robust relative pose from the predicted matches: five-point RANSAC, MSAC-scored with the squared Sampson distance at
+ * T thresholds in one pass, cheirality vote, Gauss-Newton local optimisation (DESIGN.md "Robust relative pose"; the
+ * estimator behind eval_relative_pose_robust, gluefactory/eval/utils.py:188-222 -- there OpenCV / PoseLib / pycolmap:
+ * parity with them is unpinned).  kp0 [B,M,2], kp1 [B,N,2] in pixels, m0 [B,M] int64 (a match is 0 <= m0[i] < N),
+ * stream_id [B] int64 (nullable: 0..B-1) the random stream of a pair, cam0 / cam1 [B,10] and model0 / model1 as in the
+ * pose / depth evaluation below (points go through image2cam: only OPENCV_FISHEYE removes its distortion).  T_gt
+ * [B,12] (R row-major, t; X1 = R X0 + t) is given together with r_err and t_err or all three are NULL.  thresholds: T
+ * values in pixels in HOST memory, 1 <= T <= 8, each positive and finite; a pair uses threshold / mean(fx0, fy0, fx1,
+ * fy1).  Outputs per (pair, threshold): R_out [B,T,9], t_out [B,T,3] (unit), E_out [B,T,9] = [t]x R, E_minimal [B,T,9]
+ * (the winning minimal model, unit Frobenius norm, its largest-magnitude entry positive), all fp64; inliers [B,T,M]
+ * uint8 over key points 0; num_inliers, best_hypothesis (the winning sample), best_solution (which of its <= 10
+ * models) [B,T] int32; success [B,T] uint8; r_err, t_err [B,T] fp64 degrees (t up to sign; t_err 0 when |t_gt| <
+ * ignore_gt_t_thr).  Fewer than 5 matches or no usable sample: success 0, R identity, t, E, E_minimal zero, no
+ * inliers, best_hypothesis and best_solution -1, errors +inf.  GFC_ERR_INVALID (nothing launched): B <= 0 or > 65535,
+ * M < 0, N < 0, T outside 1..8, num_hypotheses <= 0 or >= 2^27, lo_iters < 0, a model outside GFC_CAM_*, a threshold
+ * that is not positive and finite, a negative or NaN ignore_gt_t_thr, a NULL required pointer. */
+size_t gfc_eval_relative_pose_ransac_workspace_bytes(int B, int M, int T, int num_hypotheses);
+/* Camera.image2cam of kp [B,K,2] (pixels) with cam [B,10] and one model: out [B,K,2], the point on the z = 1 plane --
+ * the device function the estimator's records go through (only OPENCV_FISHEYE removes its distortion). */
+int gfc_eval_pose_image2cam(const float* kp, const float* cam, int model, int B, int K, float* out, void* stream);
+int gfc_eval_relative_pose_ransac(const float* kp0, const float* kp1, const int64_t* m0, const int64_t* stream_id,
+                                  const float* cam0, int model0, const float* cam1, int model1, const float* T_gt, int B,
+                                  int M, int N, const float* thresholds, int T, int num_hypotheses, int lo_iters,
+                                  uint64_t seed, double ignore_gt_t_thr, double* R_out, double* t_out, double* E_out,
+                                  double* E_minimal, uint8_t* inliers, int32_t* num_inliers, uint8_t* success,
+                                  int32_t* best_hypothesis, int32_t* best_solution, double* r_err, double* t_err,
+                                  void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Pose / depth evaluation (csrc/eval_pose.hip): what the reference's pose benchmarks score matches with.
  * One workgroup per pair, no workspace, no allocation, no synchronisation; everything per pair lives in LDS.
