@@ -2,30 +2,19 @@
 // optimisation by the normalised DLT of eval_common.h.  Counterpart of the estimators behind eval_homography_robust
 // (reference gluefactory/eval/utils.py:225-273; there OpenCV / PoseLib on the CPU -- randomised third-party code,
 // parity with them is unpinned).  The algorithm is written down in DESIGN.md ("Robust homography"); a float64
-// restatement of it is tests/ransac_reference.py.
+// restatement of it is tests/ransac_reference.py.  The RANSAC frame -- sampler, ranges, workspace, scoring kernel,
+// reductions, inlier epilogue, argument checks -- is ransac_common.h; this file holds what is the homography's own:
 //
 //   ransac_compact_kernel  one workgroup per pair: the matches (i, m0[i]) with 0 <= m0[i] < N in ascending i
-//                          -> (x0, y0, x1, y1) records + their key-point-0 index + the count n.
-//   ransac_score_kernel<T> one workgroup per (pair, hypothesis range): correspondences staged in LDS, ONE LANE PER
-//                          HYPOTHESIS: counter-based sample -> closed-form 4-point homography (fp64) -> residual of every
-//                          correspondence (all lanes of a wave read the same record: LDS broadcast) feeding T MSAC
-//                          sums in correspondence order -> (score, h) argmin per threshold.
+//                          -> (x0, y0, x1, y1) records + their key-point-0 index + the count n (both estimators' first
+//                          step; declared in ransac_common.h).
+//   rs_homography          the model of the frame: sample of 4 -> closed-form 4-point homography (fp64), one model per
+//                          hypothesis, packed index h, squared forward transfer error, thresholds squared on the host.
 //   ransac_lo_kernel       one workgroup per (pair, threshold): merge the ranges (score, then h), re-solve the winner,
 //                          up to lo_iters rounds of {inliers -> DLT -> accept iff the MSAC score drops}, outputs.
-// A hypothesis's score is one lane's serial sum and the winner is chosen by (score, h): the result does not depend on
-// the number of ranges, the batch or the launch shape.
 #include "ransac_common.h"
 
 #define RS_DET_EPS 1e-10
-
-struct rs_thresholds { double t2[RS_MAX_T]; };
-
-// 4 distinct indices in [0, n), n >= 4: rs_sample_k<4> of ransac_common.h
-__device__ __forceinline__ void rs_sample(unsigned long long key, int h, int n, int& i0, int& i1, int& i2, int& i3) {
-  int idx[4];
-  rs_sample_k<4>(key, h, n, idx);
-  i0 = idx[0]; i1 = idx[1]; i2 = idx[2]; i3 = idx[3];
-}
 
 // ---- minimal solve ---------------------------------------------------------------------------------------
 // twice the signed area of the triangle (a, b, c)
@@ -115,13 +104,30 @@ __device__ __forceinline__ double rs_residual2(const double* H, double x0, doubl
 
 // the four sampled correspondences of hypothesis h -> model
 __device__ __forceinline__ bool rs_hypothesis(const float4* corr, unsigned long long key, int h, int n, double* H) {
-  int i0, i1, i2, i3;
-  rs_sample(key, h, n, i0, i1, i2, i3);
-  const float4 c0 = corr[i0], c1 = corr[i1], c2 = corr[i2], c3 = corr[i3];
+  int i[4];
+  rs_sample_k<4>(key, h, n, i);
+  const float4 c0 = corr[i[0]], c1 = corr[i[1]], c2 = corr[i[2]], c3 = corr[i[3]];
   const double x0[4] = {c0.x, c1.x, c2.x, c3.x}, y0[4] = {c0.y, c1.y, c2.y, c3.y};
   const double x1[4] = {c0.z, c1.z, c2.z, c3.z}, y1[4] = {c0.w, c1.w, c2.w, c3.w};
   return rs_homography_4pt(x0, y0, x1, y1, H);
 }
+
+// the homography as a model of the frame (ransac_common.h); args.th holds the squared thresholds
+struct rs_homography {
+  static constexpr int K = 4, MAX_SOL = 1;
+  struct args { rs_thresholds th; };
+  struct work {};
+  static __device__ __forceinline__ int pack(int h, int) { return h; }
+  static __device__ __forceinline__ double t2(const args& a, int, int t) { return a.th.v[t]; }
+  static __device__ __forceinline__ int solve(const float4* corr, unsigned long long key, int h, int n, work&,
+                                              double* m, bool* ok) {
+    ok[0] = rs_hypothesis(corr, key, h, n, m);
+    return 1;
+  }
+  static __device__ __forceinline__ double residual2(const double* H, double x0, double y0, double x1, double y1) {
+    return rs_residual2(H, x0, y0, x1, y1);
+  }
+};
 
 // ---- kernels -----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(EM_THREADS) void ransac_compact_kernel(const float* __restrict__ kp0,
@@ -160,108 +166,11 @@ __global__ __launch_bounds__(EM_THREADS) void ransac_compact_kernel(const float*
   if (tid == 0) cnt[b] = base;
 }
 
-template <int T>
-__device__ __forceinline__ void rs_score_range(const float4* corr, int n, unsigned long long key, int h_lo, int h_hi,
-                                               const rs_thresholds& th, double* best, int* best_h) {
-#pragma unroll
-  for (int t = 0; t < T; ++t) { best[t] = INFINITY; best_h[t] = 0x7fffffff; }
-  for (int h = h_lo + (int)threadIdx.x; h < h_hi; h += EM_THREADS) {
-    double H[9];
-    const bool ok = rs_hypothesis(corr, key, h, n, H);
-    double acc[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) acc[t] = 0.0;
-    for (int c = 0; c < n; ++c) {
-      const float4 q = corr[c];  // the same address in every lane
-      const double r2 = rs_residual2(H, q.x, q.y, q.z, q.w);
-#pragma unroll
-      for (int t = 0; t < T; ++t) acc[t] += (r2 < th.t2[t]) ? r2 : th.t2[t];
-    }
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-      const double s = ok ? acc[t] : INFINITY;
-      if (s < best[t]) { best[t] = s; best_h[t] = h; }
-    }
-  }
-}
-
-template <int T>
-__global__ __launch_bounds__(EM_THREADS) void ransac_score_kernel(const float4* __restrict__ corr_all,
-                                                                  const int* __restrict__ cnt,
-                                                                  const long long* __restrict__ stream_id,
-                                                                  unsigned long long seed, int M, int S, int NH,
-                                                                  int use_lds, rs_thresholds th,
-                                                                  double* __restrict__ part_score,
-                                                                  int* __restrict__ part_h) {
-  extern __shared__ __attribute__((aligned(16))) float4 lds_corr[];
-  __shared__ double ws[4 * RS_MAX_T];
-  __shared__ int wh[4 * RS_MAX_T];
-  const int b = blockIdx.x / S, s = blockIdx.x % S, tid = threadIdx.x;
-  const int n = cnt[b];
-  const float4* corr = corr_all + (size_t)b * M;
-  double* ps = part_score + (size_t)blockIdx.x * T;
-  int* ph = part_h + (size_t)blockIdx.x * T;
-  if (n < 4) {
-    if (tid < T) { ps[tid] = INFINITY; ph[tid] = -1; }
-    return;
-  }
-  const unsigned long long key = rs_key(seed, stream_id ? (unsigned long long)stream_id[b] : (unsigned long long)b);
-  const int chunk = (NH + S - 1) / S;
-  const int h_lo = s * chunk, h_hi = min(NH, h_lo + chunk);
-  double best[T];
-  int best_h[T];
-  if (use_lds) {
-    for (int c = tid; c < n; c += EM_THREADS) lds_corr[c] = corr[c];
-    __syncthreads();
-    rs_score_range<T>(lds_corr, n, key, h_lo, h_hi, th, best, best_h);
-  } else {
-    rs_score_range<T>(corr, n, key, h_lo, h_hi, th, best, best_h);
-  }
-  // argmin over the block by (score, h)
-#pragma unroll
-  for (int t = 0; t < T; ++t) {
-    double sc = best[t];
-    int hh = best_h[t];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double os = __shfl_xor(sc, o, 64);
-      const int oh = __shfl_xor(hh, o, 64);
-      if (os < sc || (os == sc && oh < hh)) { sc = os; hh = oh; }
-    }
-    if ((tid & 63) == 0) { ws[(tid >> 6) * RS_MAX_T + t] = sc; wh[(tid >> 6) * RS_MAX_T + t] = hh; }
-  }
-  __syncthreads();
-  if (tid < T) {
-    double sc = ws[tid];
-    int hh = wh[tid];
-    for (int w = 1; w < 4; ++w) {
-      const double os = ws[w * RS_MAX_T + tid];
-      const int oh = wh[w * RS_MAX_T + tid];
-      if (os < sc || (os == sc && oh < hh)) { sc = os; hh = oh; }
-    }
-    ps[tid] = sc;
-    ph[tid] = (sc < INFINITY) ? hh : -1;
-  }
-}
-
-// MSAC score of H over the n correspondences, block-wide (thread-strided partial sums, then block_sum_f64)
-__device__ __forceinline__ double rs_block_msac(const double* H, const float4* corr, int n, double t2, double* red,
-                                                int tid) {
-  double v[1] = {0.0};
-  for (int c = tid; c < n; c += EM_THREADS) {
-    const float4 q = corr[c];
-    const double r2 = rs_residual2(H, q.x, q.y, q.z, q.w);
-    v[0] += (r2 < t2) ? r2 : t2;
-  }
-  block_sum_f64<1>(v, red, tid);
-  return v[0];
-}
-
 __global__ __launch_bounds__(EM_THREADS) void ransac_lo_kernel(
     const float4* __restrict__ corr_all, const int* __restrict__ cidx_all, const int* __restrict__ cnt,
     const long long* __restrict__ m0, const long long* __restrict__ stream_id, unsigned long long seed, int M, int N,
     int S, int T, int lo_iters, rs_thresholds th, const double* __restrict__ part_score,
-    const int* __restrict__ part_h, const float* __restrict__ Hgt, const float* __restrict__ size0,
+    const int* __restrict__ part_idx, const float* __restrict__ Hgt, const float* __restrict__ size0,
     double* __restrict__ Hout, unsigned char* __restrict__ inl_out, int* __restrict__ ninl_out,
     unsigned char* __restrict__ success_out, int* __restrict__ besth_out, double* __restrict__ Hmin_out,
     float* __restrict__ err_out) {
@@ -276,24 +185,11 @@ __global__ __launch_bounds__(EM_THREADS) void ransac_lo_kernel(
   const int* cidx = cidx_all + (size_t)b * M;
   const long long* mm = m0 + (size_t)b * M;
   unsigned char* inl = inl_out + o * M;
-  double t2 = th.t2[0];
-#pragma unroll
-  for (int q = 1; q < RS_MAX_T; ++q) t2 = (q == t) ? th.t2[q] : t2;
-  // winner over the hypothesis ranges: lowest score, ties to the lower h
-  double bs = INFINITY;
-  int bh = -1;
-  if (n >= 4)
-    for (int s = 0; s < S; ++s) {
-      const double os = part_score[((size_t)b * S + s) * T + t];
-      const int oh = part_h[((size_t)b * S + s) * T + t];
-      if (oh >= 0 && (os < bs || (os == bs && oh < bh))) { bs = os; bh = oh; }
-    }
+  const double t2 = rs_pick(th, t);  // squared on the host
+  const int bh = n >= 4 ? rs_merge_ranges(part_score, part_idx, b, S, T, t) : -1;
   double cur[9];
   bool ok = bh >= 0;
-  if (ok) {
-    const unsigned long long key = rs_key(seed, stream_id ? (unsigned long long)stream_id[b] : (unsigned long long)b);
-    ok = rs_hypothesis(corr, key, bh, n, cur);
-  }
+  if (ok) ok = rs_hypothesis(corr, rs_pair_key(seed, stream_id, b), bh, n, cur);
   if (!ok) {  // uniform over the block
     for (int i = tid; i < M; i += EM_THREADS) inl[i] = 0;
     if (tid < 9) { Hout[o * 9 + tid] = (tid % 4 == 0) ? 1.0 : 0.0; Hmin_out[o * 9 + tid] = (tid % 4 == 0) ? 1.0 : 0.0; }
@@ -304,7 +200,7 @@ __global__ __launch_bounds__(EM_THREADS) void ransac_lo_kernel(
     return;
   }
   if (tid < 9) Hmin_out[o * 9 + tid] = cur[tid];
-  double cur_score = rs_block_msac(cur, corr, n, t2, red, tid);
+  double cur_score = rs_block_msac<rs_homography>(cur, corr, n, t2, red, tid);
   for (int it = 0; it < lo_iters; ++it) {
     // normalised DLT over the inliers of the current model (unit weights), as dlt_kernel
     double s5[5] = {0, 0, 0, 0, 0};
@@ -351,31 +247,17 @@ __global__ __launch_bounds__(EM_THREADS) void ransac_lo_kernel(
     const int fin = sflag;
     __syncthreads();
     if (!fin) break;
-    const double cand_score = rs_block_msac(cand, corr, n, t2, red, tid);
-    if (!(cand_score < cur_score)) break;
+    if (!rs_lo_accept<rs_homography>(cand, cur_score, corr, n, t2, red, tid)) break;
 #pragma unroll
     for (int r = 0; r < 9; ++r) cur[r] = cand[r];
-    cur_score = cand_score;
   }
-  // outputs: inliers in key-point-0 indexing (every i is written exactly once: unmatched rows here, matched rows below)
-  for (int i = tid; i < M; i += EM_THREADS) {
-    const long long j = mm[i];
-    if (!(j > -1 && j < N)) inl[i] = 0;
-  }
-  double cntv[1] = {0.0};
-  for (int c = tid; c < n; c += EM_THREADS) {
-    const float4 q = corr[c];
-    const bool in = rs_residual2(cur, q.x, q.y, q.z, q.w) < t2;
-    inl[cidx[c]] = in ? 1 : 0;  // cidx[c] < M by construction (ransac_compact_kernel)
-    cntv[0] += in ? 1.0 : 0.0;
-  }
-  block_sum_f64<1>(cntv, red, tid);
+  const int ninl = rs_write_inliers<rs_homography>(cur, corr, cidx, mm, inl, n, M, N, t2, red, tid);
   if (tid == 0) {
     float Hf[9];
     bool fin = true;
     for (int r = 0; r < 9; ++r) { Hf[r] = (float)cur[r]; fin = fin && isfinite(Hf[r]); }
     for (int r = 0; r < 9; ++r) Hout[o * 9 + r] = cur[r];  // fp64, as computed; the corner error is fp32 like dlt_kernel's
-    ninl_out[o] = (int)cntv[0];
+    ninl_out[o] = ninl;
     success_out[o] = 1;
     besth_out[o] = bh;
     if (err_out) err_out[o] = fin ? corner_error(Hf, Hgt + (size_t)b * 9, size0[b * 2], size0[b * 2 + 1]) : INFINITY;
@@ -383,37 +265,8 @@ __global__ __launch_bounds__(EM_THREADS) void ransac_lo_kernel(
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------------------
-// Hypothesis ranges per pair: ceil(512 / B) of them, so that a small batch still fills the device, but at most
-// floor(NH / 256): a range (ceil(NH / S) hypotheses, the last one what is left) then has at least one hypothesis per
-// lane whenever NH >= 256.  The winner does not depend on S.
-static int rs_splits(int B, int NH) {
-  const int want = (512 + B - 1) / B, most = NH / EM_THREADS;
-  return (want < most ? want : most) < 1 ? 1 : (want < most ? want : most);
-}
-
-struct rs_layout { size_t corr, cidx, cnt, pscore, ph, total; };
-static rs_layout rs_plan(int B, int M, int T, int NH) {
-  const size_t S = (size_t)rs_splits(B, NH);
-  gfc_slots s;
-  return {s.take((size_t)B * M * sizeof(float4)), s.take((size_t)B * M * sizeof(int)), s.take((size_t)B * sizeof(int)),
-          s.take((size_t)B * S * T * sizeof(double)), s.take((size_t)B * S * T * sizeof(int)), s.off};
-}
-
 extern "C" size_t gfc_eval_homography_ransac_workspace_bytes(int B, int M, int T, int num_hypotheses) {
-  if (B <= 0 || M < 0 || T <= 0 || T > RS_MAX_T || num_hypotheses <= 0) return 0;
-  return rs_plan(B, M, T, num_hypotheses).total;
-}
-
-template <int T>
-static int rs_launch_score(int blocks, size_t lds, hipStream_t st, const float4* corr, const int* cnt,
-                            const long long* stream_id, unsigned long long seed, int M, int S, int NH, int use_lds,
-                            const rs_thresholds& th, double* ps, int* ph) {
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)ransac_score_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return GFC_ERR_LAUNCH;
-  hipLaunchKernelGGL(ransac_score_kernel<T>, dim3(blocks), dim3(EM_THREADS), lds, st, corr, cnt, stream_id, seed, M, S, NH,
-                     use_lds, th, ps, ph);
-  return GFC_OK;
+  return rs_workspace_bytes(B, M, T, num_hypotheses, 0);
 }
 
 extern "C" int gfc_eval_homography_ransac(const float* kp0, const float* kp1, const int64_t* m0,
@@ -422,54 +275,20 @@ extern "C" int gfc_eval_homography_ransac(const float* kp0, const float* kp1, co
                                           uint64_t seed, double* H_out, uint8_t* inliers, int32_t* num_inliers,
                                           uint8_t* success, int32_t* best_hypothesis, double* H_minimal, float* err_out,
                                           void* ws, size_t ws_bytes, void* stream) {
-  if (B <= 0 || M < 0 || N < 0 || T <= 0 || T > RS_MAX_T || num_hypotheses <= 0 || lo_iters < 0) return GFC_ERR_INVALID;
-  // an empty side has nothing to point at: its arrays may be NULL
-  if ((M > 0 && (!kp0 || !m0 || !inliers)) || (N > 0 && !kp1) || !thresholds || !H_out || !num_inliers || !success ||
-      !best_hypothesis || !H_minimal || !ws)
-    return GFC_ERR_INVALID;
+  if (!H_out || !H_minimal) return GFC_ERR_INVALID;
   if ((H_gt == nullptr) != (image_size0 == nullptr) || (H_gt == nullptr) != (err_out == nullptr)) return GFC_ERR_INVALID;
-  if ((size_t)B * (size_t)T > 0x7fffffffull || (size_t)B * (size_t)rs_splits(B, num_hypotheses) > 0x7fffffffull)
-    return GFC_ERR_INVALID;
-  rs_thresholds th;
-  for (int t = 0; t < RS_MAX_T; ++t) {
-    const float v = thresholds[t < T ? t : T - 1];
-    if (!(v > 0.f) || !(v < INFINITY)) return GFC_ERR_INVALID;
-    th.t2[t] = (double)v * (double)v;
-  }
-  const rs_layout L = rs_plan(B, M, T, num_hypotheses);
-  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
-  char* w = (char*)ws;
-  float4* corr = (float4*)(w + L.corr);
-  int* cidx = (int*)(w + L.cidx);
-  int* cnt = (int*)(w + L.cnt);
-  double* ps = (double*)(w + L.pscore);
-  int* ph = (int*)(w + L.ph);
-  hipStream_t st = (hipStream_t)stream;
-  const int S = rs_splits(B, num_hypotheses);
-  const long long* sid = (const long long*)stream_id;
-  hipLaunchKernelGGL(ransac_compact_kernel, dim3(B), dim3(EM_THREADS), 0, st, kp0, kp1, (const long long*)m0, M, N, corr,
-                     cidx, cnt);
-  GFC_LAUNCH_CHECK();
-  const size_t corr_bytes = (size_t)M * sizeof(float4);
-  const int use_lds = corr_bytes <= RS_LDS_CORR_BYTES ? 1 : 0;  // beyond: the records are read through L2
-  const size_t lds = use_lds ? corr_bytes : 0;
-  const int blocks = B * S;
-  int rc;
-  switch (T) {
-    case 1: rc = rs_launch_score<1>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
-    case 2: rc = rs_launch_score<2>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
-    case 3: rc = rs_launch_score<3>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
-    case 4: rc = rs_launch_score<4>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
-    case 5: rc = rs_launch_score<5>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
-    case 6: rc = rs_launch_score<6>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
-    case 7: rc = rs_launch_score<7>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
-    default: rc = rs_launch_score<8>(blocks, lds, st, corr, cnt, sid, seed, M, S, num_hypotheses, use_lds, th, ps, ph); break;
-  }
+  rs_frame f;
+  const int rc = rs_begin(kp0, kp1, m0, B, M, N, thresholds, T, num_hypotheses, lo_iters, inliers, num_inliers, success,
+                          best_hypothesis, 0, ws, ws_bytes, stream, f);
   if (rc != GFC_OK) return rc;
-  GFC_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ransac_lo_kernel, dim3(B * T), dim3(EM_THREADS), 0, st, corr, cidx, cnt, (const long long*)m0, sid,
-                     (unsigned long long)seed, M, N, S, T, lo_iters, th, ps, ph, H_gt, image_size0, H_out, inliers,
-                     num_inliers, success, best_hypothesis, H_minimal, err_out);
+  rs_homography::args a;
+  for (int t = 0; t < RS_MAX_T; ++t) a.th.v[t] = f.th.v[t] * f.th.v[t];
+  const long long* sid = (const long long*)stream_id;
+  const int rs = rs_score<rs_homography>(T, f, sid, (unsigned long long)seed, B, M, num_hypotheses, a);
+  if (rs != GFC_OK) return rs;
+  hipLaunchKernelGGL(ransac_lo_kernel, dim3(B * T), dim3(EM_THREADS), 0, f.st, f.corr, f.cidx, f.cnt, (const long long*)m0,
+                     sid, (unsigned long long)seed, M, N, f.S, T, lo_iters, a.th, f.part_score, f.part_idx, H_gt,
+                     image_size0, H_out, inliers, num_inliers, success, best_hypothesis, H_minimal, err_out);
   GFC_LAUNCH_CHECK();
   return GFC_OK;
 }

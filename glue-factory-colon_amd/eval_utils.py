@@ -153,6 +153,47 @@ def ransac_thresholds(ransac_th):
     return ths
 
 
+class _RansacCall:
+    """What `homography_ransac` and `relative_pose_ransac` share: the checked and cast inputs (k0, k1, m0), the threshold
+    list, the stream ids as a [B] long tensor (or None), and the four outputs both estimators have."""
+
+    def __init__(self, kp0, kp1, matches0, ransac_th, stream_id):
+        nat.require_cuda(kp0, "keypoints0")
+        nat.require_cuda(kp1, "keypoints1")
+        nat.require_cuda(matches0, "matches0")
+        self.dev = dev = kp0.device
+        self.b, self.m, self.n = b, m, _ = kp0.shape[0], kp0.shape[1], kp1.shape[1]
+        self.ths = [float(t) for t in ransac_th] if isinstance(ransac_th, (list, tuple, np.ndarray, torch.Tensor)) else [float(ransac_th)]
+        self.t = t = len(self.ths)
+        self.k0, self.k1 = kp0.float().contiguous(), kp1.float().contiguous()
+        self.m0 = matches0.to(torch.long).contiguous()
+        if stream_id is None:
+            self.sid = None
+        elif isinstance(stream_id, torch.Tensor):
+            self.sid = stream_id.to(device=dev, dtype=torch.long).reshape(b).contiguous()
+        else:
+            self.sid = torch.as_tensor(np.broadcast_to(np.asarray(stream_id, dtype=np.int64), (b,)).copy(), device=dev)
+        self.inl = torch.empty((b, t, m), device=dev, dtype=torch.uint8)
+        self.succ = torch.empty((b, t), device=dev, dtype=torch.uint8)
+        self.ninl, self.besth = self.empty(torch.int32), self.empty(torch.int32)
+        self.th_host = (ctypes.c_float * max(t, 1))(*self.ths)
+
+    def empty(self, dtype, *tail):
+        """An output of shape [B, T, *tail]."""
+        return torch.empty((self.b, self.t, *tail), device=self.dev, dtype=dtype)
+
+    def workspace(self, holder, nbytes):
+        return holder.get(max(nbytes, 256), self.dev)
+
+    def common(self):
+        """The result entries both estimators have, in the order they have them."""
+        return {"inliers": self.inl.bool(), "num_inliers": self.ninl, "success": self.succ.bool(),
+                "best_hypothesis": self.besth}
+
+    def thresholds(self):
+        return torch.tensor(self.ths, dtype=torch.float32, device=self.dev)
+
+
 def homography_ransac(H_0to1, kp0, kp1, matches0, image_size0, ransac_th, *, num_hypotheses=2048, lo_iters=3, seed=0,
                       stream_id=None):
     """RANSAC homography for B pairs x T thresholds in one call of `gfc_eval_homography_ransac`.  Batched device
@@ -161,45 +202,23 @@ def homography_ransac(H_0to1, kp0, kp1, matches0, image_size0, ransac_th, *, num
     the random stream of each pair.  Returns a dict of device tensors: H [B,T,3,3] float64, inliers [B,T,M] bool (key-point-0
     indexing), num_inliers [B,T] int32, success [B,T] bool, best_hypothesis [B,T] int32, H_minimal [B,T,3,3] float64,
     thresholds [T], and error [B,T] when H_0to1 is given."""
-    nat.require_cuda(kp0, "keypoints0")
-    nat.require_cuda(kp1, "keypoints1")
-    nat.require_cuda(matches0, "matches0")
-    lib = nat.lib()
-    dev = kp0.device
-    b, m, n = kp0.shape[0], kp0.shape[1], kp1.shape[1]
-    ths = [float(t) for t in ransac_th] if isinstance(ransac_th, (list, tuple, np.ndarray, torch.Tensor)) else [float(ransac_th)]
-    t = len(ths)
     if (H_0to1 is None) != (image_size0 is None):
         raise ValueError("H_0to1 and image_size0 are given together or not at all")
-    k0, k1 = kp0.float().contiguous(), kp1.float().contiguous()
-    m0 = matches0.to(torch.long).contiguous()
-    if stream_id is None:
-        sid = None
-    elif isinstance(stream_id, torch.Tensor):
-        sid = stream_id.to(device=dev, dtype=torch.long).reshape(b).contiguous()
-    else:
-        sid = torch.as_tensor(np.broadcast_to(np.asarray(stream_id, dtype=np.int64), (b,)).copy(), device=dev)
+    c = _RansacCall(kp0, kp1, matches0, ransac_th, stream_id)
+    lib, dev, b, t = nat.lib(), c.dev, c.b, c.t
     H = size = err = None
     if H_0to1 is not None:
         H = H_0to1.to(device=dev, dtype=torch.float32).reshape(b, 9).contiguous()
         size = image_size0.to(device=dev, dtype=torch.float32).reshape(b, 2).contiguous()
-        err = torch.empty((b, t), device=dev, dtype=torch.float32)
-    Hout = torch.empty((b, t, 3, 3), device=dev, dtype=torch.float64)
-    Hmin = torch.empty((b, t, 3, 3), device=dev, dtype=torch.float64)
-    inl = torch.empty((b, t, m), device=dev, dtype=torch.uint8)
-    ninl = torch.empty((b, t), device=dev, dtype=torch.int32)
-    succ = torch.empty((b, t), device=dev, dtype=torch.uint8)
-    besth = torch.empty((b, t), device=dev, dtype=torch.int32)
-    th_host = (ctypes.c_float * max(t, 1))(*ths)
-    nbytes = lib.gfc_eval_homography_ransac_workspace_bytes(b, m, t, int(num_hypotheses))
-    ws = _ransac_ws.get(max(nbytes, 256), dev)
-    nat.check(lib.gfc_eval_homography_ransac(nat.ptr(k0), nat.ptr(k1), nat.ptr(m0), nat.ptr(sid), nat.ptr(H),
-                                             nat.ptr(size), b, m, n, th_host, t, int(num_hypotheses), int(lo_iters),
-                                             int(seed) & _M64, nat.ptr(Hout), nat.ptr(inl), nat.ptr(ninl),
-                                             nat.ptr(succ), nat.ptr(besth), nat.ptr(Hmin), nat.ptr(err), nat.ptr(ws),
+        err = c.empty(torch.float32)
+    Hout, Hmin = c.empty(torch.float64, 3, 3), c.empty(torch.float64, 3, 3)
+    ws = c.workspace(_ransac_ws, lib.gfc_eval_homography_ransac_workspace_bytes(b, c.m, t, int(num_hypotheses)))
+    nat.check(lib.gfc_eval_homography_ransac(nat.ptr(c.k0), nat.ptr(c.k1), nat.ptr(c.m0), nat.ptr(c.sid), nat.ptr(H),
+                                             nat.ptr(size), b, c.m, c.n, c.th_host, t, int(num_hypotheses), int(lo_iters),
+                                             int(seed) & _M64, nat.ptr(Hout), nat.ptr(c.inl), nat.ptr(c.ninl),
+                                             nat.ptr(c.succ), nat.ptr(c.besth), nat.ptr(Hmin), nat.ptr(err), nat.ptr(ws),
                                              ws.numel(), nat.stream_ptr(dev)), "gfc_eval_homography_ransac")
-    out = {"H": Hout, "inliers": inl.bool(), "num_inliers": ninl, "success": succ.bool(), "best_hypothesis": besth,
-           "H_minimal": Hmin, "thresholds": torch.tensor(ths, dtype=torch.float32, device=dev)}
+    out = {"H": Hout, **c.common(), "H_minimal": Hmin, "thresholds": c.thresholds()}
     if err is not None:
         out["error"] = err
     return out
@@ -441,47 +460,26 @@ def relative_pose_ransac(kp0, kp1, matches0, camera0, camera1, ransac_th, T_0to1
     with T_0to1 also r_err, t_err [B,T] float64 degrees (t up to sign).  Convention X1 = R X0 + t."""
     from . import geometry
 
-    nat.require_cuda(kp0, "keypoints0")
-    nat.require_cuda(kp1, "keypoints1")
-    nat.require_cuda(matches0, "matches0")
-    lib = nat.lib()
-    dev = kp0.device
-    b, m, n = kp0.shape[0], kp0.shape[1], kp1.shape[1]
-    ths = [float(t) for t in ransac_th] if isinstance(ransac_th, (list, tuple, np.ndarray, torch.Tensor)) else [float(ransac_th)]
-    t = len(ths)
+    c = _RansacCall(kp0, kp1, matches0, ransac_th, stream_id)
+    lib, dev, b, t = nat.lib(), c.dev, c.b, c.t
     cam0, model0 = geometry.camera_args(camera0, b, dev)
     cam1, model1 = geometry.camera_args(camera1, b, dev)
-    k0, k1 = kp0.float().contiguous(), kp1.float().contiguous()
-    m0 = matches0.to(torch.long).contiguous()
-    if stream_id is None:
-        sid = None
-    elif isinstance(stream_id, torch.Tensor):
-        sid = stream_id.to(device=dev, dtype=torch.long).reshape(b).contiguous()
-    else:
-        sid = torch.as_tensor(np.broadcast_to(np.asarray(stream_id, dtype=np.int64), (b,)).copy(), device=dev)
     T01 = rerr = terr = None
     if T_0to1 is not None:
         T01, _ = geometry.pose_args(T_0to1, b, dev)
-        rerr = torch.empty((b, t), device=dev, dtype=torch.float64)
-        terr = torch.empty((b, t), device=dev, dtype=torch.float64)
-    f64 = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float64)
-    i32 = lambda: torch.empty((b, t), device=dev, dtype=torch.int32)
-    R, tv, E, Emin = f64(b, t, 3, 3), f64(b, t, 3), f64(b, t, 3, 3), f64(b, t, 3, 3)
-    inl = torch.empty((b, t, m), device=dev, dtype=torch.uint8)
-    succ = torch.empty((b, t), device=dev, dtype=torch.uint8)
-    ninl, besth, bestk = i32(), i32(), i32()
-    th_host = (ctypes.c_float * max(t, 1))(*ths)
-    nbytes = lib.gfc_eval_relative_pose_ransac_workspace_bytes(b, m, t, int(num_hypotheses))
-    ws = _relpose_ws.get(max(nbytes, 256), dev)
+        rerr, terr = c.empty(torch.float64), c.empty(torch.float64)
+    R, tv = c.empty(torch.float64, 3, 3), c.empty(torch.float64, 3)
+    E, Emin = c.empty(torch.float64, 3, 3), c.empty(torch.float64, 3, 3)
+    bestk = c.empty(torch.int32)
+    ws = c.workspace(_relpose_ws, lib.gfc_eval_relative_pose_ransac_workspace_bytes(b, c.m, t, int(num_hypotheses)))
     nat.check(lib.gfc_eval_relative_pose_ransac(
-        nat.ptr(k0), nat.ptr(k1), nat.ptr(m0), nat.ptr(sid), nat.ptr(cam0), model0, nat.ptr(cam1), model1, nat.ptr(T01),
-        b, m, n, th_host, t, int(num_hypotheses), int(lo_iters), int(seed) & _M64, float(ignore_gt_t_thr), nat.ptr(R),
-        nat.ptr(tv), nat.ptr(E), nat.ptr(Emin), nat.ptr(inl), nat.ptr(ninl), nat.ptr(succ), nat.ptr(besth),
-        nat.ptr(bestk), nat.ptr(rerr), nat.ptr(terr), nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)),
-        "gfc_eval_relative_pose_ransac")
-    out = {"R": R, "t": tv, "E": E, "E_minimal": Emin, "inliers": inl.bool(), "num_inliers": ninl,
-           "success": succ.bool(), "best_hypothesis": besth, "best_solution": bestk,
-           "thresholds": torch.tensor(ths, dtype=torch.float32, device=dev)}
+        nat.ptr(c.k0), nat.ptr(c.k1), nat.ptr(c.m0), nat.ptr(c.sid), nat.ptr(cam0), model0, nat.ptr(cam1), model1,
+        nat.ptr(T01), b, c.m, c.n, c.th_host, t, int(num_hypotheses), int(lo_iters), int(seed) & _M64,
+        float(ignore_gt_t_thr), nat.ptr(R), nat.ptr(tv), nat.ptr(E), nat.ptr(Emin), nat.ptr(c.inl), nat.ptr(c.ninl),
+        nat.ptr(c.succ), nat.ptr(c.besth), nat.ptr(bestk), nat.ptr(rerr), nat.ptr(terr), nat.ptr(ws), ws.numel(),
+        nat.stream_ptr(dev)), "gfc_eval_relative_pose_ransac")
+    out = {"R": R, "t": tv, "E": E, "E_minimal": Emin, **c.common(), "best_solution": bestk,
+           "thresholds": c.thresholds()}
     if rerr is not None:
         out["r_err"], out["t_err"] = rerr, terr
     return out

@@ -394,12 +394,49 @@ def _case_ransac(_):
     return lib.gfc_eval_homography_ransac_workspace_bytes(b, m, t, nh), run
 
 
+def _case_relpose(_):
+    """Two ranges per pair; all six (pair, threshold) blocks succeed, so every block's solve slice of the workspace is
+    used (asserted below)."""
+    lib = nat.lib()
+    g = gen(46)
+    b, m, t, nh = 2, 100, 3, 512
+    X = torch.rand((b, m, 3), generator=g) * torch.tensor([4.0, 3.0, 4.0]) + torch.tensor([-2.0, -1.5, 4.0])
+    ay, ax = torch.tensor(0.12), torch.tensor(-0.05)
+    Ry = torch.tensor([[ay.cos(), 0.0, ay.sin()], [0.0, 1.0, 0.0], [-ay.sin(), 0.0, ay.cos()]])
+    Rx = torch.tensor([[1.0, 0.0, 0.0], [0.0, ax.cos(), -ax.sin()], [0.0, ax.sin(), ax.cos()]])
+    Y = X @ (Ry @ Rx).T + torch.tensor([0.6, 0.1, 0.05])
+    f, c = 500.0, torch.tensor([320.0, 240.0])
+    kp0 = f * X[..., :2] / X[..., 2:] + c
+    kp1 = f * Y[..., :2] / Y[..., 2:] + c + 0.3 * torch.randn((b, m, 2), generator=g)
+    kp1[:, ::4] = torch.rand((b, (m + 3) // 4, 2), generator=g) * 400  # a quarter of the matches are outliers
+    m0 = torch.arange(m).expand(b, m).clone()
+    m0[:, 5::17] = -1
+    cam = torch.tensor([[640.0, 480.0, f, f, 320.0, 240.0, 0.0, 0.0, 0.0, 0.0]] * b)  # PINHOLE (model 0)
+    dk0, dk1, dm0, dcam = kp0.contiguous().to(DEV), kp1.contiguous().to(DEV), m0.to(DEV), cam.to(DEV)
+    th = (ctypes.c_float * t)(1.0, 2.0, 4.0)
+
+    def run(ws, nbytes):
+        f64 = lambda *tail: torch.zeros((b, t, *tail), device=DEV, dtype=torch.float64)  # noqa: E731
+        i32 = lambda: torch.zeros((b, t), device=DEV, dtype=torch.int32)  # noqa: E731
+        o = [f64(3, 3), f64(3), f64(3, 3), f64(3, 3), torch.zeros((b, t, m), device=DEV, dtype=torch.uint8), i32(),
+             torch.zeros((b, t), device=DEV, dtype=torch.uint8), i32(), i32()]
+        nat.check(lib.gfc_eval_relative_pose_ransac(P(dk0), P(dk1), P(dm0), None, P(dcam), 0, P(dcam), 0, None, b, m, m, th,
+                                                    t, nh, 3, 7, 0.0, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(o[5]),
+                                                    P(o[6]), P(o[7]), P(o[8]), None, None, P(ws), nbytes, st()),
+                  "gfc_eval_relative_pose_ransac")
+        assert bool(o[6].bool().all()), "a block failed: its solve slice is not exercised"
+        return o
+
+    return lib.gfc_eval_relative_pose_ransac_workspace_bytes(b, m, t, nh), run
+
+
 CASES = [(fn, arg) for arg in ("fp32", "fp16")
          for fn in (_case_lg_layer, _case_lg_assign, _case_lg_forward, _case_lg_forward_packed, _case_lg_forward_ragged,
                     _case_attention)]
 CASES += [(_case_nn_match, None), (_case_log_assignment, None), (_case_filter_matches, None), (_case_adaptive_step, None),
           (_case_sp_dense, 1), (_case_sp_dense, 3), (_case_sp_select, False), (_case_sp_select, True),
-          (_case_disk_nms_select, None), (_case_disk_instnorm, None), (_case_ransac, None)]
+          (_case_disk_nms_select, None), (_case_disk_instnorm, None), (_case_ransac, None),
+          (_case_relpose, None)]
 
 
 @pytest.mark.parametrize("case,arg", CASES, ids=[f"{fn.__name__[6:]}-{arg}" for fn, arg in CASES])

@@ -78,6 +78,16 @@ SIZES = {
         ((5, 33, 5, 1), 4352), ((0, 10, 3, 512), 0), ((2, -1, 3, 512), 0), ((2, 10, 0, 512), 0), ((2, 10, 9, 512), 0),
         ((2, 10, 3, 0), 0),
     ],
+    # the homography estimator's arguments; recorded from a build of the commit before the two estimators shared one
+    # layout function (the five slots above plus 3288 bytes of solver scratch per (pair, threshold))
+    "gfc_eval_relative_pose_ransac_workspace_bytes": [
+        ((2, 1000, 3, 4096), 61696), ((2, 100, 3, 512), 25088), ((20, 100, 8, 255), 568576),
+        ((20, 100, 8, 256), 568576), ((20, 100, 8, 511), 568576), ((20, 100, 8, 512), 570368),
+        ((3, 100, 8, 43520), 134656), ((3, 100, 8, 43776), 135168), ((3, 100, 8, 44032), 135168),
+        ((1, 100, 3, 1048576), 30976), ((511, 7, 1, 4096), 1766400), ((512, 7, 1, 4096), 1763328),
+        ((513, 7, 1, 4096), 1767936), ((3, 0, 2, 1000), 20736), ((5, 33, 5, 1), 86784), ((0, 10, 3, 512), 0),
+        ((2, -1, 3, 512), 0), ((2, 10, 0, 512), 0), ((2, 10, 9, 512), 0), ((2, 10, 3, 0), 0),
+    ],
     "gfc_lg_workspace_bytes": [
         ((2, 65, 130), 6796032), ((1, 1, 1), 35584), ((1, 63, 5), 1185536), ((1, 64, 5), 1202944),
         ((1, 65, 5), 1220352), ((3, 128, 67), 10193920), ((3, 129, 67), 10246144), ((2, 1024, 1024), 71369216),
@@ -188,6 +198,10 @@ def _short_calls():
         lib.gfc_eval_homography_ransac_workspace_bytes(2, 100, 3, 512), lambda ws: lib.gfc_eval_homography_ransac(
             f(1), f(2), f(3), None, None, None, 2, 100, 100, th, 3, 512, 3, 0, f(4), f(5), f(6), f(7), f(8), f(9), None,
             f(10), ws, None))
+    calls["eval_relative_pose_ransac"] = (
+        lib.gfc_eval_relative_pose_ransac_workspace_bytes(2, 100, 3, 512), lambda ws: lib.gfc_eval_relative_pose_ransac(
+            f(1), f(2), f(3), None, f(4), 0, f(5), 0, None, 2, 100, 100, th, 3, 512, 3, 0, 0.0, f(6), f(7), f(8), f(9),
+            f(10), f(11), f(12), f(13), f(14), None, None, f(15), ws, None))
     calls["nn_match"] = (lib.gfc_nn_workspace_bytes(B, M, N), lambda ws: lib.gfc_nn_match(
         f(1), f(2), B, M, N, 64, 0.8, 0.0, 1, f(3), f(4), f(5), f(6), f(7), f(8), f(9), ws, None))
     # the two without a size export: the sizes include/gfc_amd.h documents
@@ -221,7 +235,7 @@ def _short_calls():
 
 
 _SHORT = ["sp_dense_c1", "sp_dense_c3", "sp_select", "sp_nms_select", "disk_nms_select", "disk_instnorm_stats",
-          "eval_homography_ransac", "nn_match", "lg_log_assignment", "lg_filter_matches", "lg_adaptive_step"] + [
+          "eval_homography_ransac", "eval_relative_pose_ransac", "nn_match", "lg_log_assignment", "lg_filter_matches", "lg_adaptive_step"] + [
     f"lg_{e}_{t}" for t in ("fp32", "fp16") for e in ("layer", "assign", "forward", "forward_packed", "forward_ragged")]
 
 
