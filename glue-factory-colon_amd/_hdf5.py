@@ -190,6 +190,44 @@ def write_records(path, records: dict):
 _VISIT = ctypes.CFUNCTYPE(herr_t, hid_t, c_char_p, c_void_p, c_void_p)
 
 
+def _read_dataset(h, f, full):
+    """One dataset of the open file `f` as an array of its own type."""
+    d = _chk(h.H5Dopen2(f, full.encode(), H5P_DEFAULT), f"open dataset {full}")
+    sp, tp = h.H5Dget_space(d), h.H5Dget_type(d)
+    try:
+        nd = h.H5Sget_simple_extent_ndims(sp)
+        dims = (c_ulonglong * max(nd, 1))()
+        if nd > 0:
+            h.H5Sget_simple_extent_dims(sp, dims, None)
+        shape = tuple(int(dims[i]) for i in range(nd))
+        cls, size = h.H5Tget_class(tp), int(h.H5Tget_size(tp))
+        if cls == H5T_FLOAT:
+            key = "f" + str(size)
+        elif cls == H5T_INTEGER:
+            key = ("i" if h.H5Tget_sign(tp) else "u") + str(size)
+        else:
+            raise TypeError(f"{full}: unsupported HDF5 type class {cls}")
+        a = np.empty(shape, dtype=np.dtype(key))
+        if a.size:
+            _chk(h.H5Dread(d, _native[key], H5S_ALL, H5S_ALL, H5P_DEFAULT, a.ctypes.data_as(c_void_p)),
+                 f"read {full}")
+    finally:
+        h.H5Tclose(tp)
+        h.H5Sclose(sp)
+        h.H5Dclose(d)
+    return a
+
+
+def read_dataset(path, name):
+    """The dataset `name` (e.g. "/depth": a MegaDepth-style depth file) of an HDF5 file."""
+    h = lib()
+    f = _chk(h.H5Fopen(str(path).encode(), H5F_ACC_RDONLY, H5P_DEFAULT), f"open {path}")
+    try:
+        return _read_dataset(h, f, name)
+    finally:
+        h.H5Fclose(f)
+
+
 def read_records(path) -> dict:
     """HDF5 file -> {group path: {dataset name: ndarray}} for every dataset in the file."""
     h = lib()
@@ -214,29 +252,7 @@ def read_records(path) -> dict:
             h.H5Oclose(o)
             if kind != H5I_DATASET:
                 continue
-            d = _chk(h.H5Dopen2(f, full.encode(), H5P_DEFAULT), f"open dataset {full}")
-            sp, tp = h.H5Dget_space(d), h.H5Dget_type(d)
-            try:
-                nd = h.H5Sget_simple_extent_ndims(sp)
-                dims = (c_ulonglong * max(nd, 1))()
-                if nd > 0:
-                    h.H5Sget_simple_extent_dims(sp, dims, None)
-                shape = tuple(int(dims[i]) for i in range(nd))
-                cls, size = h.H5Tget_class(tp), int(h.H5Tget_size(tp))
-                if cls == H5T_FLOAT:
-                    key = "f" + str(size)
-                elif cls == H5T_INTEGER:
-                    key = ("i" if h.H5Tget_sign(tp) else "u") + str(size)
-                else:
-                    raise TypeError(f"{full}: unsupported HDF5 type class {cls}")
-                a = np.empty(shape, dtype=np.dtype(key))
-                if a.size:
-                    _chk(h.H5Dread(d, _native[key], H5S_ALL, H5S_ALL, H5P_DEFAULT, a.ctypes.data_as(c_void_p)),
-                         f"read {full}")
-            finally:
-                h.H5Tclose(tp)
-                h.H5Sclose(sp)
-                h.H5Dclose(d)
+            a = _read_dataset(h, f, full)
             grp, key = full.rsplit("/", 1)
             out.setdefault(grp, {})[key] = a
     finally:

@@ -153,6 +153,7 @@ SIGNATURES = {
     "gfc_eval_matches_epipolar": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_void_p] + [c_int] * 3
                                   + [c_void_p] * 2),
     "gfc_preprocess_resize": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] + [c_int] * 4 + [c_void_p]),
+    "gfc_preprocess_resample": (c_int, [c_void_p] + [c_int] * 11 + [c_float] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
     "gfc_lg_layer_workspace_bytes": (c_size_t, [c_int]),
     "gfc_lg_layer": (c_int, [POINTER(LgParams), c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                              c_int, c_void_p, c_size_t, c_void_p]),

@@ -10,10 +10,20 @@ five-point RANSAC (`eval_utils.relative_pose_ransac`) per group of pairs for all
 by pair; here consecutive items of equal shapes (key-point counts, depth-map sizes, camera models) go through ONE call
 of each kernel (one workgroup per pair either way: the numbers do not depend on the grouping).
 
-What is NOT here: the `posed_images` directory reader (tied to the fork's scene-info files and crops) and figures.
-Parity of the GPU estimator with OpenCV / PoseLib / pycolmap (what the reference delegates to) is unpinned.
+From a dataset on disk: `posed_images.PosedImages` reads the directory, `PosedPairFeeder` prepares images, depth and
+masks on the GPU, `get_predictions` exports `predictions.h5` and `run` evaluates it:
+
+    python -m glue_factory_colon_amd.eval_pose_pairs --data_dir /data --benchmark megadepth1500 \\
+        --extractor_weights superpoint_v6_from_tf.pth --matcher_weights superpoint_lightglue.pth --estimator gfc_amd
+
+What is NOT here: figures, and the `image_pairs` list reader the reference's scannet1500 is configured with (its
+settings are kept below; the command line refuses it).  Parity of the GPU estimator with OpenCV / PoseLib / pycolmap
+(what the reference delegates to) is unpinned; so is the reader against the reference's own class (posed_images.py).
 """
+import argparse
+import json
 from collections import defaultdict
+from pathlib import Path
 
 import numpy as np
 import torch
@@ -23,6 +33,24 @@ from .cache_loader import CacheLoader
 from .eval_hpatches import CONTEXT_KEYS, MEMORY_KEYS, TIMING_KEYS, med_mean_summaries
 
 MIN_MATCHES_FOR_POSE = 5
+EXPORT_KEYS = ["keypoints0", "keypoints1", "keypoint_scores0", "keypoint_scores1", "matches0", "matches1",
+               "matching_scores0", "matching_scores1"]
+OPTIONAL_EXPORT_KEYS = [*TIMING_KEYS, *MEMORY_KEYS, *CONTEXT_KEYS]
+# default_conf["data"] of the reference's pipelines (eval/megadepth1500.py:47-59, eval/scannet1500.py:28-37,
+# eval/endomapper_dense1500.py:43-56); "name" is the reference's dataset class
+BENCHMARK_DATA = {
+    "megadepth1500": {"name": "posed_images", "root": "", "image_dir": "{scene}/images", "depth_dir": "{scene}/depths",
+                      "views": "{scene}/views.txt", "view_groups": "{scene}/pairs.txt", "depth_format": "h5",
+                      "scene_list": ["megadepth1500"], "preprocessing": {"side": "long"}},
+    "scannet1500": {"name": "image_pairs", "pairs": "scannet1500/pairs_calibrated.txt", "root": "scannet1500/",
+                    "extra_data": "relative_pose", "preprocessing": {"side": "long"}, "num_workers": 14},
+    "endomapper_dense1500": {"name": "posed_images", "root": "", "image_dir": "{scene}/images",
+                             "depth_dir": "{scene}/depths", "views": "{scene}/views.txt",
+                             "view_groups": "{scene}/pairs.txt", "depth_format": "npz", "crop_endomapper_dense": True,
+                             "depth_scale_scene_info_dir": "endomapper_dense/scene_info", "read_specular_mask": True,
+                             "specular_scene_info_dir": "endomapper_dense/scene_info",
+                             "scene_list": ["endomapper_dense1500"]},
+}
 
 
 def _name(item):
@@ -40,9 +68,37 @@ def _stack_holder(holders):
 
 
 class PosePairsPipeline:
-    def __init__(self, eval_conf=None, max_group=64):
+    export_keys = EXPORT_KEYS
+    optional_export_keys = OPTIONAL_EXPORT_KEYS
+
+    def __init__(self, eval_conf=None, max_group=64, pair_batch=1):
         self.eval_conf = {"estimator": None, "ransac_th": 1.0, **dict(eval_conf or {})}
         self.max_group = int(max_group)
+        self.pair_batch = max(1, int(pair_batch))
+
+    def get_predictions(self, experiment_dir, model, feeder, overwrite=False):
+        """endomapper_dense1500.py:87-100: `predictions.h5` of every pair of `feeder` (a `PosedPairFeeder`, or any
+        iterable of loader items), `pair_batch` consecutive pairs per forward."""
+        from .export_predictions import export_predictions
+
+        pred_file = Path(experiment_dir) / "predictions.h5"
+        if not pred_file.exists() or overwrite:
+            export_predictions(feeder, model, pred_file, keys=self.export_keys, optional_keys=self.optional_export_keys,
+                               pair_batch=self.pair_batch)
+        return pred_file
+
+    def run(self, experiment_dir, model, feeder, overwrite=False):
+        """Predictions (all ranks), then the evaluation and `summaries.json` on rank 0.  Returns (summaries, results) on
+        rank 0, (None, None) elsewhere."""
+        import torch.distributed as dist
+
+        pred_file = self.get_predictions(experiment_dir, model, feeder, overwrite=overwrite)
+        if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+            return None, None
+        summaries, results = self.run_eval(feeder, pred_file)
+        with open(Path(experiment_dir) / "summaries.json", "w") as f:
+            json.dump(summaries, f, indent=1)
+        return summaries, results
 
     def thresholds(self):
         """endomapper_dense1500.py:107-111: a positive number -> that one, a non-positive one -> the sweep."""
@@ -155,3 +211,43 @@ class PosePairsPipeline:
             results = {**results, **pose_results[best_th], "pose_results": pose_results}
             summaries = {**summaries, **pose_summaries}
         return summaries, results
+
+
+def main(argv=None):
+    from . import posed_images
+    from .eval_hpatches import build_model
+
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--data_dir", required=True, help="the directory the benchmark's `root` is relative to")
+    ap.add_argument("--benchmark", required=True, choices=sorted(BENCHMARK_DATA))
+    ap.add_argument("--experiment_dir", default=None, help="default: outputs/<benchmark>")
+    ap.add_argument("--extractor_weights", default="synthetic", help="local .pth (reference key names) or 'synthetic'")
+    ap.add_argument("--matcher_weights", default="synthetic")
+    ap.add_argument("--open", action="store_true", help="superpoint-open + in-tree lightglue instead of the official pair")
+    ap.add_argument("--max_num_keypoints", type=int, default=2048)
+    ap.add_argument("--resize", type=int, default=None, help="preprocessing.resize (the benchmarks leave it unset)")
+    ap.add_argument("--estimator", default=None, choices=[None, *eval_utils.RELATIVE_POSE_ESTIMATORS],
+                    help="robust relative-pose estimator for rel_pose_error* (default: none)")
+    ap.add_argument("--ransac_th", type=float, default=1.0, help="inlier threshold in pixels; <= 0: the sweep 0.5 .. 3.0")
+    ap.add_argument("--pair_batch", type=int, default=8)
+    ap.add_argument("--overwrite", action="store_true")
+    args = ap.parse_args(argv)
+    data_conf = {k: v for k, v in BENCHMARK_DATA[args.benchmark].items()}
+    if data_conf.pop("name") != "posed_images":
+        raise NotImplementedError(f"{args.benchmark}: the reference reads it through its `image_pairs` dataset, which is "
+                                  "not built here; a `posed_images` directory (views.txt, pairs.txt) is")
+    if args.resize is not None:
+        data_conf["preprocessing"] = {**data_conf.get("preprocessing", {}), "resize": args.resize}
+    experiment_dir = Path(args.experiment_dir or f"outputs/{args.benchmark}")
+    experiment_dir.mkdir(parents=True, exist_ok=True)
+    dataset = posed_images.PosedImages(data_conf, args.data_dir)
+    pipe = PosePairsPipeline({"estimator": args.estimator, "ransac_th": args.ransac_th}, pair_batch=args.pair_batch)
+    model = build_model(args.extractor_weights, args.matcher_weights, official=not args.open,
+                        max_num_keypoints=args.max_num_keypoints).to("cuda")
+    summaries, _ = pipe.run(experiment_dir, model, dataset.feeder("cuda"), overwrite=args.overwrite)
+    print(json.dumps(summaries, indent=1))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

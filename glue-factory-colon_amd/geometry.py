@@ -94,6 +94,12 @@ class Pose(_Holder):
         Rt = self.R.transpose(-1, -2)
         return self.__class__.from_Rt(Rt, -(Rt @ self.t.unsqueeze(-1)).squeeze(-1))
 
+    def compose(self, other):
+        """self @ other: the pose that applies `other` first (T_A2C = T_B2C @ T_A2B)."""
+        return self.__class__.from_Rt(self.R @ other.R, self.t + (self.R @ other.t.unsqueeze(-1)).squeeze(-1))
+
+    __matmul__ = compose
+
 
 class Camera(_Holder):
     def __init__(self, data, model=None):

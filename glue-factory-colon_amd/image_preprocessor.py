@@ -54,6 +54,86 @@ def resize(img, size, align_corners=None, antialias=True, bgr=False):
     return out if batched else out[0]
 
 
+RESAMPLE_MODES = {"nearest": 0, "area": 1}  # GFC_RS_NEAREST / GFC_RS_AREA
+_RS_F32_CHW, _RS_U8_HWC, _RS_U8_PLANE, _RS_BITS = range(4)
+
+
+def downscales(in_hw, out_hw):
+    """kornia's condition for its blur: some axis shrinks (factors in fp32, as the kernel evaluates them)."""
+    return max(np.float32(in_hw[0]) / np.float32(out_hw[0]), np.float32(in_hw[1]) / np.float32(out_hw[1])) > 1
+
+
+def resample(img, size, mode, crop=None, antialias=False, value_scale=1.0, want_valid=False, bits_shape=None):
+    """Crop window -> `nearest` / `area` resample in one launch of `gfc_preprocess_resample` (include/gfc_amd.h).
+
+    img, on the GPU: float [H,W] / [C,H,W] / [B,C,H,W]; uint8 [H,W,C] / [H,W] / [B,H,W,C] (decoded image, converted
+    like numpy_image_to_torch); bool [H,W] / [B,H,W] (a mask plane); or, with bits_shape = (H, W), the uint8 bytes
+    `numpy.packbits` makes of the flattened mask ([nbytes] / [B,nbytes]).  crop = (left, top, width, height) in the
+    source plane (default: all of it); everything else sees only the window.  antialias: kornia's blur before a
+    down-scale (nearest only).  value_scale multiplies every source value.
+    -> float [.., size[0], size[1]] with the input's leading axes ([C,h,w] for an [H,W,C] image) -- and with want_valid
+    also `out > 0` as float -- or, for the two mask forms, bool [.., size[0], size[1]] = value > 0.5."""
+    nat.require_cuda(img, "img")
+    if mode not in RESAMPLE_MODES:
+        raise NotImplementedError(f"resample mode {mode!r}: 'nearest' and 'area' are built")
+    lib = nat.lib()
+    oh, ow = int(size[0]), int(size[1])
+    lead = None
+    if bits_shape is not None:
+        if img.dtype != torch.uint8 or img.ndim not in (1, 2):
+            raise ValueError(f"packed bits: expected uint8 [nbytes] or [B,nbytes], got {img.dtype} {tuple(img.shape)}")
+        h, w = int(bits_shape[0]), int(bits_shape[1])
+        x = (img if img.ndim == 2 else img[None]).contiguous()
+        if x.shape[1] != (h * w + 7) // 8:
+            raise ValueError(f"packed bits: {x.shape[1]} bytes per plane for a {h}x{w} mask")
+        b, c, kind, lead = x.shape[0], 1, _RS_BITS, tuple(img.shape[:-1])
+    elif img.dtype == torch.bool:
+        if img.ndim not in (2, 3):
+            raise ValueError(f"mask plane: expected bool [H,W] or [B,H,W], got {tuple(img.shape)}")
+        x = (img if img.ndim == 3 else img[None]).contiguous()
+        (b, h, w), c, kind, lead = x.shape, 1, _RS_U8_PLANE, tuple(img.shape[:-2])
+    elif img.dtype == torch.uint8:
+        x = img if img.ndim != 2 else img[..., None]
+        x = (x if x.ndim == 4 else x[None]).contiguous()
+        (b, h, w, c), kind = x.shape, _RS_U8_HWC
+        lead = ((b,) if img.ndim == 4 else ()) + (c,)
+    else:
+        x = (img.float().reshape((-1,) + tuple(img.shape[-3:])) if img.ndim >= 3 else img.float()[None, None]).contiguous()
+        (b, c, h, w), kind, lead = x.shape, _RS_F32_CHW, tuple(img.shape[:-2])
+    left, top, cw, ch = (0, 0, w, h) if crop is None else (int(v) for v in crop)
+    if mode == "area" and antialias and 0 < cw and 0 < ch and downscales((ch, cw), (oh, ow)):
+        raise NotImplementedError("interpolation 'area' with antialias=True on a down-scale is not built "
+                                  "(the reference's own 'area' configuration sets antialias: False)")
+    is_mask = kind in (_RS_U8_PLANE, _RS_BITS)
+    if is_mask and want_valid:
+        raise ValueError("want_valid with a mask source")
+    out = torch.empty((b, c, oh, ow), device=img.device, dtype=torch.uint8 if is_mask else torch.float32)
+    valid = torch.empty_like(out) if want_valid else None
+    nat.check(lib.gfc_preprocess_resample(nat.ptr(x), kind, b, c, h, w, left, top, cw, ch, RESAMPLE_MODES[mode],
+                                          int(bool(antialias)), float(value_scale), nat.ptr(out), nat.ptr(valid), oh, ow,
+                                          nat.stream_ptr(img.device)), "gfc_preprocess_resample")
+    if is_mask:
+        out = out.view(torch.bool)
+    out = out.reshape(lead + (oh, ow))
+    return (out, valid.reshape(lead + (oh, ow))) if want_valid else out
+
+
+ENDOMAPPER_DENSE_TARGET = (512, 672)          # (h, w) of the cropped image
+ENDOMAPPER_DENSE_FIRST = (0, 35, 540, 675)    # (top, left, h, w) of the first window
+
+
+def endomapper_dense_window(h, w):
+    """The fixed Endomapper-dense crop (image.py:77-103) of an h x w plane as a window (left, top, width, height):
+    the whole plane when it already is 512x672, else the centred 512x672 of the 540x675 window at (top 0, left 35)."""
+    th, tw = ENDOMAPPER_DENSE_TARGET
+    if (h, w) == (th, tw):
+        return 0, 0, tw, th
+    top, left, ch, cw = ENDOMAPPER_DENSE_FIRST
+    if h < ch or w < left + cw:
+        raise ValueError(f"Image too small for Endomapper dense crop: {(h, w)}.")
+    return left + (cw - tw) // 2, top + (ch - th) // 2, tw, th
+
+
 class ImagePreprocessor:
     default_conf = DEFAULT_CONF
 
@@ -73,11 +153,21 @@ class ImagePreprocessor:
         size = h, w
         if self.conf["resize"] is not None:
             interpolation = interpolation or self.conf["interpolation"]
-            if interpolation != "bilinear":
-                raise NotImplementedError(f"interpolation {interpolation!r}: only 'bilinear' is built on the GPU path")
+            if interpolation not in ("bilinear", *RESAMPLE_MODES):
+                raise NotImplementedError(f"interpolation {interpolation!r}: 'bilinear', 'nearest' and 'area' are built "
+                                          "on the GPU path")
             size = self.get_new_image_size(h, w)
+            if interpolation in RESAMPLE_MODES:
+                if self.conf["align_corners"] is not None:  # F.interpolate's own refusal
+                    raise ValueError("align_corners option can only be set with the interpolating modes: linear | "
+                                     f"bilinear | bicubic | trilinear (got {interpolation!r})")
+                if interpolation == "area" and self.conf["antialias"] and downscales((h, w), size):
+                    raise NotImplementedError("interpolation 'area' with antialias=True on a down-scale is not built "
+                                              "(the reference's own 'area' configuration sets antialias: False)")
+                if tuple(size) != (h, w) or u8:
+                    img = resample(img, size, interpolation, antialias=self.conf["antialias"])
             # kornia.resize returns its input unchanged when the size already matches
-            if tuple(size) != (h, w) or u8:
+            elif tuple(size) != (h, w) or u8:
                 img = resize(img, size, self.conf["align_corners"], self.conf["antialias"])
         elif u8:
             img = resize(img, size, None, False)  # conversion only
@@ -95,6 +185,15 @@ class ImagePreprocessor:
         else:
             data["image"] = img
         return data
+
+    def crop_endomapper_dense(self, img):
+        """The fixed Endomapper-dense crop of a [..., H, W] tensor (image.py:77-103) -> (cropped view, (left, top));
+        `endomapper_dense_window` gives the same crop as a window for `resample`."""
+        h, w = int(img.shape[-2]), int(img.shape[-1])
+        left, top, cw, ch = endomapper_dense_window(h, w)
+        if (cw, ch) == (w, h):
+            return img, (0.0, 0.0)
+        return img[..., top: top + ch, left: left + cw], (float(left), float(top))
 
     def get_new_image_size(self, h: int, w: int):
         """Target (height, width) for `resize` = edge length on the side named by `side` (image.py:105-132):

@@ -717,6 +717,31 @@ int gfc_eval_matches_epipolar(const float* kp0, const float* kp1, const int64_t*
 int gfc_preprocess_resize(const void* src, int src_is_u8_hwc, int bgr, int B, int C, int H, int W, float* dst, int OH,
                           int OW, int align_corners, int antialias, void* stream);
 
+/* Crop + nearest / area resample in one launch: what the posed_images reader does to depth maps, specular masks and
+ * images (gluefactory/datasets/posed_images.py:219-269: crop, then ImagePreprocessor with "nearest" / "area").
+ * src_kind: GFC_RS_F32_CHW B planar CxHxW fp32 images; GFC_RS_U8_HWC B interleaved HxWxC byte images converted like
+ * numpy_image_to_torch; GFC_RS_U8_PLANE B byte planes HxW, non-zero = 1; GFC_RS_BITS B bit planes as numpy.packbits
+ * makes them of the flattened HxW mask (bit k = y W + x is (byte[k >> 3] >> (7 - (k & 7))) & 1, ceil(H W / 8) bytes per
+ * plane; posed_images.py:75-82).  The two mask kinds need C = 1.  (left, top, cw, ch): the crop window inside HxW;
+ * everything else sees only the window (GFC_ERR_INVALID when it leaves the plane).  value_scale multiplies every
+ * source value at load (the per-image depth scale, posed_images.py:235-236).
+ * mode GFC_RS_NEAREST: torch's legacy "nearest", source index min((int)floorf(dst * ((float)in / (float)out)), in - 1);
+ * with antialias != 0 and a down-scaling axis the window is blurred first as gfc_preprocess_resize blurs (same sigma,
+ * kernel size, weights and reflect border -- at the WINDOW's edges -- same GFC_ERR_UNSUPPORTED / GFC_ERR_INVALID).
+ * mode GFC_RS_AREA: adaptive average pooling, box [floor(i in / out), ceil((i + 1) in / out)) per axis, fp32 sum / count;
+ * GFC_ERR_UNSUPPORTED together with a blur.
+ * dst: fp32 [B,C,OH,OW] for the two image kinds, and valid (optional, same shape) = dst > 0 ? 1.f : 0.f
+ * (posed_images.py:249); uint8 [B,1,OH,OW] holding value > 0.5 for the two mask kinds (valid must be NULL). */
+#define GFC_RS_F32_CHW 0
+#define GFC_RS_U8_HWC 1
+#define GFC_RS_U8_PLANE 2
+#define GFC_RS_BITS 3
+#define GFC_RS_NEAREST 0
+#define GFC_RS_AREA 1
+int gfc_preprocess_resample(const void* src, int src_kind, int B, int C, int H, int W, int left, int top, int cw, int ch,
+                            int mode, int antialias, float value_scale, void* dst, float* valid, int OH, int OW,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
