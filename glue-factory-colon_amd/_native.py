@@ -58,6 +58,18 @@ class LgParams(Structure):
                 + [(n, c_void_p * GFC_LG_MAX_LAYERS) for n in _LG_ARRAYS_F16])
 
 
+GFC_SG_MAX_LAYERS = 32
+_SG_ARRAYS = ["wqkv", "bqkv", "merge_w", "merge_b", "mlp0_w", "mlp0_b", "mlp_scale", "mlp_shift", "mlp1_w", "mlp1_b"]
+
+
+class SgParams(Structure):
+    _fields_ = ([("n_layers", c_int), ("use_scores", c_int), ("cross", c_int * GFC_SG_MAX_LAYERS),
+                 ("kenc_w", c_void_p * 5), ("kenc_b", c_void_p * 5), ("kenc_scale", c_void_p * 4),
+                 ("kenc_shift", c_void_p * 4)]
+                + [(n, c_void_p * GFC_SG_MAX_LAYERS) for n in _SG_ARRAYS]
+                + [("final_proj_w", c_void_p), ("final_proj_b", c_void_p), ("bin_score", c_float)])
+
+
 _lib = None
 
 # name -> (restype, argtypes); every symbol declared in include/gfc_amd.h
@@ -174,6 +186,15 @@ SIGNATURES = {
     "gfc_lg_adaptive_step": (c_int, [POINTER(LgParams), c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 3
                              + [c_int] * 3 + [c_float, c_float, c_double, c_int, c_int] + [c_void_p] * 5 + [c_int]
                              + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "gfc_sg_keypoint_encoder_workspace_bytes": (c_size_t, [c_int]),
+    "gfc_sg_keypoint_encoder": (c_int, [POINTER(SgParams), c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+    "gfc_sg_mlp": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 8 + [c_int, c_int, c_void_p]),
+    "gfc_sg_sinkhorn_workspace_bytes": (c_size_t, [c_int] * 3),
+    "gfc_sg_sinkhorn": (c_int, [c_void_p, c_float] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gfc_sg_workspace_bytes": (c_size_t, [c_int] * 3),
+    "gfc_sg_forward": (c_int, [POINTER(SgParams)] + [c_void_p] * 8 + [c_int] * 4 + [c_float] + [c_void_p] * 8
+                       + [c_size_t, c_void_p]),
 }
 
 

@@ -494,7 +494,10 @@ __device__ __forceinline__ float halfwave_transpose_sum32(const float (&x)[32], 
 // (ascending 8-deep groups, k = 4h + s inside a group), same epilogue association (residual + (acc + bias)): the
 // results are bit-identical to the two-kernel path.  The [M,512] hidden activation never exists in HBM.
 #define FF_HLD 148  // hidden-chunk row stride in floats (= 20 mod 64: the conflict-free ds_read_b128 pattern of the K-tile rows)
-template <bool MLP>
+// BNRELU = true (with MLP): the SuperGlue propagation MLP.  The epilogue between the two GEMMs is an eval-mode BatchNorm
+// folded to a per-column scale / shift (gamma / beta carry them) followed by ReLU instead of LayerNorm + GELU: no row
+// statistics, everything else -- tiles, K order, the hidden hand-over through LDS, the residual epilogue -- is shared.
+template <bool MLP, bool BNRELU = false>
 __global__ __launch_bounds__(512, 2) void gemm_rows512_ln_gelu_kernel(GemmArgs g, const float* __restrict__ gamma,
                                                                       const float* __restrict__ beta,
                                                                       const float* __restrict__ W3, int ldw3,
@@ -640,68 +643,80 @@ __global__ __launch_bounds__(512, 2) void gemm_rows512_ln_gelu_kernel(GemmArgs g
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mt][nt][r] += bi[nt];
-  // row of value index v = 16 mt + r held by this lane after the butterfly
-  const int vb = ((l31 & 1) << 4) | ((l31 & 2) << 2) | (l31 & 4) | ((l31 & 8) >> 2) | ((l31 & 16) >> 4);
-  const int my_row = wm * 64 + (vb >> 4) * 32 + acc_row(vb & 15, h);
-  float mu[2][16];
-  {
-    float x[32];
+  bool full_rows;  // (assigned where the LayerNorm path always computed it: its instantiations stay instruction-identical)
+  if constexpr (BNRELU) {
+    static_assert(MLP, "the BatchNorm + ReLU epilogue only exists in the fused two-GEMM form");
+    full_rows = m0 + BM <= g.M;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        x[mt * 16 + r] = (acc[mt][0][r] + acc[mt][1][r]) + (acc[mt][2][r] + acc[mt][3][r]);
-    red[wn * BM + my_row] = halfwave_transpose_sum32(x, l31);
-  }
-  __syncthreads();
-  if (tid < BM) stat[tid] = ((red[tid] + red[BM + tid]) + (red[2 * BM + tid] + red[3 * BM + tid])) * (1.f / 512.f);
-  __syncthreads();
+      for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
+        for (int r = 0; r < 16; ++r) acc[mt][nt][r] = fmaxf(acc[mt][nt][r] * ga[nt] + be[nt], 0.f);
+  } else {
+    // row of value index v = 16 mt + r held by this lane after the butterfly
+    const int vb = ((l31 & 1) << 4) | ((l31 & 2) << 2) | (l31 & 4) | ((l31 & 8) >> 2) | ((l31 & 16) >> 4);
+    const int my_row = wm * 64 + (vb >> 4) * 32 + acc_row(vb & 15, h);
+    float mu[2][16];
+    {
+      float x[32];
 #pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-      const float4 m4 = *reinterpret_cast<const float4*>(stat + wm * 64 + mt * 32 + 8 * gq + 4 * h);
-      mu[mt][4 * gq] = m4.x; mu[mt][4 * gq + 1] = m4.y; mu[mt][4 * gq + 2] = m4.z; mu[mt][4 * gq + 3] = m4.w;
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          x[mt * 16 + r] = (acc[mt][0][r] + acc[mt][1][r]) + (acc[mt][2][r] + acc[mt][3][r]);
+      red[wn * BM + my_row] = halfwave_transpose_sum32(x, l31);
     }
-  {
-    float x[32];
+    __syncthreads();
+    if (tid < BM) stat[tid] = ((red[tid] + red[BM + tid]) + (red[2 * BM + tid] + red[3 * BM + tid])) * (1.f / 512.f);
+    __syncthreads();
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d0 = acc[mt][0][r] - mu[mt][r], d1 = acc[mt][1][r] - mu[mt][r];
-        const float d2 = acc[mt][2][r] - mu[mt][r], d3 = acc[mt][3][r] - mu[mt][r];
-        x[mt * 16 + r] = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+      for (int gq = 0; gq < 4; ++gq) {
+        const float4 m4 = *reinterpret_cast<const float4*>(stat + wm * 64 + mt * 32 + 8 * gq + 4 * h);
+        mu[mt][4 * gq] = m4.x; mu[mt][4 * gq + 1] = m4.y; mu[mt][4 * gq + 2] = m4.z; mu[mt][4 * gq + 3] = m4.w;
       }
-    red[wn * BM + my_row] = halfwave_transpose_sum32(x, l31);  // `red` was last read before the previous barrier
-  }
-  __syncthreads();
-  if (tid < BM) {
-    const float var = ((red[tid] + red[BM + tid]) + (red[2 * BM + tid] + red[3 * BM + tid])) * (1.f / 512.f);
-    stat[BM + tid] = 1.f / sqrtf(var + 1e-5f);
-  }
-  __syncthreads();
-  if constexpr (!MLP) GEMM_STAMP(3);  // statistics done
-  const bool full_rows = m0 + BM <= g.M;
+    {
+      float x[32];
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
+      for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-      const float4 r4 = *reinterpret_cast<const float4*>(stat + BM + wm * 64 + mt * 32 + 8 * gq + 4 * h);
-      const float rs[4] = {r4.x, r4.y, r4.z, r4.w};
+        for (int r = 0; r < 16; ++r) {
+          const float d0 = acc[mt][0][r] - mu[mt][r], d1 = acc[mt][1][r] - mu[mt][r];
+          const float d2 = acc[mt][2][r] - mu[mt][r], d3 = acc[mt][3][r] - mu[mt][r];
+          x[mt * 16 + r] = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        }
+      red[wn * BM + my_row] = halfwave_transpose_sum32(x, l31);  // `red` was last read before the previous barrier
+    }
+    __syncthreads();
+    if (tid < BM) {
+      const float var = ((red[tid] + red[BM + tid]) + (red[2 * BM + tid] + red[3 * BM + tid])) * (1.f / 512.f);
+      stat[BM + tid] = 1.f / sqrtf(var + 1e-5f);
+    }
+    __syncthreads();
+    if constexpr (!MLP) GEMM_STAMP(3);  // statistics done
+    full_rows = m0 + BM <= g.M;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = 4 * gq + j;
-        const int row = m0 + wm * 64 + mt * 32 + acc_row(r, h);
-        if constexpr (MLP) {  // the activated value replaces the pre-activation in its accumulator register
+    for (int mt = 0; mt < 2; ++mt) {
 #pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
-            acc[mt][nt][r] = gfc_gelu((acc[mt][nt][r] - mu[mt][r]) * rs[j] * ga[nt] + be[nt]);
-        } else if (full_rows || row < g.M) {  // full_rows: workgroup-uniform, no per-row predicate blocks
-          float* yp = g.Y + (size_t)row * g.ldy + wn * 128 + l31;
+      for (int gq = 0; gq < 4; ++gq) {
+        const float4 r4 = *reinterpret_cast<const float4*>(stat + BM + wm * 64 + mt * 32 + 8 * gq + 4 * h);
+        const float rs[4] = {r4.x, r4.y, r4.z, r4.w};
 #pragma unroll
-          for (int nt = 0; nt < 4; ++nt) {
-            yp[nt * 32] = gfc_gelu((acc[mt][nt][r] - mu[mt][r]) * rs[j] * ga[nt] + be[nt]);
+        for (int j = 0; j < 4; ++j) {
+          const int r = 4 * gq + j;
+          const int row = m0 + wm * 64 + mt * 32 + acc_row(r, h);
+          if constexpr (MLP) {  // the activated value replaces the pre-activation in its accumulator register
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+              acc[mt][nt][r] = gfc_gelu((acc[mt][nt][r] - mu[mt][r]) * rs[j] * ga[nt] + be[nt]);
+          } else if (full_rows || row < g.M) {  // full_rows: workgroup-uniform, no per-row predicate blocks
+            float* yp = g.Y + (size_t)row * g.ldy + wn * 128 + l31;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+              yp[nt * 32] = gfc_gelu((acc[mt][nt][r] - mu[mt][r]) * rs[j] * ga[nt] + be[nt]);
+            }
           }
         }
       }
@@ -821,6 +836,27 @@ extern "C" int gfc_ffn_fused(const float* A0, int lda0, int K0, const float* A1,
 #endif
   hipLaunchKernelGGL(gemm_rows512_ln_gelu_kernel<true>, dim3((M + 127) / 128), dim3(512), lds, (hipStream_t)stream, g,
                      gamma, beta, W3, ldw3, b3);
+  GFC_LAUNCH_CHECK();
+  return GFC_OK;
+}
+
+// SuperGlue's propagation MLP (superglue.py:140-149 with the residual of :175) on the same row-owning tiles:
+//   Y[M,256] = residual + ( ReLU( ([A0 | A1] * W0[512,512]^T + b0) * scale + shift ) * W1[256,512]^T + b1 ).
+extern "C" int gfc_sg_mlp(const float* A0, int lda0, const float* A1, int lda1, const float* W0, const float* b0,
+                          const float* scale, const float* shift, const float* W1, const float* b1,
+                          const float* residual, float* Y, int ldy, int M, void* stream) {
+  if (!A0 || !A1 || !W0 || !scale || !shift || !W1 || !Y || M <= 0) return GFC_ERR_INVALID;
+  if (lda0 % 4 || lda1 % 4 || lda0 < 256 || lda1 < 256 || ldy < 256) return GFC_ERR_INVALID;
+  GemmArgs g = {};
+  g.A0 = A0; g.A1 = A1; g.W = W0; g.bias = b0; g.residual = residual; g.Y = Y;
+  g.lda0 = lda0; g.lda1 = lda1; g.ldw = GW_BN; g.ldy = ldy;
+  g.K0 = 256; g.K1 = 256; g.M = M; g.N = GW_BN; g.alpha = 1.f;
+  constexpr size_t k1 = (size_t)2 * (128 + GW_BN) * 20, k2 = (size_t)128 * FF_HLD + (size_t)2 * 256 * 20;
+  constexpr size_t lds = (k1 > k2 ? k1 : k2) * sizeof(float);
+  static std::atomic<unsigned long long> lds_ok{0};
+  gfc_allow_dynamic_lds((const void*)gemm_rows512_ln_gelu_kernel<true, true>, lds, lds_ok);
+  hipLaunchKernelGGL((gemm_rows512_ln_gelu_kernel<true, true>), dim3((M + 127) / 128), dim3(512), lds,
+                     (hipStream_t)stream, g, scale, shift, W1, GW_BN, b1);
   GFC_LAUNCH_CHECK();
   return GFC_OK;
 }

@@ -18,6 +18,8 @@ ALIASES = {
     "lightglue_pretrained": "lightglue_pretrained",
     "matchers.nearest_neighbor_matcher": "nearest_neighbor_matcher",
     "nearest_neighbor_matcher": "nearest_neighbor_matcher",
+    "gluefactory_nonfree.superglue": "superglue",
+    "superglue": "superglue",
     "extractors.disk_kornia": "disk_kornia",
     "disk_kornia": "disk_kornia",
     "gluefactory.models.extractors.disk_kornia": "disk_kornia",

@@ -12,6 +12,7 @@ Key layouts follow the reference:
   SuperPoint-open   gluefactory/models/extractors/superpoint_open.py:61-118
   SuperPoint (off.) gluefactory_nonfree/superpoint.py:183-200
   LightGlue         gluefactory/models/matchers/lightglue.py:349-408
+  SuperGlue         gluefactory_nonfree/superglue.py:249-260
 """
 import math
 import os
@@ -161,6 +162,53 @@ def lightglue_state_dict(seed: int = 0, input_dim=256, descriptor_dim=256, n_lay
         sd[p + ".final_proj.bias"] = torch.zeros(d)
     for i in range(n_layers - 1):
         _linear(sd, f"token_confidence.{i}.token.0", d, 1, seed)
+    return sd
+
+
+def _conv1d(sd, prefix, cin, cout, seed, gain=1.0, bias_std=0.02):
+    sd[prefix + ".weight"] = _randn(prefix + ".weight", seed, (cout, cin, 1), gain / math.sqrt(cin))
+    sd[prefix + ".bias"] = _randn(prefix + ".bias", seed, (cout,), bias_std)
+
+
+def _bn1d(sd, prefix, c, seed):
+    """BatchNorm1d with weights near 1 and running statistics far enough from (0, 1) that a wrong fold shows."""
+    sd[prefix + ".weight"] = _rand(prefix + ".weight", seed, (c,), 0.9, 1.1)
+    sd[prefix + ".bias"] = _randn(prefix + ".bias", seed, (c,), 0.05)
+    sd[prefix + ".running_mean"] = _randn(prefix + ".running_mean", seed, (c,), 0.3, 0.2)
+    sd[prefix + ".running_var"] = _rand(prefix + ".running_var", seed, (c,), 0.4, 2.5)
+    sd[prefix + ".num_batches_tracked"] = torch.tensor(1, dtype=torch.long)
+
+
+def superglue_state_dict(seed: int = 0, descriptor_dim=256, keypoint_encoder=(32, 64, 128, 256), n_layers=18,
+                         use_scores=True, residual_gain=0.05, encoder_gain=0.1, assign_gain=12.0, qk_gain=8.0):
+    """Key names of gluefactory_nonfree/superglue.py:249-260 (`kenc.encoder.{0,1,3,4,...,12}`,
+    `gnn.layers.{i}.attn.{merge,proj.{0,1,2}}`, `gnn.layers.{i}.mlp.{0,1,3}`, `final_proj`, `bin_score`), Conv1d
+    weights [cout, cin, 1].
+
+    Gains are chosen so that the random network still matches planted correspondences: small gains on the residual
+    branches (the last MLP layer of every propagation block and the last encoder layer) keep corresponding descriptors
+    aligned through the layers, a large near-orthogonal `final_proj` makes the optimal transport peaky, the query /
+    key projections are large enough for the attention not to be uniform, and `bin_score` is 1."""
+    d = descriptor_dim
+    sd = OrderedDict()
+    chans = [3 if use_scores else 2, *keypoint_encoder, d]
+    for i in range(1, len(chans)):
+        last = i == len(chans) - 1
+        _conv1d(sd, f"kenc.encoder.{3 * (i - 1)}", chans[i - 1], chans[i], seed,
+                gain=encoder_gain if last else math.sqrt(2.0))
+        if not last:
+            _bn1d(sd, f"kenc.encoder.{3 * (i - 1) + 1}", chans[i], seed)
+    for i in range(n_layers):
+        p = f"gnn.layers.{i}"
+        _conv1d(sd, p + ".attn.merge", d, d, seed)
+        for j in range(3):
+            _conv1d(sd, p + f".attn.proj.{j}", d, d, seed, gain=qk_gain if j < 2 else 1.0)
+        _conv1d(sd, p + ".mlp.0", 2 * d, 2 * d, seed, gain=math.sqrt(2.0))
+        _bn1d(sd, p + ".mlp.1", 2 * d, seed)
+        _conv1d(sd, p + ".mlp.3", 2 * d, d, seed, gain=residual_gain)
+    sd["final_proj.weight"] = _randn("final_proj.weight", seed, (d, d, 1), assign_gain / math.sqrt(d))
+    sd["final_proj.bias"] = torch.zeros(d)
+    sd["bin_score"] = torch.tensor(1.0)
     return sd
 
 

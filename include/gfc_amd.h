@@ -742,6 +742,83 @@ int gfc_preprocess_resample(const void* src, int src_kind, int B, int C, int H, 
                             int mode, int antialias, float value_scale, void* dst, float* valid, int OH, int OW,
                             void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * SuperGlue matcher (gluefactory_nonfree/superglue.py:268-322, inference path).  All fp32; rows are row-major
+ * [rows,256] where the reference is channel-first Conv1d on [B,256,N]; a batch is packed as LightGlue's: the side-0
+ * rows of every pair, then the side-1 rows.
+ * Head order: the reference splits heads with view(b, dim, h, -1) (superglue.py:133), so channel c belongs to head
+ * c % 4 at position c / 4 -- interleaved, not head-major.  The caller permutes the rows of the three proj weights
+ * (packed row h*64 + d <- state-dict row d*4 + h) and the columns of merge the same way, so that the kernels see
+ * head-major 64-wide columns.
+ * ---------------------------------------------------------------------------------- */
+#define GFC_SG_MAX_LAYERS 32
+typedef struct {
+  int n_layers;                  /* len(GNN_layers), 18 */
+  int use_scores;                /* 1: the encoder reads [x, y, score]; 0: [x, y] */
+  int cross[GFC_SG_MAX_LAYERS];  /* per layer: 0 = "self", 1 = "cross" (superglue.py:179-185) */
+  /* kenc.encoder (superglue.py:98-111): layers 0..3 TRANSPOSED to [cin][cout] (cin = 3 or 2, 32, 64, 128) with their
+   * eval-mode BatchNorm1d (eps 1e-5) folded to y * scale + shift; layer 4 as stored, [256][256], no BatchNorm. */
+  const float* kenc_w[5];
+  const float* kenc_b[5];
+  const float* kenc_scale[4];
+  const float* kenc_shift[4];
+  /* gnn.layers.{l}: attn.proj.{0,1,2} stacked to [768][256] = [q | k | v], each head-major; attn.merge [256][256] with
+   * head-major columns; mlp.0 [512][512] with mlp.1 (BatchNorm1d) folded to scale / shift [512]; mlp.3 [256][512]. */
+  const float* wqkv[GFC_SG_MAX_LAYERS];
+  const float* bqkv[GFC_SG_MAX_LAYERS];
+  const float* merge_w[GFC_SG_MAX_LAYERS];
+  const float* merge_b[GFC_SG_MAX_LAYERS];
+  const float* mlp0_w[GFC_SG_MAX_LAYERS];
+  const float* mlp0_b[GFC_SG_MAX_LAYERS];
+  const float* mlp_scale[GFC_SG_MAX_LAYERS];
+  const float* mlp_shift[GFC_SG_MAX_LAYERS];
+  const float* mlp1_w[GFC_SG_MAX_LAYERS];
+  const float* mlp1_b[GFC_SG_MAX_LAYERS];
+  const float* final_proj_w; /* [256][256] */
+  const float* final_proj_b;
+  float bin_score;
+} gfc_sg_params;
+
+/* desc [B*n,256] += kenc([x, y, score]) in place (superglue.py:85-111,289-290).  kpts [B,n,2] pixel coordinates are
+ * normalised per image with sizes [B,2] = (w, h): (k - size/2) / (0.7 max(w, h)); scores [B,n], NULL exactly when
+ * p->use_scores == 0.  Layers 3 -> 32 -> 64 -> 128 -> 256 run in one kernel with the activations in LDS, the last
+ * 256 -> 256 layer and the addition on the matrix pipe.  ws: [B*n,256] hidden rows.  Only the kenc_* fields of p are read. */
+size_t gfc_sg_keypoint_encoder_workspace_bytes(int rows);
+int gfc_sg_keypoint_encoder(const gfc_sg_params* p, const float* kpts, const float* scores, const float* sizes, int B,
+                            int n, float* desc, void* ws, size_t ws_bytes, void* stream);
+
+/* The propagation MLP with its residual in one kernel (superglue.py:140-149, the desc + delta of :175):
+ *   Y[M,256] = residual + ( ReLU( ([A0 | A1] * W0[512,512]^T + b0) * scale + shift ) * W1[256,512]^T + b1 ),
+ * A0, A1 [M,256] (row strides lda0, lda1, multiples of 4), scale / shift [512] = the folded BatchNorm1d.  The 512-wide
+ * hidden tile stays on chip (the tiles of the fused LightGlue FFN kernel).  residual (nullable) and Y share ldy and may
+ * alias; b0, b1 nullable. */
+int gfc_sg_mlp(const float* A0, int lda0, const float* A1, int lda1, const float* W0, const float* b0,
+               const float* scale, const float* shift, const float* W1, const float* b1, const float* residual, float* Y,
+               int ldy, int M, void* stream);
+
+/* log_optimal_transport + log_sinkhorn_iterations (superglue.py:188-216): from cost [B,M,N] and bin_score, `iters`
+ * iterations of u = log_mu - LSE_j(Z + v), v = log_nu - LSE_i(Z + u) on the augmented [M+1,N+1] matrix in the log
+ * domain (maximum subtracted), out [B,M+1,N+1] = Z + u + v - norm.  A workgroup holds a block of whole rows in LDS:
+ * the matrix is read once per iteration; the two half-steps are separate launches in stream order (no workgroup waits
+ * for another).  GFC_ERR_UNSUPPORTED when one row of N + 1 floats and v do not fit in 160 KB of LDS. */
+size_t gfc_sg_sinkhorn_workspace_bytes(int B, int M, int N);
+int gfc_sg_sinkhorn(const float* cost, float bin_score, int B, int M, int N, int iters, float* out, void* ws,
+                    size_t ws_bytes, void* stream);
+
+/* The whole matcher for B pairs of (M, N) key points: encoder, n_layers x (256 -> 768 projection, attention with
+ * scale 1/8 -- self: problems (i, i); cross: (0 <- 1) and (1 <- 0) --, merge, MLP), final_proj, cost = mdesc0 .
+ * mdesc1^T / 16, Sinkhorn, the mutual-argmax filter LightGlue uses (superglue.py:303-313 is the same rule).
+ * kpts0 [B,M,2], kpts1 [B,N,2] pixels; scores0 [B,M], scores1 [B,N] (NULL when !use_scores); desc0 [B,M,256], desc1
+ * [B,N,256] (read-only); size0 / size1 [B,2] = (w, h).  Outputs: sinkhorn_cost [B,M,N], log_assignment [B,M+1,N+1],
+ * m0 [B,M] / m1 [B,N] int64, ms0 / ms1; desc_taps (nullable) [4][B*M + B*N, 256]: the rows after the encoder, layer 0,
+ * layer 1 (slots 1, 2 only when those layers exist) and the last layer. */
+size_t gfc_sg_workspace_bytes(int B, int M, int N);
+int gfc_sg_forward(const gfc_sg_params* p, const float* kpts0, const float* kpts1, const float* scores0,
+                   const float* scores1, const float* desc0, const float* desc1, const float* size0, const float* size1,
+                   int B, int M, int N, int iters, float threshold, float* sinkhorn_cost, float* log_assignment,
+                   int64_t* m0, int64_t* m1, float* ms0, float* ms1, float* desc_taps, void* ws, size_t ws_bytes,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
