@@ -128,6 +128,8 @@ SIGNATURES = {
     "gfc_nn_workspace_bytes": (c_size_t, [c_int] * 3),
     "gfc_nn_match": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_int] + [c_void_p] * 7
                      + [c_size_t, c_void_p]),
+    "gfc_eval_matches_homography_lds_bytes": (c_size_t, [c_int] * 2),
+    "gfc_eval_matches_depth_lds_bytes": (c_size_t, [c_int] * 2),
     "gfc_eval_matches_homography": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float] * 2 + [c_void_p] * 3),
     "gfc_pack_conv3x3_wino": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "gfc_conv3x3_wino": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),

@@ -6,6 +6,22 @@
 
 #define EM_THREADS 256
 
+// LDS of the two match-metric kernels (eval_metrics.hip, eval_pose.hip).  A workgroup of this part has 160 KB in all:
+// the dynamic arrays (every key point of the pair) PLUS the kernel's static variables.  Each kernel declares ALL its
+// static LDS as one struct, so that the size the launcher counts is tied to the declaration; the dynamic array is
+// 16-byte aligned and follows it.  A pair is refused (nothing launched) exactly when the sum exceeds the limit, and the
+// launch asks for the dynamic part only.
+constexpr size_t EVAL_LDS_LIMIT = 160 * 1024;
+constexpr size_t eval_static_lds(size_t bytes) { return (bytes + 15) / 16 * 16; }
+struct EmStaticLds { float acc7[7]; };  // eval_matches_kernel: the seven block sums
+struct EdStaticLds { float acc[9]; };   // eval_matches_depth_kernel: the nine block sums
+constexpr size_t EM_STATIC_LDS = eval_static_lds(sizeof(EmStaticLds));
+constexpr size_t ED_STATIC_LDS = eval_static_lds(sizeof(EdStaticLds));
+// k01, a0 [M][2], k10, a1 [N][2] floats and min1 [N] ints
+inline size_t em_dynamic_lds(int M, int N) { return (size_t)16 * M + (size_t)20 * N; }
+// a0, k01 [M][2], a1, k10 [N][2], best1 [N] floats and flag0, min0 [M], flag1, min1 [N] ints
+inline size_t ed_dynamic_lds(int M, int N) { return (size_t)24 * M + (size_t)28 * N; }
+
 __device__ __forceinline__ void warp_pt(const float* Hm, float x, float y, float eps, float& ox, float& oy) {
   // to_homogeneous(p) @ H^T then division by (w + eps): einsum order x*H[r][0] + y*H[r][1] + 1*H[r][2]
   const float wx = x * Hm[0] + y * Hm[1] + Hm[2];

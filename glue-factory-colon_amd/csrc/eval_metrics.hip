@@ -20,7 +20,8 @@ __global__ __launch_bounds__(EM_THREADS) void eval_matches_kernel(const float* _
   float* a0 = k10 + 2 * N;      // [M][2] local copy of kp0
   float* a1 = a0 + 2 * M;       // [N][2] local copy of kp1
   int* min1 = reinterpret_cast<int*>(a1 + 2 * N);  // [N] argmin over rows
-  __shared__ float red[6];
+  __shared__ EmStaticLds st;
+  float* acc7 = st.acc7;
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* p0 = kp0 + (size_t)b * M * 2;
   const float* p1 = kp1 + (size_t)b * N * 2;
@@ -28,7 +29,6 @@ __global__ __launch_bounds__(EM_THREADS) void eval_matches_kernel(const float* _
   float Hm[9], Hi[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) { Hm[i] = H[b * 9 + i]; Hi[i] = Hinv[b * 9 + i]; }
-  if (tid < 6) red[tid] = 0.f;
   for (int i = tid; i < M; i += EM_THREADS) {
     const float x = p0[2 * i], y = p0[2 * i + 1];
     a0[2 * i] = x; a0[2 * i + 1] = y;
@@ -74,7 +74,8 @@ __global__ __launch_bounds__(EM_THREADS) void eval_matches_kernel(const float* _
     if (N == 0) gt = -1;
     if (gt_m0_out) gt_m0_out[(size_t)b * M + i] = gt;
     const long long m = mm[i];
-    if (m > -1) {
+    if (m > -1) s_match += 1.f;
+    if (m > -1 && m < N) {  // an index >= N names no key point: counted, its error infinite, never read
       // symmetric transfer error of the predicted match (plain division, homography.py:314-323)
       float ax, ay, bx, by;
       warp_pt(Hm, x0, y0, 0.f, ax, ay);
@@ -83,7 +84,6 @@ __global__ __launch_bounds__(EM_THREADS) void eval_matches_kernel(const float* _
       const float e01 = sqrtf((ax - x1) * (ax - x1) + (ay - y1) * (ay - y1));
       const float e10 = sqrtf((bx - x0) * (bx - x0) + (by - y0) * (by - y0));
       const float err = (e01 + e10) / 2.f;
-      s_match += 1.f;
       s_p1 += err < 1.f ? 1.f : 0.f;
       s_p3 += err < 3.f ? 1.f : 0.f;
     }
@@ -92,7 +92,6 @@ __global__ __launch_bounds__(EM_THREADS) void eval_matches_kernel(const float* _
   }
   // block reduction (7 sums): wave shuffle then LDS atomics
   float v[7] = {s_match, s_p1, s_p3, s_gt, s_rec, s_mask, s_prec};
-  __shared__ float acc7[7];
   if (tid < 7) acc7[tid] = 0.f;
   __syncthreads();
 #pragma unroll
@@ -113,14 +112,24 @@ __global__ __launch_bounds__(EM_THREADS) void eval_matches_kernel(const float* _
   }
 }
 
+extern "C" size_t gfc_eval_matches_homography_lds_bytes(int M, int N) {
+  return (M < 0 || N < 0) ? 0 : em_dynamic_lds(M, N) + EM_STATIC_LDS;
+}
+
 extern "C" int gfc_eval_matches_homography(const float* kp0, const float* kp1, const int64_t* m0, const float* H,
                                            const float* Hinv, int B, int M, int N, float pos_th, float neg_th,
                                            float* out, int64_t* gt_m0_out, void* stream) {
-  if (!kp0 || !kp1 || !m0 || !H || !Hinv || !out || B <= 0 || M < 0 || N < 0) return GFC_ERR_INVALID;
-  const size_t lds = (size_t)(4 * (M + N)) * sizeof(float) + (size_t)N * sizeof(int) + 64;
-  if (lds > 160 * 1024) return GFC_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)eval_matches_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  // an empty side has no array to point at: its pointers may be NULL
+  if (!H || !Hinv || !out || B <= 0 || M < 0 || N < 0 || (M > 0 && (!kp0 || !m0)) || (N > 0 && !kp1))
+    return GFC_ERR_INVALID;
+  const size_t lds = em_dynamic_lds(M, N);  // the dynamic arrays only: the launch adds the static ones itself
+  if (lds + EM_STATIC_LDS > EVAL_LDS_LIMIT) return GFC_ERR_UNSUPPORTED;
+  static std::atomic<unsigned long long> lds_ok{0};
+  if (lds > 64 * 1024 &&
+      !gfc_allow_dynamic_lds((const void*)eval_matches_kernel, EVAL_LDS_LIMIT - EM_STATIC_LDS, lds_ok)) {
+    (void)hipGetLastError();
+    return GFC_ERR_LAUNCH;
+  }
   hipLaunchKernelGGL(eval_matches_kernel, dim3(B), dim3(EM_THREADS), lds, (hipStream_t)stream, kp0, kp1,
                      (const long long*)m0, H, Hinv, M, N, pos_th, neg_th, out, (long long*)gt_m0_out);
   GFC_LAUNCH_CHECK();
@@ -196,11 +205,10 @@ __global__ __launch_bounds__(EM_THREADS) void dlt_kernel(const float* __restrict
     bool finite = true;
     for (int r = 0; r < 9; ++r) { Hf[r] = (float)(f[r] / den); finite = finite && isfinite(Hf[r]); }
     float err = INFINITY;
-    if (finite) {
-      err = corner_error(Hf, Hgt + b * 9, size0[b * 2], size0[b * 2 + 1]);
-    } else {
+    if (finite) err = corner_error(Hf, Hgt + b * 9, size0[b * 2], size0[b * 2 + 1]);
+    // an estimate that sends a corner to infinity (degenerate input) is no estimate: err = +inf exactly where H = +inf
+    if (!isfinite(err))
       for (int r = 0; r < 9; ++r) Hf[r] = INFINITY;
-    }
     for (int r = 0; r < 9; ++r) Hout[b * 9 + r] = Hf[r];
     err_out[b] = err;
   }

@@ -52,7 +52,8 @@ __global__ __launch_bounds__(EM_THREADS) void eval_matches_depth_kernel(
   int* flag1 = flag0 + M;                               // [N]; after the column sweep also bit 8: negative
   int* min0 = flag1 + N;                                // [M] argmin over columns
   int* min1 = min0 + M;                                 // [N] argmin over rows
-  __shared__ float acc[9];
+  __shared__ EdStaticLds st;
+  float* acc = st.acc;
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* p0 = kp0 + (size_t)b * M * 2;
   const float* p1 = kp1 + (size_t)b * N * 2;
@@ -231,6 +232,10 @@ extern "C" int gfc_eval_pose_project(const float* kp, const float* depth_i, cons
   return GFC_OK;
 }
 
+extern "C" size_t gfc_eval_matches_depth_lds_bytes(int M, int N) {
+  return (M < 0 || N < 0) ? 0 : ed_dynamic_lds(M, N) + ED_STATIC_LDS;
+}
+
 extern "C" int gfc_eval_matches_depth(const float* kp0, const float* kp1, const int64_t* matches0, const float* depth0,
                                       const float* depth1, const float* cam0, int model0, const float* cam1, int model1,
                                       const float* T_0to1, const float* T_1to0, int B, int M, int N, int H0, int W0,
@@ -241,11 +246,14 @@ extern "C" int gfc_eval_matches_depth(const float* kp0, const float* kp1, const 
       W0 <= 0 || H1 <= 0 || W1 <= 0 || !ep_model_ok(model0) || !ep_model_ok(model1) ||
       (M > 0 && (!kp0 || !matches0)) || (N > 0 && !kp1))
     return GFC_ERR_INVALID;
-  const size_t lds = ((size_t)6 * M + (size_t)7 * N) * sizeof(float) + 64;  // + 64: the kernel's static LDS
-  if (lds > 160 * 1024) return GFC_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)eval_matches_depth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
+  const size_t lds = ed_dynamic_lds(M, N);  // the dynamic arrays only: the launch adds the static ones itself
+  if (lds + ED_STATIC_LDS > EVAL_LDS_LIMIT) return GFC_ERR_UNSUPPORTED;
+  static std::atomic<unsigned long long> lds_ok{0};
+  if (lds > 64 * 1024 &&
+      !gfc_allow_dynamic_lds((const void*)eval_matches_depth_kernel, EVAL_LDS_LIMIT - ED_STATIC_LDS, lds_ok)) {
+    (void)hipGetLastError();
+    return GFC_ERR_LAUNCH;
+  }
   hipLaunchKernelGGL(eval_matches_depth_kernel, dim3(B), dim3(EM_THREADS), lds, (hipStream_t)stream, kp0, kp1,
                      (const long long*)matches0, depth0, depth1, cam0, model0, cam1, model1, T_0to1, T_1to0, M, N, H0,
                      W0, H1, W1, pos_th, neg_th, out, (long long*)gt_matches0, (long long*)gt_matches1);

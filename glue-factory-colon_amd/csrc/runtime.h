@@ -25,12 +25,14 @@ const GfcKnobs& gfc_knobs();
 int gfc_device_cus();
 
 // hipFuncAttributeMaxDynamicSharedMemorySize, applied once per (kernel instantiation, device).
-// `done` is one word per kernel instantiation (bit d = device d configured); safe from any thread.
-inline void gfc_allow_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done) {
+// `done` is one word per kernel instantiation (bit d = device d configured); safe from any thread.  `bytes` is the
+// largest dynamic size the kernel is ever launched with.  false: the runtime refused (asked again at the next call).
+inline bool gfc_allow_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsigned long long>& done) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
   const unsigned long long bit = 1ull << dev;
-  if (done.load(std::memory_order_acquire) & bit) return;
-  (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (done.load(std::memory_order_acquire) & bit) return true;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
   done.fetch_or(bit, std::memory_order_release);
+  return true;
 }

@@ -576,7 +576,14 @@ int gfc_nn_match(const float* desc0, const float* desc1, int B, int M, int N, in
  * gt_match_recall@pos_th, gt_match_precision@pos_th;  gt_m0_out (nullable) [B,M] int64 ground-truth
  * matches (-1 unmatched, -2 ignore).  Replaces eval_matches_homography (gluefactory/eval/utils.py:141-185),
  * sym_homography_error (geometry/homography.py:314-323), gt_matches_from_homography
- * (geometry/gt_generation.py:730-801; the evaluation calls it with pos_th = neg_th = 3). */
+ * (geometry/gt_generation.py:730-801; the evaluation calls it with pos_th = neg_th = 3).
+ * A match index >= N names no key point of image 1: it is never read, it counts in num_matches (and, with a ground
+ * truth other than ignore, in the precision denominator), its transfer error is infinite (in neither prec@), and it
+ * equals no ground-truth index.  (gfc_eval_homography_dlt skips such a match.)
+ * Every key point of a pair lives in LDS: GFC_ERR_UNSUPPORTED (nothing launched) exactly when
+ * gfc_eval_matches_homography_lds_bytes(M, N) = 16 M + 20 N + the kernel's static LDS exceeds 160 KB (163840 bytes);
+ * about 4500 x 4500 key points.  GFC_ERR_LAUNCH when the runtime refuses more than 64 KB of dynamic LDS. */
+size_t gfc_eval_matches_homography_lds_bytes(int M, int N);
 int gfc_eval_matches_homography(const float* kp0, const float* kp1, const int64_t* m0, const float* H,
                                 const float* Hinv, int B, int M, int N, float pos_th, float neg_th, float* out,
                                 int64_t* gt_m0_out, void* stream);
@@ -691,8 +698,12 @@ int gfc_eval_pose_project(const float* kp, const float* depth_i, const float* ca
  * calls it with pos_th 3, neg_th 5): dist = max(d0, d1), +inf outside visible0 x visible1; mutual argmin (first index
  * on ties) and dist < pos_th^2 is a match; -1 where the UNMASKED min of d0 (d1 for view 1) exceeds neg_th^2 and the
  * point's depth is valid; -2 otherwise.  Means over an empty set are 0.  gt_matches0 [B,M] / gt_matches1 [B,N] int64,
- * each nullable.  M == 0 or N == 0: all -1.  The M x N matrix is never materialised.  GFC_ERR_UNSUPPORTED (nothing
- * launched) when the pair does not fit in 160 KB of LDS: (6 M + 7 N) * 4 + 64 bytes. */
+ * each nullable.  M == 0 or N == 0: all -1.  The M x N matrix is never materialised.  A match index >= N counts as
+ * a match (covisible_percent, precision denominator), is never covisible and equals no ground-truth index.
+ * GFC_ERR_UNSUPPORTED (nothing launched) exactly when the pair does not fit in 160 KB (163840 bytes) of LDS:
+ * gfc_eval_matches_depth_lds_bytes(M, N) = 24 M + 28 N + the kernel's static LDS; about 3100 x 3100 key points.
+ * GFC_ERR_LAUNCH when the runtime refuses more than 64 KB of dynamic LDS. */
+size_t gfc_eval_matches_depth_lds_bytes(int M, int N);
 int gfc_eval_matches_depth(const float* kp0, const float* kp1, const int64_t* matches0, const float* depth0,
                            const float* depth1, const float* cam0, int model0, const float* cam1, int model1,
                            const float* T_0to1, const float* T_1to0, int B, int M, int N, int H0, int W0, int H1, int W1,

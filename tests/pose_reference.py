@@ -316,10 +316,15 @@ def _cell_status(depth, iy, ix):
 
 
 def _sampling_undecided(kp, depth):
+    return int(_sampling_undecided_mask(kp, depth).sum())
+
+
+def _sampling_undecided_mask(kp, depth):
+    """Per key point: whether the cells its depth sample reads depend on rounding AND one of them is a hole or outside."""
     import numpy as np
 
-    count = 0
-    for x, y in kp.astype(np.float64):
+    mask = np.zeros(len(kp), dtype=bool)
+    for q, (x, y) in enumerate(kp.astype(np.float64)):
         fx_, fy_ = x - 0.5, y - 0.5  # source index of the sample
         near_lin = [abs(v - round(v)) < BAND for v in (fx_, fy_)]      # pixel coordinate at k + 0.5
         near_nn = [abs(v - 0.5 - round(v - 0.5)) < BAND for v in (fx_, fy_)]  # pixel coordinate at k
@@ -329,10 +334,10 @@ def _sampling_undecided(kp, depth):
         rows = range(int(round(fy_)) - 1, int(round(fy_)) + 2) if near_lin[1] else range(int(np.floor(fy_)), int(np.floor(fy_)) + 2)
         status = [_cell_status(depth, r, c) for r in rows for c in cols]
         if any(near_lin) and any(status):
-            count += 1  # the bilinear footprint itself depends on rounding and touches a hole or the outside
+            mask[q] = True  # the bilinear footprint itself depends on rounding and touches a hole or the outside
         elif any(near_nn) and 1 in status:
-            count += 1  # bilinear is NaN for certain, so the nearest pixel decides, and which one depends on rounding
-    return count
+            mask[q] = True  # bilinear is NaN for certain, so the nearest pixel decides, and which one depends on rounding
+    return mask
 
 
 def undecidable_counts(fx):
@@ -415,3 +420,78 @@ def coverage(fx):
             near = D0.min(1) < 25.0  # a neighbour within neg_th without the visibility mask ...
         n["valid_not_visible_near"] += int((fx["valid0"][c] & near & ~(np.isfinite(D).any(1)) & (g == -2)).sum())  # ... only
     return n
+
+
+# ---- the same rules for ARBITRARY inputs: which key points and matches a float32 evaluation may decide differently ----
+NEAR_PX = 1.0  # a partner whose own projection is unsure counts as a possible match within pos_th + NEAR_PX
+
+
+def _unsure_points(kp, depth_i, cam_i, model_i, cam_j, model_j, T_itoj):
+    """Per key point of view i (float64 evaluation): its depth sample, its visibility or its projection depends on
+    rounding -- the sampling-cell, depth-sign and image-bound rules of `undecidable_counts`."""
+    kp, depth_i, cam_i, cam_j, T = kp.double(), depth_i.double(), cam_i.double(), cam_j.double(), T_itoj.double()
+    d, valid, proj, _ = pose_project(kp, depth_i, cam_i, model_i, cam_j, model_j, T)
+    nx, ny = pixel_to_ray(cam_i, model_i, kp[:, 0], kp[:, 1])
+    Z = (torch.stack([nx * d, ny * d, d], -1) @ rot(T).t() + T[9:])[:, 2]
+    unsure = torch.from_numpy(_sampling_undecided_mask(kp.numpy(), depth_i.numpy()))
+    unsure = unsure | (valid & ((Z - Z_MIN).abs() < 1e-5))
+    for a in (0, 1):
+        v = proj[:, a]
+        unsure = unsure | (valid & torch.isfinite(v) & ((v.abs() < BAND) | ((v - (cam_j[a] - 1)).abs() < BAND)))
+    return unsure
+
+
+def undecided(kp0, kp1, matches0, depth0, depth1, cam0, model0, cam1, model1, T_0to1, T_1to0=None, pos_th=3.0,
+              neg_th=5.0):
+    """ONE pair, evaluated in float64: which verdicts of `gt_matches` / `reprojection_errors` rest on a decision within a
+    rounding error of going the other way (the rules of `undecidable_counts`, per key point instead of per fixture).
+    A key point is undecided when its own sample / visibility is unsure (`_unsure_points`); when its best distance is
+    within BAND of pos_th or its nearest unmasked neighbour within BAND of neg_th; when the runner-up of its argmin -- or
+    of the argmin of its partner's line -- is within BAND (1 + best) of the winner (squared distances) while the winner
+    is below pos_th + BAND; or when a point of the other view that is itself unsure lies within pos_th + NEAR_PX of it.
+    Candidates with bit-identical coordinates are exempt from the runner-up rule: their distances are equal in any
+    arithmetic and the lower index is the answer.  A match is undecided when its error is within BAND of 1, 3 or 5 px
+    or one of its end points is unsure.  -> {"undecided0" [M], "undecided1" [N], "undecided_match" [M]} bool"""
+    kp0, kp1, depth0, depth1 = kp0.double(), kp1.double(), depth0.double(), depth1.double()
+    cam0, cam1, T_0to1 = cam0.double(), cam1.double(), T_0to1.double()
+    T_1to0 = invert_pose(T_0to1) if T_1to0 is None else T_1to0.double()
+    M, N = kp0.shape[0], kp1.shape[0]
+    uns0 = _unsure_points(kp0, depth0, cam0, model0, cam1, model1, T_0to1)
+    uns1 = _unsure_points(kp1, depth1, cam1, model1, cam0, model0, T_1to0)
+    if M == 0 or N == 0:
+        return {"undecided0": torch.zeros(M, dtype=torch.bool), "undecided1": torch.zeros(N, dtype=torch.bool),
+                "undecided_match": torch.zeros(M, dtype=torch.bool)}
+    _, valid0, p01, vis0 = pose_project(kp0, depth0, cam0, model0, cam1, model1, T_0to1)
+    _, valid1, p10, vis1 = pose_project(kp1, depth1, cam1, model1, cam0, model0, T_1to0)
+    inf = float("inf")
+    D0 = ((p01[:, None] - kp1[None]) ** 2).sum(-1)
+    D1 = ((kp0[:, None] - p10[None]) ** 2).sum(-1)
+    D = torch.where(vis0[:, None] & vis1[None], torch.maximum(D0, D1), torch.full_like(D0, inf))
+    near2 = (pos_th + NEAR_PX) ** 2
+    close = torch.minimum(torch.nan_to_num(D0, nan=inf), torch.nan_to_num(D1, nan=inf)) < near2
+    by_other0 = (close & uns1[None]).any(1)
+    by_other1 = (close & uns0[:, None]).any(0)
+    del close
+    und, near, arg = [], [], []
+    for dim, Dn, kp_other, valid in ((1, D0, kp1, valid0), (0, D1, kp0, valid1)):
+        best, idx = D.min(dim)
+        twin = (kp_other[None] == kp_other[idx][:, None]).all(-1)  # [this side, other side]
+        second = torch.where(twin if dim == 1 else twin.t(), torch.full_like(D, inf), D).min(dim).values
+        ok = torch.isfinite(best)
+        b = torch.where(ok, best, torch.zeros_like(best))
+        near.append(ok & (second - b < BAND * (1 + b)) & (b.sqrt() < pos_th + BAND))
+        arg.append(idx)
+        dmin = Dn.min(dim).values  # NaN where the point's own projection is
+        u = ok & ((b.sqrt() - pos_th).abs() < BAND)
+        u = u | (valid & torch.isfinite(dmin) & ((torch.nan_to_num(dmin, nan=0.0).sqrt() - neg_th).abs() < BAND))
+        und.append(u)
+    und0 = uns0 | by_other0 | und[0] | near[0] | near[1][arg[0]]
+    und1 = uns1 | by_other1 | und[1] | near[1] | near[0][arg[1]]
+    has = (matches0 > -1) & (matches0 < N)
+    j = torch.where(has, matches0, torch.zeros_like(matches0))
+    err = 0.5 * (((p01 - kp1[j]) ** 2).sum(-1).sqrt() + ((p10[j] - kp0) ** 2).sum(-1).sqrt())
+    at_th = torch.zeros(M, dtype=torch.bool)
+    for th in (1.0, 3.0, 5.0):
+        at_th = at_th | ((torch.nan_to_num(err, nan=inf) - th).abs() < BAND)
+    und_match = has & ((valid0 & valid1[j] & at_th) | uns0 | uns1[j])
+    return {"undecided0": und0, "undecided1": und1, "undecided_match": und_match}

@@ -310,3 +310,83 @@ def test_pipeline_on_eight_pairs(scenes, tmp_path):
     with pytest.raises(NotImplementedError, match="five-point"):
         eval_utils.eval_relative_pose_robust(to_cuda_item(items[0]), {k: v.cuda() for k, v in preds[0].items()},
                                              {"estimator": "poselib", "ransac_th": 1.0})
+
+
+# ---- the depth kernel on its large path: above 64 KB of LDS, the evaluation's 2048 x 2048, and the LDS limit -------------
+# One workgroup keeps every key point of a pair in LDS: 24 M + 28 N bytes of dynamic arrays beside the kernel's static
+# ones.  The fixture and the scenes above stay below 4 KB; these scenes (240 x 320 maps) are the first shape above
+# 64 KB, the evaluation's shape, and the largest shape the launcher admits -- the next one up is refused before any launch.
+# Checker: pose_reference in float64.  Only what pose_reference.undecided flags is exempt (its own undecidable rules, per
+# key point), and every scene asserts on the CPU side, before the kernel's answer is looked at, that at most 1 % of the
+# key points of either view and at most 1 % of the matches are flagged.
+BIG_H, BIG_W, LDS_LIMIT, CAP = 240, 320, 160 * 1024, 0.01
+
+
+def largest_admitted_depth(m):
+    lds_bytes = eval_utils.nat.lib().gfc_eval_matches_depth_lds_bytes
+    n = 0
+    while lds_bytes(m, n + 1) <= LDS_LIMIT:
+        n += 1
+    return n
+
+
+def check_large(model, m, n, b, seed):
+    items, preds = synthetic.posed_plane_pairs(b, BIG_H, BIG_W, seed=seed, model=model, num_keypoints=(m, n))
+    bt = batch_of(items, preds, range(b))
+    T10 = torch.stack([pr.invert_pose(t.double()) for t in bt["T"]])
+    dbl = {k: v.double() for k, v in bt.items() if k not in ("m0", "model")}
+    flags = [pr.undecided(bt["kp0"][i], bt["kp1"][i], bt["m0"][i], bt["depth0"][i], bt["depth1"][i], bt["cam0"][i], model,
+                          bt["cam1"][i], model, bt["T"][i]) for i in range(b)]
+    for f, m0 in zip(flags, bt["m0"]):  # the condition on the input
+        shares = (float(f["undecided0"].float().mean()), float(f["undecided1"].float().mean()),
+                  float(f["undecided_match"].sum()) / max(int((m0 > -1).sum()), 1))
+        print(model, (m, n), "undecided shares", shares)
+        assert max(shares) <= CAP, ("bad input: too many undecided", shares)
+    m7, c0, c1 = pr.depth_metrics(dbl["kp0"], dbl["kp1"], bt["m0"], dbl["depth0"], dbl["depth1"], dbl["cam0"], model,
+                                  dbl["cam1"], model, dbl["T"], T10)
+    out, g0, g1, _ = run_gpu(bt)
+    out = out.double()
+    for i, f in enumerate(flags):
+        s0, s1 = ~f["undecided0"], ~f["undecided1"]
+        assert torch.equal(g0[i][s0], c0[i][s0]), (i, torch.nonzero((g0[i] != c0[i]) & s0).flatten()[:10])
+        assert torch.equal(g1[i][s1], c1[i][s1]), (i, torch.nonzero((g1[i] != c1[i]) & s1).flatten()[:10])
+        assert (c0[i] > -1).any() and (c0[i] == -1).any() and (c0[i] == -2).any()
+        m0 = bt["m0"][i]
+        err, valid = pr.reprojection_errors(dbl["kp0"][i], dbl["kp1"][i], m0, dbl["depth0"][i], dbl["depth1"][i],
+                                            dbl["cam0"][i], model, dbl["cam1"][i], model, dbl["T"][i], T10[i])
+        und = f["undecided_match"][m0 > -1]
+        n_und, nm = int(und.sum()), int((m0 > -1).sum())
+        nv = float(out[i, 3])
+        sure_valid = int((valid & ~und).sum())
+        assert nv == round(nv) and sure_valid <= nv <= sure_valid + n_und, (i, nv, sure_valid, n_und)
+        assert abs(float(out[i, 4]) / 100.0 - nv / nm) <= 1e-6
+        e = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err)
+        for col, th in ((0, 1.0), (1, 3.0), (2, 5.0)):
+            sure_true = int((valid & ~und & (e < th)).sum())
+            k = round(float(out[i, col]) * nv)
+            assert sure_true <= k <= sure_true + n_und, (i, th, k, sure_true, n_und)
+            assert abs(float(out[i, col]) - k / nv) <= 1e-6
+        # recall and precision from the kernel's OWN ground truth: the reduction, pinned apart from the verdicts
+        agree, rec, prec = m0 == g0[i], g0[i] > -1, (m0 > -1) & (g0[i] >= -1)
+        assert abs(float(out[i, 5]) - float((agree & rec).sum()) / (1e-8 + float(rec.sum()))) <= 1e-6
+        assert abs(float(out[i, 6]) - float((agree & prec).sum()) / (1e-8 + float(prec.sum()))) <= 1e-6
+
+
+@pytest.mark.parametrize("model,m,n,b,seed", [("PINHOLE", 1300, 1250, 1, 21), ("OPENCV_FISHEYE", 1300, 1250, 1, 21),
+                                               ("PINHOLE", 2048, 2048, 2, 22)])
+def test_depth_metrics_above_64_kb_of_lds(model, m, n, b, seed):
+    lds_bytes = eval_utils.nat.lib().gfc_eval_matches_depth_lds_bytes
+    assert lds_bytes(m, n) > 64 * 1024 >= lds_bytes(1250, 1250)  # 1300 x 1250 is just above, 1250 x 1250 below
+    check_large(model, m, n, b, seed)
+
+
+def test_depth_metrics_largest_admitted_shape_and_the_next_one_refused():
+    m = 3150
+    n = largest_admitted_depth(m)
+    lds_bytes = eval_utils.nat.lib().gfc_eval_matches_depth_lds_bytes
+    assert n >= 3100 and lds_bytes(m, n) <= LDS_LIMIT < lds_bytes(m, n + 1)
+    check_large("PINHOLE", m, n, 1, 23)
+    # one more key point: refused by the launcher's own arithmetic, nothing is launched
+    items, preds = synthetic.posed_plane_pairs(1, BIG_H, BIG_W, seed=23, model="PINHOLE", num_keypoints=(m, n + 1))
+    with pytest.raises(eval_utils.nat.NativeError, match="UNSUPPORTED"):
+        run_gpu(batch_of(items, preds, range(1)))
