@@ -250,7 +250,9 @@ class SuperGlue(BaseModel):
     def forward_pairs(self, datas: list) -> list:
         """MI355X addition: `[self(d) for d in datas]` for batch-1 pairs, the pairs of equal (m, n) stacked into one
         batch each and sent through the batched core once per group.  Per-pair dictionaries with the keys of the
-        single-pair call, in the order given; pairs with an empty side or a batch size other than 1 take `self(d)`."""
+        single-pair call, in the order given; pairs with an empty side or a batch size other than 1 take `self(d)`.
+        Against the single-pair calls: matches identical outside near-ties, floats within 1e-4 -- not bit for bit, since
+        the attention's key split and the GEMM tile follow the size of the launch (Sinkhorn alone is bit-identical)."""
         outs = [None] * len(datas)
         shapes = {}
         for i, d in enumerate(datas):

@@ -601,6 +601,56 @@ def test_attention(shapes, use_ws):
             assert torch.isnan(o[r + nq:r + max(nq, nk)]).all()  # rows of other problems untouched
 
 
+@pytest.mark.parametrize("shapes", [[(600, 600)] * 2, [(100, 161), (161, 100)]], ids=["2x600x600", "cross_100_161"])
+def test_attention_scratch_smaller_than_the_full_split(shapes):
+    """gfc_att_split shrinks the key split until its partials fit the scratch it is offered (the callers with M != N
+    offer less than the full split: the kernel indexes n_problems * max_nq query slots, they have fewer rows).  Three
+    offers from one buffer filled with 0xA5: the full size (split 8); exactly the partials of a 3-way split (600 keys:
+    10 tiles shared 4 + 4 + 2; 161 / 100 keys: 3 and 2 tiles, the third share of the latter empty); 4 bytes short of a
+    2-way split (no split: the scratch is not touched).  Each result against a float64 soft-max; nothing behind the
+    offer is written.  Whether the three results agree among themselves is not asserted."""
+    lib = nat.lib()
+    g = gen(len(shapes) + shapes[0][0])
+    heads, n_prob = 4, len(shapes)
+    rows = sum(max(nq, nk) for nq, nk in shapes)
+    q = torch.randn((rows, 256), generator=g) * 1.5
+    k = torch.randn((rows, 256), generator=g) * 1.5
+    v = torch.randn((rows, 256), generator=g)
+    probs, r0 = [], 0
+    for nq, nk in shapes:
+        probs.append([r0, nq, r0, nk])
+        r0 += max(nq, nk)
+    qd, kd, vd = D(q), D(k), D(v)
+    pt = D(torch.tensor(probs, dtype=torch.int32))
+    max_nq = max(s[0] for s in shapes)
+    refs = []
+    for r, nq, _, nk in probs:
+        qq, kk, vv = (t[r:r + n_].double().view(n_, heads, 64).transpose(0, 1) for t, n_ in ((q, nq), (k, nk), (v, nk)))
+        refs.append((torch.softmax(qq @ kk.transpose(1, 2) * 0.125, -1) @ vv).transpose(0, 1).reshape(nq, 256))
+    full = lib.gfc_attention_workspace_bytes(n_prob, max_nq, heads)
+    part = lambda split: n_prob * max_nq * heads * split * 66 * 4  # noqa: E731
+    assert full == (part(8) + 255) // 256 * 256  # the dispatch wants all 8 splits for both problem sets
+    buf = torch.empty(full, dtype=torch.uint8, device=DEV)
+    for offer, split in ((full, 8), (part(3), 3), (part(2) - 4, 1)):
+        buf.fill_(0xA5)
+        o = torch.full((rows, 256), float("nan"), device=DEV)
+        nat.check(lib.gfc_attention(nat.ptr(qd), 256, nat.ptr(kd), 256, nat.ptr(vd), 256, nat.ptr(o), 256, nat.ptr(pt),
+                                    n_prob, max_nq, heads, 0.125, nat.ptr(buf), offer, st()), "attention")
+        torch.cuda.synchronize()
+        oc = o.cpu()
+        for (r, nq, _, nk), ref in zip(probs, refs):
+            assert maxerr(oc[r:r + nq], ref) < 2e-5, (offer, split)
+            if nq < max(nq, nk):
+                assert torch.isnan(oc[r + nq:r + max(nq, nk)]).all()  # rows of other problems untouched
+        assert bool((buf[offer:] == 0xA5).all()), f"wrote behind an offer of {offer} bytes"
+        # the partials of `split` shares end exactly at part(split): the path the offer is meant to reach did run
+        used = buf[:offer] != 0xA5
+        if split == 1:
+            assert not bool(used.any()), "no split fits: the scratch must stay untouched"
+        else:
+            assert bool(used[part(split) - 66 * 4:part(split)].any()) and not bool(used[part(split):].any())
+
+
 def test_attention_peaky_rows():
     """A spiked key forces the running-max rescale branch at a chosen tile (online softmax)."""
     lib = nat.lib()

@@ -44,12 +44,13 @@ def ratio(got, ref):
 
 def record(case, **ratios):
     for k, v in ratios.items():
-        print(f"{case}: {k} {v:.3e}")
+        print(f"{case}: {k} {v:.3e}" if isinstance(v, float) else f"{case}: {k} {v}")
     _parity.setdefault(case, {}).update(ratios)
     if os.environ.get("GFC_WRITE_PROFILES") == "1":
         with open(os.path.join(ROOT, "profiles", "superglue_parity.json"), "w") as f:
             json.dump({"what": "largest |kernel - reference| / (1 + |reference|) per test case of tests/test_gpu_superglue.py; "
-                               "bound 1e-4; name-seeded weights (weights.superglue_state_dict(0))",
+                               "bound 1e-4; name-seeded weights (weights.superglue_state_dict(0)); integers are counts, "
+                               "booleans observations (informational)",
                        "device": torch.cuda.get_device_name(0), "bound": BOUND, "cases": _parity}, f, indent=1)
 
 
@@ -162,7 +163,46 @@ def sinkhorn_gpu(cost, bin_score, iters):
 SINKHORN_CASES = [  # (B, M, N, iterations, half-width of the uniform cost)
     (1, 1, 1, 50, 4.0), (1, 1, 1030, 50, 4.0), (3, 301, 258, 1, 4.0), (3, 301, 258, 50, 4.0), (3, 301, 258, 100, 4.0),
     (1, 301, 258, 50, 120.0),  # spans +-120: exp overflows / underflows without the maximum subtraction
+    # the edges of the row-block plan (PLAN_EDGES below)
+    (1, 2048, 70, 20, 4.0), (2, 21, 4600, 20, 4.0), (1, 3, 20463, 5, 4.0), (2, 16, 40, 20, 4.0),
+    (2, 16, 40, 0, 4.0),  # no iteration: u = v = 0, the result is Z - norm
 ]
+SK_LDS_MAX = 160 * 1024
+
+
+def sk_plan(m, n):
+    """sk_plan of csrc/superglue.hip restated: (rows per workgroup, row blocks, rows of the last block, bytes of dynamic
+    LDS of the rows kernel), or None where a row of N + 1 floats plus v does not fit."""
+    row = (n + 1) * 4
+    fit = (SK_LDS_MAX - 32 * 4) // row
+    if fit < 2:
+        return None
+    rb = min(max((m + 64) // 64, 8), 32, fit - 1, m + 1)
+    nblk = (m + rb) // rb
+    return rb, nblk, m + 1 - (nblk - 1) * rb, (rb + 1) * row + rb * 4
+
+
+PLAN_EDGES = {  # (M, N): what the shape is in SINKHORN_CASES for
+    (2048, 70): (32, 65, 1, 33 * 71 * 4 + 128),  # the cap of 32 rows; the last block is the dustbin row alone
+    (21, 4600): (7, 4, 1, 8 * 4601 * 4 + 28),    # 8 rows fit: clipped to 7 beside v; the dustbin row alone again
+    (3, 20463): (1, 4, 1, 163716),               # the last N admitted: one row per workgroup, 124 bytes below the limit
+    (16, 40): (8, 3, 1, 9 * 41 * 4 + 32),        # the default 8 rows, 17 rows in all
+}
+
+
+def test_sinkhorn_plan_edges_are_what_the_cases_are_for():
+    """If sk_plan changes, the shapes above must move with it: this restates it (no kernel runs)."""
+    for shape, want in PLAN_EDGES.items():
+        assert sk_plan(*shape) == want, (shape, sk_plan(*shape))
+        assert shape in {(c[1], c[2]) for c in SINKHORN_CASES}
+    assert sk_plan(3, 20463)[3] <= SK_LDS_MAX and sk_plan(3, 20464) is None
+    assert sk_plan(8, 4546)[0] == 8 and sk_plan(8, 4547)[0] == 7  # where the LDS clip starts
+    lib = nat.lib()
+    for (m, n), (rb, nblk, _, _) in PLAN_EDGES.items():  # u | v | partials, each slot rounded up to 256 bytes
+        up = lambda x: (x + 255) // 256 * 256  # noqa: E731
+        for b in (1, 2):
+            assert lib.gfc_sg_sinkhorn_workspace_bytes(b, m, n) == (up(b * (m + 1) * 4) + up(b * (n + 1) * 4)
+                                                                   + up(b * nblk * (n + 1) * 8)), (b, m, n)
 
 
 @pytest.mark.parametrize("case", SINKHORN_CASES, ids=lambda c: "B{}_{}x{}_it{}_w{:g}".format(*c))
@@ -179,6 +219,34 @@ def test_sinkhorn_against_float64(case):
     r = ratio(got, ref)
     record("sinkhorn_B{}_{}x{}_it{}_w{:g}".format(*case), log_assignment=r)
     assert r <= BOUND, r
+
+
+def test_sinkhorn_refuses_what_its_plan_cannot_hold():
+    """N = 20 464 is the first row that does not fit in LDS beside v: no workspace size, GFC_ERR_UNSUPPORTED, nothing
+    launched; the whole matcher names no workspace either.  M + 1 = 65 536 rows exceed the finalize kernel's grid."""
+    lib = nat.lib()
+    ws = torch.full((256,), 0xA5, dtype=torch.uint8, device="cuda")
+    for (b, m, n), status in (((1, 3, 20464), "GFC_ERR_UNSUPPORTED"), ((1, 65535, 4), "GFC_ERR_INVALID")):
+        cost = torch.zeros((b, m, n), device="cuda")
+        out = torch.full((b, m + 1, n + 1), float("nan"), device="cuda")
+        got = lib.gfc_sg_sinkhorn(nat.ptr(cost), 0.7, b, m, n, 20, nat.ptr(out), nat.ptr(ws), ws.numel(),
+                                  nat.stream_ptr(cost.device))
+        torch.cuda.synchronize()
+        assert nat.STATUS[got] == status, (b, m, n, got)
+        assert bool(torch.isnan(out).all()) and bool((ws == 0xA5).all())
+    assert lib.gfc_sg_sinkhorn_workspace_bytes(1, 3, 20464) == 0 and lib.gfc_sg_workspace_bytes(1, 3, 20464) == 0
+    assert lib.gfc_sg_sinkhorn_workspace_bytes(1, 3, 20463) > 0 and lib.gfc_sg_workspace_bytes(1, 3, 20463) > 0
+
+
+def test_sinkhorn_of_a_matrix_does_not_depend_on_its_batch():
+    """The row-block plan is a function of (M, N) alone and no kernel sums across matrices: matrix i of a batched call
+    equals the call on that matrix alone, bit for bit."""
+    b, m, n, iters = 3, 301, 258, 50
+    cost = (torch.rand(b, m, n, generator=torch.Generator().manual_seed(1000 * m + n)) * 2 - 1) * 4.0
+    batched = sinkhorn_gpu(cost, 0.7, iters)
+    assert bool(torch.isfinite(batched).all())
+    for i in range(b):
+        assert torch.equal(batched[i:i + 1], sinkhorn_gpu(cost[i:i + 1], 0.7, iters)), i
 
 
 # ------------------------------------------------------------------------------ 4. the MLP and the encoder alone
@@ -295,7 +363,27 @@ def test_one_loud_head_rules_out_a_head_order_mix_up():
 
 
 # ------------------------------------------------------------------------------------------------ 6. forward_pairs
+def att_partition(b, m, n, nk):
+    """(key split, key tiles per split) of the attention launch of gfc_sg_forward for B pairs of (m, n) points, keys of
+    a side with nk points: the integer arithmetic of gfc_attention / gfc_att_split / sg_ws restated."""
+    heads, problems, max_nq = 4, 2 * b, max(m, n)
+    wgs = lambda aq: (max_nq + aq - 1) // aq * heads * problems  # noqa: E731
+    tiles = (nk + 63) // 64
+    if wgs(256) >= 1024 or wgs(128) >= 256:  # 256 queries per workgroup / enough workgroups of 128: no split
+        return 1, tiles
+    split = min((511 + wgs(128)) // wgs(128), 8)
+    rows = b * (m + n)
+    scratch = rows * heads * 8 * 66 * 4 if rows <= 8192 else 0  # sg_ws: the full split of B (M + N) query slots
+    while split > 1 and scratch < problems * max_nq * heads * split * 66 * 4:
+        split -= 1
+    return split, (tiles + split - 1) // split
+
+
 def test_forward_pairs_equals_single_pair_calls():
+    """Bit equality holds at these shapes because both runs take the same key partition in the attention (asserted
+    first) and the same GEMM tile; it is not a contract (test_a_pair_in_a_batch_of_six_... states that one)."""
+    for nk in (65, 130):
+        assert att_partition(1, 65, 130, nk) == att_partition(2, 65, 130, nk) == (6, 1)
     mod = model(50)
     shapes = [(65, 130), (40, 17), (65, 130), (12, 0)]  # three distinct (m, n), one pair empty on one side
     datas = []
@@ -316,6 +404,55 @@ def test_forward_pairs_equals_single_pair_calls():
             assert s[k].dtype == b[k].dtype and torch.equal(s[k], b[k]), k
     assert sorted(single[3]) == ["matches0", "matches1", "matching_scores0", "matching_scores1"]
     assert single[3]["matches0"].dtype == torch.int and int((single[0]["matches0"] >= 0).sum()) > 0
+
+
+def test_a_pair_in_a_batch_of_six_against_float64_and_its_single_call():
+    """What a pair's result may depend on its batch for.  Six pairs of 300 + 300 points run the attention with a 4-way
+    key split of two 64-key tiles each, one such pair alone with an 8-way split of one tile (asserted from the
+    dispatch arithmetic first: if that changes, this test compares a kernel with itself and must be given another
+    shape).  The partial soft-maxes are then merged in another order, so the floats may differ in their last bits.  The
+    contract: every run within the bound of float64; integers identical to float64's and to each other outside the
+    near-ties (gap_band of the float64 log-assignment); matching scores within 1e-4.  Sinkhorn alone is bit-identical
+    across batches (test_sinkhorn_of_a_matrix_does_not_depend_on_its_batch)."""
+    shape = (6, 300, 300, 50)
+    b, m, n, iters = shape
+    assert att_partition(1, m, n, 300) == (8, 1) and att_partition(b, m, n, 300) == (4, 2)
+    inp, r64 = ref64(shape)
+    rows, cols = sgr.gap_band(r64["log_assignment"])
+    # condition on the inputs: near-ties are rare (the restatement alone: 0 rows and 1 column of 3600)
+    assert int(rows.sum()) <= 0.01 * rows.numel() and int(cols.sum()) <= 0.01 * cols.numel()
+    mod = model(iters)
+
+    def gpu(sub):
+        with torch.no_grad():
+            out = mod._run(*mod._inputs(sgr.as_data(sub, "cuda")))
+        torch.cuda.synchronize()
+        return {k: v.cpu() for k, v in out.items()}
+
+    batched = gpu(inp)
+    single = [gpu({k: v[i:i + 1] for k, v in inp.items()}) for i in range(b)]
+    single = {k: torch.cat([s[k] for s in single], 0) for k in batched}
+    r = {}
+    for name, out in (("batched", batched), ("single", single)):
+        r[f"{name}_log_assignment"] = ratio(out["log_assignment"], r64["log_assignment"])
+        r[f"{name}_sinkhorn_cost"] = ratio(out["sinkhorn_cost"], r64["sinkhorn_cost"])
+        r[f"{name}_matching_scores_abs"] = scores_ratio(out, r64, r64["log_assignment"])
+    d0 = (batched["matching_scores0"].double() - single["matching_scores0"].double()).abs()
+    d1 = (batched["matching_scores1"].double() - single["matching_scores1"].double()).abs()
+    r["batched_vs_single_matching_scores_abs"] = float(max(d0.max(), d1.max()))
+    r["batched_vs_single_log_assignment"] = ratio(batched["log_assignment"], single["log_assignment"])
+    record("pair_in_batch_of_six_300x300", **r, band_rows=int(rows.sum()), band_cols=int(cols.sum()),
+           batched_log_assignment_bit_equal_to_single=bool(torch.equal(batched["log_assignment"],
+                                                                       single["log_assignment"])))
+    for name, out in (("batched", batched), ("single", single)):
+        assert out["matches0"].dtype == torch.long and int((out["matches0"] >= 0).sum()) > 0
+        assert torch.equal(out["matches0"][~rows], r64["matches0"][~rows]), name
+        assert torch.equal(out["matches1"][~cols], r64["matches1"][~cols]), name
+    assert torch.equal(batched["matches0"][~rows], single["matches0"][~rows])
+    assert torch.equal(batched["matches1"][~cols], single["matches1"][~cols])
+    for k in ("batched_log_assignment", "batched_sinkhorn_cost", "single_log_assignment", "single_sinkhorn_cost",
+              "batched_vs_single_matching_scores_abs"):
+        assert r[k] <= BOUND, (k, r[k])
 
 
 # --------------------------------------------------------------------------------------------- 7. TwoViewPipeline

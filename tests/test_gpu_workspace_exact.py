@@ -430,13 +430,91 @@ def _case_relpose(_):
     return lib.gfc_eval_relative_pose_ransac_workspace_bytes(b, m, t, nh), run
 
 
+# ------------------------------------------------------------------------------------------------ SuperGlue
+def _sg(names):
+    """(module, gfc_sg_params) of a synthetic matcher with the GNN layers `names`: none for the encoder alone (weights of
+    test_keypoint_encoder_against_float64), two for the whole forward."""
+    key = ("sg", names)
+    if key not in _MODELS:
+        from glue_factory_colon_amd import superglue, weights
+
+        if names:
+            m = superglue.SuperGlue({"weights": "synthetic", "GNN_layers": list(names), "num_sinkhorn_iterations": 20})
+        else:
+            m = superglue.SuperGlue({"weights": None, "GNN_layers": []})
+            m.load_state_dict(weights.superglue_state_dict(5, n_layers=0), strict=True)
+        m = m.eval().to(DEV)
+        _MODELS[key] = (m, m.ensure_packed(DEV)[0])
+    return _MODELS[key]
+
+
+def _sg_points(rows, g):
+    """key points of 640 x 480 images, detection scores, unit descriptors"""
+    return (torch.rand((rows, 2), generator=g) * torch.tensor([640.0, 480.0])).to(DEV), \
+        torch.rand((rows,), generator=g).to(DEV), _desc(rows, g).to(DEV)
+
+
+def _case_sg_keypoint_encoder(_):
+    """The hidden [rows, 256] activations in front of the last encoder layer are the whole workspace."""
+    lib, (_, params) = nat.lib(), _sg(())
+    kp, sc, de = _sg_points(B * N, gen(51))
+    size = torch.tensor([[640.0, 480.0], [300.0, 500.0]], device=DEV)
+
+    def run(ws, nbytes):
+        desc = de.clone()  # in: the descriptors, out: descriptors + encoding
+        nat.check(lib.gfc_sg_keypoint_encoder(ctypes.byref(params), P(kp), P(sc), P(size), B, N, P(desc), P(ws), nbytes,
+                                              st()), "gfc_sg_keypoint_encoder")
+        return [desc]
+
+    return lib.gfc_sg_keypoint_encoder_workspace_bytes(B * N), run
+
+
+def _case_sg_sinkhorn(_):
+    """u | v | the column partials of every row block"""
+    lib = nat.lib()
+    cost = ((torch.rand((B, M, N), generator=gen(52)) * 2 - 1) * 4.0).to(DEV)
+
+    def run(ws, nbytes):
+        out = torch.full((B, M + 1, N + 1), float("nan"), device=DEV)
+        nat.check(lib.gfc_sg_sinkhorn(P(cost), 0.7, B, M, N, 20, P(out), P(ws), nbytes, st()), "gfc_sg_sinkhorn")
+        return [out]
+
+    return lib.gfc_sg_sinkhorn_workspace_bytes(B, M, N), run
+
+
+def _case_sg_forward(_):
+    """Two layers (self, cross).  The qkv slot holds the encoder's hidden rows, then Q | K | V, then the final_proj
+    output; the Sinkhorn and filter workspaces are carved from this one; and M != N, so the attention scratch, sized for
+    B (M + N) query slots, is smaller than the 8-way split of the 2 B max(M, N) slots the kernel indexes: gfc_att_split
+    shrinks the split (asserted below), and the partials of the split it lands on must fit."""
+    lib, (_, params) = nat.lib(), _sg(("self", "cross"))
+    g = gen(53)
+    k0, s0, d0 = _sg_points(B * M, g)
+    k1, s1, d1 = _sg_points(B * N, g)
+    size = torch.tensor([[640.0, 480.0]] * B, device=DEV)
+    rows, slots = B * (M + N), 2 * B * max(M, N)
+    assert slots * 2 <= rows * 8 < slots * 8  # room for a split of at least 2, not for all 8: the shrink loop runs
+
+    def run(ws, nbytes):
+        i64 = lambda n: torch.full((B, n), -7, dtype=torch.long, device=DEV)  # noqa: E731
+        o = [torch.zeros((B, M, N), device=DEV), torch.zeros((B, M + 1, N + 1), device=DEV), i64(M), i64(N),
+             torch.zeros((B, M), device=DEV), torch.zeros((B, N), device=DEV)]
+        taps = torch.zeros((4, rows, 256), device=DEV)
+        nat.check(lib.gfc_sg_forward(ctypes.byref(params), P(k0), P(k1), P(s0), P(s1), P(d0), P(d1), P(size), P(size), B, M,
+                                     N, 20, 0.2, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(o[5]), P(taps), P(ws),
+                                     nbytes, st()), "gfc_sg_forward")
+        return o + list(taps)
+
+    return lib.gfc_sg_workspace_bytes(B, M, N), run
+
+
 CASES = [(fn, arg) for arg in ("fp32", "fp16")
          for fn in (_case_lg_layer, _case_lg_assign, _case_lg_forward, _case_lg_forward_packed, _case_lg_forward_ragged,
                     _case_attention)]
 CASES += [(_case_nn_match, None), (_case_log_assignment, None), (_case_filter_matches, None), (_case_adaptive_step, None),
           (_case_sp_dense, 1), (_case_sp_dense, 3), (_case_sp_select, False), (_case_sp_select, True),
           (_case_disk_nms_select, None), (_case_disk_instnorm, None), (_case_ransac, None),
-          (_case_relpose, None)]
+          (_case_relpose, None), (_case_sg_keypoint_encoder, None), (_case_sg_sinkhorn, None), (_case_sg_forward, None)]
 
 
 @pytest.mark.parametrize("case,arg", CASES, ids=[f"{fn.__name__[6:]}-{arg}" for fn, arg in CASES])
