@@ -168,6 +168,8 @@ SIGNATURES = {
                                   + [c_void_p] * 2),
     "gfc_preprocess_resize": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] + [c_int] * 4 + [c_void_p]),
     "gfc_preprocess_resample": (c_int, [c_void_p] + [c_int] * 11 + [c_float] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
+    "gfc_warp_perspective": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] + [c_int] * 2
+                             + [c_void_p]),
     "gfc_lg_layer_workspace_bytes": (c_size_t, [c_int]),
     "gfc_lg_layer": (c_int, [POINTER(LgParams), c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                              c_int, c_void_p, c_size_t, c_void_p]),

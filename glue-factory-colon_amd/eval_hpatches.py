@@ -87,6 +87,8 @@ def robust_summaries(per_threshold, auc_ths=(1, 3, 5), key="H_error_ransac", uni
 class HPatchesPipeline:
     export_keys = EXPORT_KEYS
     optional_export_keys = OPTIONAL_EXPORT_KEYS
+    default_data_conf = DEFAULT_DATA_CONF
+    shard_group = 5  # consecutive items that share their view 0 (an HPatches sequence has five pairs)
 
     def __init__(self, data_conf=None, pair_batch=32, num_workers=2, eval_conf=None):
         self.eval_conf = dict(eval_conf or {})
@@ -94,17 +96,25 @@ class HPatchesPipeline:
             raise ValueError(f"unknown homography estimator {self.eval_conf['estimator']!r}: available here: "
                              f"{list(eval_utils.RANSAC_ESTIMATORS)}")
         self._robust_conf()  # refuses a bad threshold list here, not in the middle of an evaluation
-        self.data_conf = {**DEFAULT_DATA_CONF, **dict(data_conf or {})}
+        self.data_conf = {**self.default_data_conf, **dict(data_conf or {})}
         self.pair_batch, self.num_workers = int(pair_batch), int(num_workers)
-        self.dataset = hpatches.HPatches(self.data_conf)
+        self.dataset = self._get_dataset(self.data_conf)
+
+    def _get_dataset(self, data_conf):
+        """The pair list -- `len()`, `meta(i)`, `view_key`, `feeder()`; a hook for the pipelines over other pair lists
+        (the fork's Endopatches1800Pipeline picks its dataset in a `_get_dataset` too, eval/endopatches1800.py:63-67)."""
+        return hpatches.HPatches(data_conf)
+
+    def _feeder(self):
+        return self.dataset.feeder(num_workers=self.num_workers, depth=max(64, 2 * self.pair_batch))
 
     def get_predictions(self, experiment_dir, model, overwrite=False):
         """eval/hpatches.py:98-110.  Under torch.distributed every rank calls this; rank 0 writes the file."""
         pred_file = Path(experiment_dir) / "predictions.h5"
         if not pred_file.exists() or overwrite:
-            export_predictions(self.dataset.feeder(num_workers=self.num_workers, depth=max(64, 2 * self.pair_batch)), model, pred_file, keys=self.export_keys,
+            export_predictions(self._feeder(), model, pred_file, keys=self.export_keys,
                                optional_keys=self.optional_export_keys, pair_batch=self.pair_batch,
-                               view_key=self.dataset.view_key if self.pair_batch > 1 else None, shard_group=5)
+                               view_key=self.dataset.view_key if self.pair_batch > 1 else None, shard_group=self.shard_group)
         return pred_file
 
     def run_eval(self, pred_file, device="cuda"):

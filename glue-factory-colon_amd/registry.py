@@ -27,6 +27,22 @@ ALIASES = {
     "cache_loader": "cache_loader",
 }
 
+# `get_dataset(name)`: the reference's dataset names (gluefactory/datasets/__init__.py looks a module of that name up)
+# -> (module, class) of the reader this package has for them
+DATASETS = {
+    "hpatches": ("hpatches", "HPatches"),
+    "posed_images": ("posed_images", "PosedImages"),
+    "homographies": ("homographies", "HomographyPairs"),
+}
+
+
+def get_dataset(name: str):
+    key = name.rsplit(".", 1)[-1]
+    if key not in DATASETS:
+        raise RuntimeError(f"Dataset {name} not found: this package only reads {sorted(DATASETS)}")
+    module, cls = DATASETS[key]
+    return getattr(importlib.import_module(f"{_PKG}.{module}"), cls)
+
 
 def get_model(name: str):
     from .base_model import BaseModel

@@ -753,6 +753,27 @@ int gfc_preprocess_resample(const void* src, int src_kind, int B, int C, int H, 
                             int mode, int antialias, float value_scale, void* dst, float* valid, int OH, int OW,
                             void* stream);
 
+/* Perspective warp of a batch of items in one launch: the pair generator of the `homographies` dataset
+ * (gluefactory/datasets/homographies.py:37-44: cv2.warpPerspective(img, H, size) per view; :714-718 the vignette crop;
+ * :517-519 the grey sum after the warp).  UNPINNED: the rule restates OpenCV's warpPerspective with INTER_LINEAR and
+ * BORDER_CONSTANT 0 -- OpenCV is absent here, the pin is the float64 restatement of tests/warp_reference.py.
+ * src: S sources of HxW, GFC_RS_U8_HWC (interleaved HxWxC bytes converted like numpy_image_to_torch: value / 255) or
+ * GFC_RS_F32_CHW (planar CxHxW fp32); C is 1 or 3.  (left, top, cw, ch): the crop window shared by the launch; the
+ * window IS the image -- a tap outside it counts as 0 even where the plane goes on (GFC_ERR_INVALID when the window
+ * leaves the plane).  Per item b < B, on the device: src_index[b] (int32; an index outside [0, S) reads nothing and
+ * gives a zero image) and M + 9 b, nine doubles row-major, the DESTINATION -> SOURCE matrix (the inverse of the sampler's
+ * H_; the caller inverts in float64).
+ * Per destination pixel (x, y), in fp64: X = M0 x + (M1 y + M2), Y and W alike; W <- 32 / W when W != 0, else 0;
+ * fX = X W, fY = Y W saturated to the int32 range and rounded half to even -> qx, qy; source cell (qx >> 5, qy >> 5)
+ * (arithmetic shift), fractions (qx & 31) / 32, (qy & 31) / 32; the weights w00 = (1 - fx)(1 - fy), w01 = fx (1 - fy),
+ * w10 = (1 - fx) fy, w11 = fx fy are exact in fp32; out = t00 w00 + t01 w01 + t10 w10 + t11 w11 summed left to right in
+ * fp32 (t01 the tap at x + 1, t10 at y + 1).
+ * dst: fp32 [B,C,OH,OW]; with gray != 0 (needs C = 3) [B,1,OH,OW] = 0.299 r + 0.587 g + 0.114 b in fp32, left to right.
+ * No workspace, no LDS. */
+int gfc_warp_perspective(const void* src, int src_kind, int S, int C, int H, int W, int left, int top, int cw, int ch,
+                         const int* src_index, const double* M, int B, int gray, float* dst, int OH, int OW,
+                         void* stream);
+
 /* ------------------------------------------------------------------------------------
  * SuperGlue matcher (gluefactory_nonfree/superglue.py:268-322, inference path).  All fp32; rows are row-major
  * [rows,256] where the reference is channel-first Conv1d on [B,256,N]; a batch is packed as LightGlue's: the side-0
