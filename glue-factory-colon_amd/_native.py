@@ -170,6 +170,23 @@ SIGNATURES = {
     "gfc_preprocess_resample": (c_int, [c_void_p] + [c_int] * 11 + [c_float] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
     "gfc_warp_perspective": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] + [c_int] * 2
                              + [c_void_p]),
+    "gfc_sift_pyramid_layout": (c_int, [c_int] * 4 + [POINTER(c_int64)]),
+    "gfc_sift_pyramid": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 3),
+    "gfc_sift_detect_workspace_bytes": (c_size_t, [c_int] * 2),
+    "gfc_sift_detect": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_double] * 2 + [c_int]
+                        + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "gfc_sift_orient_workspace_bytes": (c_size_t, [c_int] * 2),
+    "gfc_sift_orient": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 3 + [c_int] * 2
+                        + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "gfc_sift_describe": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 3 + [c_int]
+                          + [c_void_p] * 2),
+    "gfc_sift_gray": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
+    "gfc_sift_filter_workspace_bytes": (c_size_t, [c_int] * 4),
+    "gfc_sift_filter": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 8
+                        + [c_size_t, c_void_p]),
+    "gfc_sift_extract_workspace_bytes": (c_size_t, [c_int] * 7),
+    "gfc_sift_extract": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2 + [c_int] * 2 + [c_double] * 2 + [c_int] * 7
+                         + [c_void_p] * 10 + [c_size_t, c_void_p]),
     "gfc_lg_layer_workspace_bytes": (c_size_t, [c_int]),
     "gfc_lg_layer": (c_int, [POINTER(LgParams), c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                              c_int, c_void_p, c_size_t, c_void_p]),

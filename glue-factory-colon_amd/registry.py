@@ -23,6 +23,9 @@ ALIASES = {
     "extractors.disk_kornia": "disk_kornia",
     "disk_kornia": "disk_kornia",
     "gluefactory.models.extractors.disk_kornia": "disk_kornia",
+    "extractors.sift": "sift",
+    "sift": "sift",
+    "gluefactory.models.extractors.sift": "sift",
     "two_view_pipeline": "two_view_pipeline",
     "cache_loader": "cache_loader",
 }

@@ -775,6 +775,92 @@ int gfc_warp_perspective(const void* src, int src_kind, int S, int C, int H, int
                          void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * SIFT: scale space, detection, orientation, descriptor (csrc/sift.hip).  The algorithm is the one stated in
+ * tests/sift_reference.py: Lowe's detector and descriptor with pycolmap's meaning of the reference's conf keys
+ * (gluefactory/models/extractors/sift.py:139-144).  UNPINNED: OpenCV, pycolmap and CudaSift are absent here; these
+ * are NOT their key points, the pin is the float64 restatement.
+ * Shared arguments: image fp32 [B,H,W], clipped to [0, 1] where it is read (the reference's np.clip, sift.py:208); valid_wh int32 [B,2] (w, h) on the device or NULL (every image is
+ * W x H): each image's pyramid is that of ITS OWN top-left valid region (own octave sizes, own replicate border, own
+ * number of octaves).  first_octave is -1 (2x bilinear up-sample first) or 0; num_octaves 1..8; an octave exists
+ * while its shorter side is >= 16; 3 layers per octave, 6 Gaussian and 5 DoG levels.
+ * GFC_ERR_UNSUPPORTED (nothing launched): another first_octave, num_octaves outside 1..8, a base level (H, W; doubled
+ * for first_octave -1) with a side above 16384 or a shorter side below 16.  (No level is ever narrower than a tap
+ * radius: the widest incremental blur has radius 13 and the narrowest level 16 samples; a 16-sample side under 27 taps,
+ * where both replicate borders fall inside one window, is the extreme.)
+ * Layout: per image one array of gauss_floats and one of dog_floats; octave o holds 6 (5) planes of h_o x w_o floats,
+ * row stride w_o, sized from the PADDED (H, W); an image writes and reads only its own region of each plane.  The
+ * layout call fills out[35] (int64, host): n_octaves, gauss_floats, dog_floats, then (h_o, w_o, gauss offset, dog
+ * offset) per octave. */
+int gfc_sift_pyramid_layout(int H, int W, int first_octave, int num_octaves, int64_t* out);
+/* image fp32 [B,3,H,W] -> out [B,H,W] = 0.299 r + 0.587 g + 0.114 b, summed left to right in fp32 (the package's
+ * rgb-to-grey kernel; the reference's kornia rgb_to_grayscale has the same weights). */
+int gfc_sift_gray(const float* image, float* out, int B, int H, int W, void* stream);
+/* gauss [B,gauss_floats], dog [B,dog_floats].  One launch per level: the input tile and its halo pass through LDS once,
+ * rows then columns (taps: radius ceil(4 sigma), float64 on the host, normalised, rounded to fp32), and the same launch
+ * writes the DoG level and, for level 3, every second pixel into level 0 of the next octave.  No workspace. */
+int gfc_sift_pyramid(const float* image, int B, int H, int W, const int32_t* valid_wh, int first_octave,
+                     int num_octaves, float* gauss, float* dog, void* stream);
+/* Extrema of the DoG levels (strictly above or below all 26 neighbours, |v| > 0.8 detection_threshold), refined in fp64
+ * (quadratic fit, at most 5 moves while an offset exceeds 0.6), accepted when |D| >= detection_threshold and
+ * tr^2 / det < (r + 1)^2 / r, det > 0, r = edge_threshold.  Per image at most `cap` candidates are kept: the ones
+ * beyond are counted, not stored.  Output, ordered by (octave, layer, y, x) of the integer extremum whatever the order
+ * of arrival: raw_f fp32 [B,cap,8] = (x, y, sigma, |D|, x_oct, y_oct, sigma_oct, 0) -- x, y in input pixels, corner
+ * convention (+ 0.5), sigma in input pixels, the _oct values in the octave's own pixels; raw_i int32 [B,cap,8] =
+ * (octave, layer, y, x of the extremum, layer, y, x after the moves, 0); counts int32 [B,4] = (key points, candidates
+ * found, candidates beyond cap, 0).  B <= 21845.
+ * COST LIMIT: the order is made by counting, every candidate of an image against every other -- n^2 / 2 key reads for
+ * n candidates, sized for the few thousand of a VGA image (8 700 candidates: 3.4 ms for 32 images); the top-k of the
+ * filter call below ranks its kept list the same way.  cap bounds n; a cap far above 2^16 buys quadratic time, not a
+ * faster sort (the radix select of the SuperPoint selection is not reused here). */
+size_t gfc_sift_detect_workspace_bytes(int B, int cap);
+int gfc_sift_detect(const float* dog, int B, int H, int W, const int32_t* valid_wh, int first_octave,
+                    int num_octaves, double detection_threshold, double edge_threshold, int cap, float* raw_f,
+                    int32_t* raw_i, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+/* 36-bin gradient histogram on the key point's Gaussian level (radius round(4.5 sigma_oct), weight magnitude x Gaussian
+ * of 1.5 sigma_oct, linear in the bin), smoothed six times, peaks >= 0.8 max refined parabolically: one output per peak,
+ * at most 4 per key point, in the order (key point, bin).  ori_f fp32 [B,ocap,8] = the raw record with the angle in
+ * (-pi, pi] in slot 7; ori_i int32 [B,ocap,4] = (raw index, octave, level, peak); ocounts int32 [B,2] = (written,
+ * beyond ocap).  One wave per key point; the bins are 64-bit fixed-point integers, so the sums do not depend on order. */
+size_t gfc_sift_orient_workspace_bytes(int B, int cap);
+int gfc_sift_orient(const float* gauss, int B, int H, int W, const int32_t* valid_wh, int first_octave,
+                    int num_octaves, const float* raw_f, const int32_t* raw_i, const int32_t* counts, int cap,
+                    int ocap, float* ori_f, int32_t* ori_i, int32_t* ocounts, void* ws, size_t ws_bytes,
+                    void* stream);
+/* 4 x 4 cells x 8 bins, cell width 3 sigma_oct, window rotated by the angle, trilinear, Gaussian weight of 2 cells,
+ * samples outside the level skipped; L2, clamp at 0.2, L2 (pycolmap's Normalization.L2).  desc fp32 [B,ocap,128], index
+ * (cell_y * 4 + cell_x) * 8 + bin; rows at and beyond ocounts[b][0] are not written.  One wave per key point. */
+int gfc_sift_describe(const float* gauss, int B, int H, int W, const int32_t* valid_wh, int first_octave,
+                      int num_octaves, const float* ori_f, const int32_t* ori_i, const int32_t* ocounts, int ocap,
+                      float* desc, void* stream);
+/* The reference's post-processing of a SIFT list on the device (sift.py:288-380), per image, on the oriented list of
+ * the calls above (x, y in slots 0-1, sigma 2, score 3, angle 7): the specular-mask rule (extractors/utils.py:4-42,
+ * offset 0.5; specular uint8 [B,H,W], nonzero = keep, NULL = none; cropped to the image's valid size), then
+ * filter_dog_point (sift.py:29-62; nms_radius < 0 skips it, as conf nms_radius None does; GFC_ERR_UNSUPPORTED above
+ * 16): per pixel round(p - 0.5) the largest score, among equals the smallest |angle|, then the (2 r + 1)^2 max-pool
+ * test -- planes of order-preserving integer keys built with vector atomic max / min, so the result does not depend on
+ * order -- then the k largest by score (score x sigma with scale_weighting; k <= 0: all) in torch.topk's descending
+ * order, the list order when nothing is cut.  Outputs [B,out_cap,...], out_cap >= min(k, ocap): kpts (rows at and
+ * beyond counts_out[b] are left as they are, for the padding), scales, oris, scores (0 there), desc_out (rootsift != 0:
+ * sift_to_rootsift of every row, sift.py:65-68, the padded rows included as in the reference), index int32 (row of the
+ * oriented list, -1 beyond the count), counts_out int32 [B]. */
+size_t gfc_sift_filter_workspace_bytes(int B, int H, int W, int ocap);
+int gfc_sift_filter(const float* ori_f, const float* desc, const int32_t* ocounts, int B, int ocap, int H, int W,
+                    const int32_t* valid_wh, const unsigned char* specular, int nms_radius, int scale_weighting, int k,
+                    int rootsift, int out_cap, float* kpts, float* scales, float* oris, float* scores, float* desc_out,
+                    int32_t* index, int32_t* counts_out, void* ws, size_t ws_bytes, void* stream);
+/* The stages above in sequence on one stream -- pyramid, detect, orient, describe, filter -- with every intermediate in
+ * ONE workspace and no host read in between: the same launches as the separate calls with the same cap and ocap, hence
+ * the same bits.  counts [B,4] and ocounts [B,2] are those of detect and orient (the candidates beyond cap and the
+ * orientations beyond ocap are counted there, never dropped silently); the other outputs are the filter's.  The
+ * workspace holds both pyramids, the raw and the oriented list, B x ocap descriptors and the largest stage scratch. */
+size_t gfc_sift_extract_workspace_bytes(int B, int H, int W, int first_octave, int num_octaves, int cap, int ocap);
+int gfc_sift_extract(const float* image, int B, int H, int W, const int32_t* valid_wh, const unsigned char* specular,
+                     int first_octave, int num_octaves, double detection_threshold, double edge_threshold, int cap,
+                     int ocap, int nms_radius, int scale_weighting, int k, int rootsift, int out_cap, float* kpts,
+                     float* scales, float* oris, float* scores, float* desc_out, int32_t* index, int32_t* counts_out,
+                     int32_t* counts, int32_t* ocounts, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * SuperGlue matcher (gluefactory_nonfree/superglue.py:268-322, inference path).  All fp32; rows are row-major
  * [rows,256] where the reference is channel-first Conv1d on [B,256,N]; a batch is packed as LightGlue's: the side-0
  * rows of every pair, then the side-1 rows.
