@@ -12,16 +12,8 @@
 //     -> descriptors read at the integer pixel, L2-normalised over D (F.normalize, eps 1e-12).
 // HBM-bound byte / index work: coalesced row reads, LDS halo tile for the window test, one workgroup per image for
 // the order-preserving compaction (wave-contiguous segments of the map, then a compact survivor list).
+#include "block_select.h"
 #include "common.h"
-
-__device__ __forceinline__ unsigned int dk_order_bits(float f) {
-  unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dk_from_order_bits(unsigned int o) {
-  unsigned int u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-  return __uint_as_float(u);
-}
 
 #define DK_T 32  // output tile edge
 
@@ -71,11 +63,11 @@ __global__ __launch_bounds__(1024) void disk_select_kernel(const float* __restri
                                                            float* __restrict__ kpts, float* __restrict__ kscores,
                                                            int* __restrict__ counts, int* __restrict__ list_idx_all,
                                                            float* __restrict__ list_sc_all) {
-  __shared__ unsigned int hist[256];
-  __shared__ unsigned int s_prefix, s_want;
-  __shared__ unsigned int wsum[16];
+  __shared__ int hist[256];
+  __shared__ unsigned int s_prefix;
+  __shared__ int s_want;
+  __shared__ int wsum[4];
   __shared__ int wave_cnt[16];
-  __shared__ int s_base;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int total = H * W;
   const float* src = cand + (size_t)b * total;
@@ -93,7 +85,7 @@ __global__ __launch_bounds__(1024) void disk_select_kernel(const float* __restri
       v[u] = i < s1 ? src[i] : -INFINITY;
     }
 #pragma unroll
-    for (int u = 0; u < DKS_U; ++u) c += __popcll(__ballot(v[u] > -INFINITY));
+    for (int u = 0; u < DKS_U; ++u) c += gfc_wave_count(v[u] > -INFINITY);
   }
   if (lane == 0) wave_cnt[wave] = c;
   __syncthreads();
@@ -114,13 +106,13 @@ __global__ __launch_bounds__(1024) void disk_select_kernel(const float* __restri
 #pragma unroll
     for (int u = 0; u < DKS_U; ++u) {
       const bool keep = v[u] > -INFINITY;
-      const unsigned long long bal = __ballot(keep);
+      int kept;
+      const int slot = base + gfc_wave_rank(keep, kept);
       if (keep) {
-        const int slot = base + __popcll(bal & ((1ull << lane) - 1ull));
         list_idx[slot] = i0 + u * 64 + lane;
         list_sc[slot] = v[u];
       }
-      base += __popcll(bal);
+      base += kept;
     }
   }
   __threadfence();
@@ -131,75 +123,31 @@ __global__ __launch_bounds__(1024) void disk_select_kernel(const float* __restri
     if (count == 0) {
       drop_all = true;  // (torch.kthvalue on an empty tensor raises in the reference; nothing to return either way)
     } else {
-      // threshold = the k-th largest survivor, k = min(n + 1, count): MSB-first radix select on the order bits; the
-      // bin that holds it is found by a 256-thread scan (all four passes run: the threshold is an exact score)
-      if (tid == 0) { s_prefix = 0u; s_want = (unsigned int)min(n + 1, count); }
-      __syncthreads();
-      for (int shift = 24; shift >= 0; shift -= 8) {
-        if (tid < 256) hist[tid] = 0;
-        const unsigned int prefix = s_prefix, want = s_want;
-        __syncthreads();
-        const unsigned int hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
-        for (int i = tid; i < count; i += 1024) {
-          const unsigned int o = dk_order_bits(list_sc[i]);
-          if ((o & hi_mask) == prefix) atomicAdd(&hist[(o >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        unsigned int hv = 0, inc = 0;
-        if (tid < 256) {  // waves 0..3, whole waves; bins in descending order
-          hv = hist[255 - tid];
-          inc = hv;
-#pragma unroll
-          for (int o = 1; o < 64; o <<= 1) {
-            const unsigned int up = __shfl_up(inc, o);
-            if (lane >= o) inc += up;
-          }
-          if (lane == 63) wsum[wave] = inc;
-        }
-        __syncthreads();
-        if (tid < 256) {
-          for (int i = 0; i < wave; ++i) inc += wsum[i];
-          if (inc >= want && inc - hv < want) {  // the first bin from the top whose running count reaches `want`
-            s_prefix = prefix | ((unsigned int)(255 - tid) << shift);
-            s_want = want - (inc - hv);
-          }
-        }
-        __syncthreads();
-      }
-      thr = dk_from_order_bits(s_prefix);
+      // threshold = the k-th largest survivor, k = min(n + 1, count): radix select on the order bits (block_select.h)
+      // WITHOUT the early stop -- all four passes run, because the threshold is used as an exact score
+      thr = gfc_from_order_bits(gfc_block_radix_select<unsigned int, false, 1024>(
+          [&](unsigned int i) { return gfc_order_bits(list_sc[i]); }, (unsigned int)count,
+          (unsigned int)min(n + 1, count), hist, wsum, &s_prefix, &s_want));
     }
   }
   // ---- ordered filter of the list: {score > thr} in row-major order, clipped to the first `lim` ----
   const int lim = n >= 0 ? min(n, cap) : cap;
-  if (tid == 0) s_base = 0;
-  __syncthreads();
-  for (int i0 = 0; i0 < count; i0 += 1024) {
+  int kept = 0;
+  for (int i0 = 0; i0 < count && kept < lim; i0 += 1024) {  // uniform
     const int i = i0 + tid;
     const float v = i < count ? list_sc[i] : -INFINITY;
     const bool keep = !drop_all && i < count && v > thr;
-    const unsigned long long bal = __ballot(keep);
-    const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_cnt[wave] = __popcll(bal);
-    __syncthreads();
-    int off = s_base, all = 0;
-    for (int w = 0; w < 16; ++w) {
-      const int t = wave_cnt[w];
-      if (w < wave) off += t;
-      all += t;
-    }
-    const int slot = off + in_wave;
+    int all;
+    const int slot = kept + gfc_block_rank<16>(keep, wave_cnt, all);
     if (keep && slot < lim) {
       const int idx = list_idx[i];
       kpts[((size_t)b * cap + slot) * 2] = (float)(idx % W);
       kpts[((size_t)b * cap + slot) * 2 + 1] = (float)(idx / W);
       kscores[(size_t)b * cap + slot] = v;
     }
-    __syncthreads();
-    if (tid == 0) s_base += all;
-    __syncthreads();
-    if (s_base >= lim) break;  // uniform
+    kept += all;
   }
-  if (tid == 0) counts[b] = min(s_base, lim);
+  if (tid == 0) counts[b] = min(kept, lim);
 }
 
 // survivor map [B,H,W] | survivor list: index [B,H*W] | score [B,H*W]

@@ -9,6 +9,7 @@
 // Plain vector loads and stores only; every output element has exactly one writer, so nothing is atomic.
 #include <climits>
 
+#include "block_select.h"
 #include "common.h"
 #include "lg_rowdot.h"
 
@@ -74,23 +75,6 @@ __global__ __launch_bounds__(256) void adaptive_count_kernel(const int32_t* __re
   }
 }
 
-// inclusive scan over the 256 threads of the workgroup
-__device__ __forceinline__ int block_scan256(int v, int* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = 1; o < 256; o <<= 1) {
-    const int a = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += a;
-    __syncthreads();
-  }
-  const int r = sh[t];
-  __syncthreads();
-  return r;
-}
-
 // one workgroup, thread t = pair t (B <= 128).  plan[t] = {first output row of side 0, of side 1, copy-all flag, 0}.
 __global__ __launch_bounds__(256) void adaptive_plan_kernel(const int32_t* __restrict__ seg,
                                                             const int32_t* __restrict__ pairs, int B, int rows,
@@ -99,7 +83,7 @@ __global__ __launch_bounds__(256) void adaptive_plan_kernel(const int32_t* __res
                                                             int32_t* __restrict__ plan, int32_t* __restrict__ seg_out,
                                                             int32_t* __restrict__ pairs_out, int32_t* __restrict__ self_p,
                                                             int32_t* __restrict__ cross_p) {
-  __shared__ int sh[256];
+  __shared__ int s_wave[4];
   __shared__ int s_cnt[256];
   const int t = threadIdx.x;
   int state = GFC_LG_ADAPTIVE_LIVE, c0 = 0, c1 = 0, cnt = 0, live = 0;
@@ -127,8 +111,8 @@ __global__ __launch_bounds__(256) void adaptive_plan_kernel(const int32_t* __res
     }
     live = state == GFC_LG_ADAPTIVE_LIVE;
   }
-  const int incl = block_scan256(live, sh);
-  const int n_live = sh[255];
+  int n_live, n_rows;
+  const int incl = gfc_block_scan_excl<4>(live, s_wave, n_live) + live;
   // live pairs keep their order in front, finished pairs keep theirs behind them
   const int pos = live ? incl - 1 : n_live + (t - incl);
   s_cnt[t] = 0;
@@ -136,7 +120,7 @@ __global__ __launch_bounds__(256) void adaptive_plan_kernel(const int32_t* __res
   if (t < B) { s_cnt[2 * pos] = c0; s_cnt[2 * pos + 1] = c1; }
   __syncthreads();
   const int mine = s_cnt[t];
-  const int off = block_scan256(mine, sh) - mine;  // exclusive, in output order
+  const int off = gfc_block_scan_excl<4>(mine, s_wave, n_rows);  // in output order
   s_cnt[t] = off;
   __syncthreads();
   if (t >= B) return;
@@ -154,8 +138,8 @@ __global__ __launch_bounds__(256) void adaptive_plan_kernel(const int32_t* __res
 }
 
 // grid (chunks, 2B): workgroup (c, s) packs the 256-row chunks c, c + gridDim.x, ... of segment s.  Destination of a kept
-// row = first output row of the segment + kept rows before it: ballot + popcount inside the wave, wave totals through
-// LDS, and a running base over the part of the segment in front of the chunk.
+// row = first output row of the segment + kept rows before it: the rank inside the chunk (block_select.h) and a running
+// base over the part of the segment in front of the chunk.
 __global__ __launch_bounds__(256) void adaptive_pack_kernel(
     const float* __restrict__ x, const float* __restrict__ cosb, const float* __restrict__ sinb,
     const int32_t* __restrict__ ind, int rows, const int32_t* __restrict__ seg, const int32_t* __restrict__ pairs,
@@ -190,21 +174,13 @@ __global__ __launch_bounds__(256) void adaptive_pack_kernel(
     }
     const int i = c0 + t;
     const bool k = i < n && (all || (flags[row0 + i] & FLAG_KEEP));
-    const unsigned long long m = __ballot(k);
-    const int pre = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[w] = __popcll(m);
-    __syncthreads();
-    int wbase = 0, total = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = s_wave[j];
-      if (j < w) wbase += c;
-      total += c;
-    }
+    // slot among the kept rows of the chunk.  The barriers inside the rank also put this chunk's writes of s_wave and
+    // s_src behind every read of the chunk before, so the loop body needs no barrier at its end.
+    int total;
+    const int j = gfc_block_rank<4>(k, s_wave, total);
     // the output buffers hold `rows` rows: a consistent table never asks for more (kept <= live), an inconsistent one is cut
     total = max(0, min(total, rows - (dst0 + base)));
-    if (k && wbase + pre < total) {
-      const int j = wbase + pre;
+    if (k && j < total) {
       s_src[j] = t;
       const int id = ind[row0 + i];
       ind_out[dst0 + base + j] = id;
@@ -232,7 +208,6 @@ __global__ __launch_bounds__(256) void adaptive_pack_kernel(
     }
     base += total;
     counted = c0 + 256;
-    __syncthreads();
   }
 }
 

@@ -12,6 +12,7 @@
 //                          hypothesis, packed index h, squared forward transfer error, thresholds squared on the host.
 //   ransac_lo_kernel       one workgroup per (pair, threshold): merge the ranges (score, then h), re-solve the winner,
 //                          up to lo_iters rounds of {inliers -> DLT -> accept iff the MSAC score drops}, outputs.
+#include "block_select.h"
 #include "ransac_common.h"
 
 #define RS_DET_EPS 1e-10
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(EM_THREADS) void ransac_compact_kernel(const float*
                                                                     float4* __restrict__ corr, int* __restrict__ cidx,
                                                                     int* __restrict__ cnt) {
   __shared__ int wsum[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const float* p0 = kp0 + (size_t)b * M * 2;
   const float* p1 = kp1 + (size_t)b * N * 2;
   const long long* mm = m0 + (size_t)b * M;
@@ -148,20 +149,13 @@ __global__ __launch_bounds__(EM_THREADS) void ransac_compact_kernel(const float*
     long long j = -1;
     if (i < M) j = mm[i];
     const bool valid = (i < M) && j > -1 && j < N;
-    const unsigned long long bal = __ballot(valid);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wave; ++w) off += wsum[w];
-    const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    int total;
+    const int pos = base + gfc_block_rank<EM_THREADS / 64>(valid, wsum, total);  // < M: at most one slot per valid i
     if (valid) {
-      const int pos = off + before;  // < M: at most one slot per valid i
       cc[pos] = make_float4(p0[2 * i], p0[2 * i + 1], p1[2 * j], p1[2 * j + 1]);
       ci[pos] = i;
     }
     base += total;
-    __syncthreads();
   }
   if (tid == 0) cnt[b] = base;
 }

@@ -22,6 +22,7 @@
 //          addition commutes, so the sums do not depend on the order in which the lanes arrive.
 #include <math.h>
 
+#include "block_select.h"
 #include "common.h"
 
 namespace {
@@ -278,37 +279,20 @@ __global__ __launch_bounds__(256) void sift_refine_kernel(const float* __restric
   flag[slot] = 1;
 }
 
-// exclusive scan of one value per thread over a block of 1024; `total` is the block's sum
-__device__ __forceinline__ int block_scan_1024(int v, int* lds, int& total) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const int a = t >= d ? lds[t - d] : 0;
-    __syncthreads();
-    lds[t] += a;
-    __syncthreads();
-  }
-  const int incl = lds[t];
-  total = lds[1023];
-  __syncthreads();
-  return incl - v;
-}
-
 __global__ __launch_bounds__(1024) void sift_compact_kernel(int cap, const float* __restrict__ tmp_f,
                                                             const int32_t* __restrict__ tmp_i, const int32_t* __restrict__ flag,
                                                             float* __restrict__ raw_f, int32_t* __restrict__ raw_i,
                                                             int32_t* __restrict__ counts) {
-  __shared__ int lds[1024];
+  __shared__ int wave_lds[16];
   const int b = blockIdx.x;
   const int found = counts[4 * b + 1], n = min(found, cap);
   int done = 0;
   for (int i0 = 0; i0 < n; i0 += 1024) {
     const int i = i0 + threadIdx.x;
     const size_t slot = (size_t)b * cap + i;
-    const int f = i < n ? flag[slot] : 0;
+    const bool f = i < n && flag[slot];
     int total;
-    const int at = done + block_scan_1024(f, lds, total);
+    const int at = done + gfc_block_rank<16>(f, wave_lds, total);
     if (f) {
       const size_t out = (size_t)b * cap + at;
       for (int k = 0; k < 8; ++k) { raw_f[out * 8 + k] = tmp_f[slot * 8 + k]; raw_i[out * 8 + k] = tmp_i[slot * 8 + k]; }
@@ -402,15 +386,15 @@ __global__ __launch_bounds__(256) void sift_orient_kernel(const float* __restric
   const float hm = __shfl(hv, lm), hp = __shfl(hv, lp);
   const float top = wave_max(lane < 36 ? hv : -INFINITY);
   const bool peak = lane < 36 && top > 0.f && hv > hm && hv > hp && hv >= 0.8f * top;
-  const unsigned long long mask = __ballot(peak);
-  const int before = __popcll(mask & ((1ull << lane) - 1ull));
+  int peaks;
+  const int before = gfc_wave_rank(peak, peaks);
   if (peak && before < 4) {
     const float di = -0.5f * (hp - hm) / (hp + hm - 2.f * hv);
     float th = 6.283185307179586f * ((float)lane + di + 0.5f) / 36.f;
     if (th > 3.141592653589793f) th -= 6.283185307179586f;
     angles[rec * 4 + before] = th;
   }
-  if (lane == 0) n_ori[rec] = min(__popcll(mask), 4);
+  if (lane == 0) n_ori[rec] = min(peaks, 4);
 }
 
 __global__ __launch_bounds__(1024) void sift_orient_compact_kernel(int cap, int ocap, const float* __restrict__ raw_f,
@@ -419,7 +403,7 @@ __global__ __launch_bounds__(1024) void sift_orient_compact_kernel(int cap, int 
                                                                    const int32_t* __restrict__ n_ori,
                                                                    const float* __restrict__ angles, float* __restrict__ ori_f,
                                                                    int32_t* __restrict__ ori_i, int32_t* __restrict__ ocounts) {
-  __shared__ int lds[1024];
+  __shared__ int wave_lds[16];
   const int b = blockIdx.x;
   const int n = min(counts[4 * b], cap);
   int done = 0;
@@ -428,7 +412,7 @@ __global__ __launch_bounds__(1024) void sift_orient_compact_kernel(int cap, int 
     const size_t rec = (size_t)b * cap + i;
     const int k = i < n ? n_ori[rec] : 0;
     int total;
-    const int at = done + block_scan_1024(k, lds, total);
+    const int at = done + gfc_block_scan_excl<16>(k, wave_lds, total);
     for (int j = 0; j < k; ++j) {
       if (at + j >= ocap) break;
       const size_t out = (size_t)b * ocap + at + j;
@@ -733,14 +717,14 @@ __global__ __launch_bounds__(256) void sift_filter_mark_kernel(int phase, const 
 __global__ __launch_bounds__(1024) void sift_filter_compact_kernel(int ocap, const int32_t* __restrict__ ocounts,
                                                                    const int32_t* __restrict__ flag, int32_t* __restrict__ kept,
                                                                    int32_t* __restrict__ m) {
-  __shared__ int lds[1024];
+  __shared__ int wave_lds[16];
   const int b = blockIdx.x, n = min(ocounts[2 * b], ocap);
   int done = 0;
   for (int i0 = 0; i0 < n; i0 += 1024) {
     const int i = i0 + threadIdx.x;
-    const int f = i < n ? flag[(size_t)b * ocap + i] : 0;
+    const bool f = i < n && flag[(size_t)b * ocap + i];
     int total;
-    const int at = done + block_scan_1024(f, lds, total);
+    const int at = done + gfc_block_rank<16>(f, wave_lds, total);
     if (f) kept[(size_t)b * ocap + at] = i;
     done += total;
   }

@@ -1,5 +1,6 @@
 // SuperPoint detection tail: heat-map decode, NMS, key-point selection, descriptor sampling.
 // All HBM-bound byte/compare work: coalesced loads into LDS, wavefront reductions, no GEMM shapes.
+#include "block_select.h"
 #include "common.h"
 
 #include <type_traits>
@@ -20,16 +21,6 @@
 // ------------------------------------------------------------------------------------------
 #define NT 64
 #define NR_MAX 4
-
-// order-preserving float -> uint map (selection keys)
-__device__ __forceinline__ unsigned int float_order_bits(float f) {
-  unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float float_from_order_bits(unsigned int o) {
-  unsigned int u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-  return __uint_as_float(u);
-}
 
 // (no NaNs reach the pools: one v_max_f32 / v_max3_f32 instead of compare + select; the keep masks are 0 / 1 bytes)
 __device__ __forceinline__ float window_max(float a, float b) { return fmaxf(a, b); }
@@ -174,7 +165,7 @@ __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ hea
         const int i = tid + it * 1024;
         const unsigned int idx = (unsigned int)((ty * NT + i / NT) * W + tx * NT + i % NT);
         cand[(size_t)b * H * W + tile_base + slots[it]] =
-            ((unsigned long long)float_order_bits(vals[it]) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+            ((unsigned long long)gfc_order_bits(vals[it]) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
       }
     }
   }
@@ -368,7 +359,7 @@ __global__ __launch_bounds__(256) void nms_stream_kernel(const float* __restrict
           if (c) {
             const unsigned int idx = (unsigned int)(y * W + col);
             cb[ccnt + __popcll(mask & ((1ull << lane) - 1ull))] =
-                ((unsigned long long)float_order_bits(v) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+                ((unsigned long long)gfc_order_bits(v) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
           }
           ccnt += n;
         }
@@ -402,7 +393,7 @@ __global__ void nms_r0_kernel(const float* __restrict__ heat, int H, int W, int 
   if (cand && v > cand_thr) {
     const int slot = atomicAdd(&cand_count[b], 1);
     cand[(size_t)b * H * W + slot] =
-        ((unsigned long long)float_order_bits(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned int)i);
+        ((unsigned long long)gfc_order_bits(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned int)i);
   }
 }
 
@@ -475,41 +466,17 @@ extern "C" int gfc_sp_nms(const float* heatmap, int B, int H, int W, int radius,
 #define SEL_THREADS 1024
 #define SEL_MAXK 8192
 
-
-__device__ __forceinline__ unsigned int block_exclusive_scan(unsigned int v, unsigned int* total, unsigned int* wsum) {
-  // 1024 threads = 16 waves; returns exclusive prefix of v, *total = block sum
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    unsigned int n = __shfl_up(inc, o);
-    if (lane >= o) inc += n;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  unsigned int base = 0, tot = 0;
-  for (int i = 0; i < SEL_THREADS / 64; ++i) {
-    unsigned int w = wsum[i];
-    if (i < wave) base += w;
-    tot += w;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
 __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const float* __restrict__ scores, int H, int W, float th,
                                                              int k, int cap, float* __restrict__ kpts,
                                                              float* __restrict__ kscores, int* __restrict__ counts,
                                                              unsigned long long* __restrict__ cand_all,
                                                              const int* __restrict__ precount) {
   __shared__ unsigned long long keys[SEL_MAXK];
-  __shared__ unsigned int hist[256];
-  __shared__ unsigned int wsum[SEL_THREADS / 64];
+  __shared__ int hist[256];
+  __shared__ int wsum[SEL_THREADS / 64];
   __shared__ unsigned int sh_cnt;
   __shared__ unsigned long long sh_prefix;
-  __shared__ unsigned int sh_remaining;
-  __shared__ unsigned int sh_done;
+  __shared__ int sh_state[2];  // radix select: what is still wanted, done
   const int b = blockIdx.x, tid = threadIdx.x;
   const long long HW = (long long)H * W;
   const float* sb = scores + (size_t)b * HW;
@@ -527,13 +494,13 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const float* __rest
       v[j] = (i < HW) ? sb[i] : -INFINITY;
       if (i < HW && v[j] > th) flags |= 1u << j;
     }
-    unsigned int cnt = __popc(flags), tot;
-    unsigned int off = n + block_exclusive_scan(cnt, &tot, wsum);
+    int tot;
+    unsigned int off = n + gfc_block_scan_excl<SEL_THREADS / 64>(__popc(flags), wsum, tot);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (flags & (1u << j)) {
         unsigned int idx = (unsigned int)(i0 + j);
-        cand[off++] = ((unsigned long long)float_order_bits(v[j]) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+        cand[off++] = ((unsigned long long)gfc_order_bits(v[j]) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
       }
     n += tot;
   }
@@ -541,101 +508,49 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const float* __rest
 
   float* kp = kpts + (size_t)b * cap * 2;
   float* ks = kscores + (size_t)b * cap;
+  // key = score bits << 32 | ~pixel index -> key point i; every exit zero-fills [count, cap)
+  auto write_point = [&](unsigned int i, unsigned long long key) {
+    const unsigned int idx = 0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull);
+    kp[2 * i] = (float)(idx % W);
+    kp[2 * i + 1] = (float)(idx / W);
+    ks[i] = gfc_from_order_bits((unsigned int)(key >> 32));
+  };
+  auto finish = [&](unsigned int count) {
+    for (unsigned int i = count + tid; i < (unsigned int)cap; i += SEL_THREADS) {
+      kp[2 * i] = 0.f; kp[2 * i + 1] = 0.f; ks[i] = 0.f;
+    }
+    if (tid == 0) counts[b] = (int)count;
+  };
   if (precount && n <= (unsigned int)k) {
     // candidates arrived unordered: restore the row-major order (ascending pixel index = descending low word)
     unsigned int P = 1;
     while (P < n) P <<= 1;
     for (unsigned int i = tid; i < P; i += SEL_THREADS) {
       const unsigned long long key = i < n ? cand[i] : 0ull;
-      keys[i] = i < n ? ((key & 0xFFFFFFFFull) << 32) | (key >> 32) : 0ull;  // (~idx, score bits)
+      keys[i] = i < n ? (key << 32) | (key >> 32) : 0ull;  // (~idx, score bits)
     }
     __syncthreads();
-    for (unsigned int sz = 2; sz <= P; sz <<= 1)
-      for (unsigned int st = sz >> 1; st > 0; st >>= 1) {
-        for (unsigned int i = tid; i < P / 2; i += SEL_THREADS) {
-          unsigned int lo = (i / st) * (st * 2) + (i % st), hi = lo + st;
-          bool desc = ((lo & sz) == 0);
-          unsigned long long a = keys[lo], c = keys[hi];
-          if ((a < c) == desc) { keys[lo] = c; keys[hi] = a; }
-        }
-        __syncthreads();
-      }
-    for (unsigned int i = tid; i < n; i += SEL_THREADS) {
-      const unsigned long long key = keys[i];
-      const unsigned int idx = 0xFFFFFFFFu - (unsigned int)(key >> 32);
-      kp[2 * i] = (float)(idx % W);
-      kp[2 * i + 1] = (float)(idx / W);
-      ks[i] = float_from_order_bits((unsigned int)(key & 0xFFFFFFFFull));
-    }
-    for (unsigned int i = n + tid; i < (unsigned int)cap; i += SEL_THREADS) {
-      kp[2 * i] = 0.f; kp[2 * i + 1] = 0.f; ks[i] = 0.f;
-    }
-    if (tid == 0) counts[b] = (int)n;
+    gfc_block_bitonic_desc<SEL_THREADS>(keys, P);
+    for (unsigned int i = tid; i < n; i += SEL_THREADS) write_point(i, (keys[i] << 32) | (keys[i] >> 32));
+    finish(n);
     return;
   }
   if (k < 0 || n <= (unsigned int)k) {
     // all candidates, row-major (unsorted)
     unsigned int cnt = min(n, (unsigned int)cap);
-    for (unsigned int i = tid; i < cnt; i += SEL_THREADS) {
-      unsigned long long key = cand[i];
-      unsigned int idx = 0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull);
-      kp[2 * i] = (float)(idx % W);
-      kp[2 * i + 1] = (float)(idx / W);
-      ks[i] = float_from_order_bits((unsigned int)(key >> 32));
-    }
-    for (unsigned int i = cnt + tid; i < (unsigned int)cap; i += SEL_THREADS) {
-      kp[2 * i] = 0.f; kp[2 * i + 1] = 0.f; ks[i] = 0.f;
-    }
-    if (tid == 0) counts[b] = (int)cnt;
+    for (unsigned int i = tid; i < cnt; i += SEL_THREADS) write_point(i, cand[i]);
+    finish(cnt);
     return;
   }
 
-  // ---- radix select: find the k-th largest key ----
-  // Per pass: a 256-bin histogram of the next byte of the keys that still match the prefix, then the bin that holds the
-  // k-th key -- found by 256 threads (inclusive scan over the bins in descending order; a serial walk by one thread
-  // costs a dependent LDS read per bin, ~10 k cycles per pass).  When the bin's count equals what is still missing, ALL
-  // its keys are winners: k-th = prefix with the lower bytes zero, and the remaining passes are skipped (the low word
-  // is the unique pixel index, so this happens at the latest once the score bytes are through, unless scores tie).
-  if (tid == 0) { sh_prefix = 0ull; sh_remaining = (unsigned int)k; sh_done = 0u; }
-  __syncthreads();
-  for (int pass = 7; pass >= 0; --pass) {
-    const int shift = pass * 8;
-    if (tid < 256) hist[tid] = 0;
-    const unsigned long long prefix = sh_prefix;
-    const unsigned int rem = sh_remaining;
-    __syncthreads();
-    const unsigned long long himask = (pass == 7) ? 0ull : (~0ull << (shift + 8));
-    for (unsigned int i = tid; i < n; i += SEL_THREADS) {
-      unsigned long long key = cand[i];
-      if ((key & himask) == prefix) atomicAdd(&hist[(unsigned int)(key >> shift) & 0xFF], 1u);
-    }
-    __syncthreads();
-    unsigned int v = 0, inc = 0;
-    if (tid < 256) {  // waves 0..3, whole waves
-      v = hist[255 - tid];  // bins in descending order
-      inc = v;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        unsigned int up = __shfl_up(inc, o);
-        if ((tid & 63) >= o) inc += up;
-      }
-      if ((tid & 63) == 63) wsum[tid >> 6] = inc;
-    }
-    __syncthreads();
-    if (tid < 256) {
-      for (int i = 0; i < (tid >> 6); ++i) inc += wsum[i];
-      if (inc >= rem && inc - v < rem) {  // exactly one bin: the first (from the top) whose running count reaches rem
-        sh_prefix = prefix | ((unsigned long long)(255 - tid) << shift);
-        sh_remaining = rem - (inc - v);
-        sh_done = (inc == rem) ? 1u : 0u;
-      }
-    }
-    __syncthreads();
-    if (sh_done) break;  // uniform
-  }
-  const unsigned long long kth = sh_prefix;  // exactly k keys are >= kth (keys are unique)
+  // ---- radix select: find the k-th largest key (block_select.h) ----
+  // With the early stop: when a bin's count equals what is still missing, ALL its keys are winners: k-th = prefix with
+  // the lower bytes zero, and the remaining passes are skipped (the low word is the unique pixel index, so this happens
+  // at the latest once the score bytes are through, unless scores tie).
   if (tid == 0) sh_cnt = 0;
-  __syncthreads();
+  const unsigned long long kth = gfc_block_radix_select<unsigned long long, true, SEL_THREADS>(
+      [&](unsigned int i) { return cand[i]; }, n, (unsigned int)k, hist, wsum, &sh_prefix, sh_state);
+  // exactly k keys are >= kth (keys are unique)
   for (unsigned int i = tid; i < n; i += SEL_THREADS) {
     unsigned long long key = cand[i];
     if (key >= kth) {
@@ -649,29 +564,9 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const float* __rest
   __syncthreads();
   for (unsigned int i = (unsigned int)k + tid; i < P; i += SEL_THREADS) keys[i] = 0ull;
   __syncthreads();
-  for (unsigned int sz = 2; sz <= P; sz <<= 1) {
-    for (unsigned int st = sz >> 1; st > 0; st >>= 1) {
-      for (unsigned int i = tid; i < P / 2; i += SEL_THREADS) {
-        unsigned int lo = (i / st) * (st * 2) + (i % st);
-        unsigned int hi = lo + st;
-        bool desc = ((lo & sz) == 0);
-        unsigned long long a = keys[lo], c = keys[hi];
-        if ((a < c) == desc) { keys[lo] = c; keys[hi] = a; }
-      }
-      __syncthreads();
-    }
-  }
-  for (unsigned int i = tid; i < (unsigned int)k; i += SEL_THREADS) {
-    unsigned long long key = keys[i];
-    unsigned int idx = 0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull);
-    kp[2 * i] = (float)(idx % W);
-    kp[2 * i + 1] = (float)(idx / W);
-    ks[i] = float_from_order_bits((unsigned int)(key >> 32));
-  }
-  for (unsigned int i = (unsigned int)k + tid; i < (unsigned int)cap; i += SEL_THREADS) {
-    kp[2 * i] = 0.f; kp[2 * i + 1] = 0.f; ks[i] = 0.f;
-  }
-  if (tid == 0) counts[b] = k;
+  gfc_block_bitonic_desc<SEL_THREADS>(keys, P);
+  for (unsigned int i = tid; i < (unsigned int)k; i += SEL_THREADS) write_point(i, keys[i]);
+  finish((unsigned int)k);
 }
 
 // candidate keys [B][H*W], behind the per-image counters [B] of the fused path
@@ -892,16 +787,14 @@ __global__ __launch_bounds__(FK_THREADS) void filter_keypoints_kernel(float* __r
                                                                       const unsigned char* __restrict__ mask, int Hm, int Wm,
                                                                       const int* __restrict__ wh, float offset) {
   __shared__ int wave_tot[FK_THREADS / 64];
-  __shared__ int base_s;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   float* kp = kpts + (size_t)b * cap * 2;
   float* ks = kscores + (size_t)b * cap;
   const unsigned char* m = mask + (size_t)b * Hm * Wm;
   int eh = Hm, ew = Wm;
   if (wh) { ew = min(ew, wh[2 * b]); eh = min(eh, wh[2 * b + 1]); }
   const int n = min(counts[b], cap);
-  if (tid == 0) base_s = 0;
-  __syncthreads();
+  int base = 0;
   for (int start = 0; start < n; start += FK_THREADS) {
     const int i = start + tid;
     float x = 0.f, y = 0.f, s = 0.f;
@@ -913,22 +806,14 @@ __global__ __launch_bounds__(FK_THREADS) void filter_keypoints_kernel(float* __r
       if (x0 >= 0 && x1 < ew && y0 >= 0 && y1 < eh)
         keep = m[(size_t)y0 * Wm + x0] && m[(size_t)y0 * Wm + x1] && m[(size_t)y1 * Wm + x0] && m[(size_t)y1 * Wm + x1];
     }
-    const unsigned long long bal = __ballot(keep);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(bal);
-    __syncthreads();  // all loads of this chunk are done, wave totals visible
-    int off = base_s;
-    for (int w = 0; w < wave; ++w) off += wave_tot[w];
-    if (keep) { kp[2 * (off + before)] = x; kp[2 * (off + before) + 1] = y; ks[off + before] = s; }
-    __syncthreads();
-    if (tid == 0) {
-      int t = 0;
-      for (int w = 0; w < FK_THREADS / 64; ++w) t += wave_tot[w];
-      base_s += t;
-    }
-    __syncthreads();
+    // in place: the barriers inside the rank put all loads of this chunk before any store of it (a store lands at or
+    // below its own load, so it never reaches the chunks still to be read)
+    int total;
+    const int at = base + gfc_block_rank<FK_THREADS / 64>(keep, wave_tot, total);
+    if (keep) { kp[2 * at] = x; kp[2 * at + 1] = y; ks[at] = s; }
+    base += total;
   }
-  if (tid == 0) counts[b] = base_s;
+  if (tid == 0) counts[b] = base;
 }
 
 extern "C" int gfc_sp_filter_keypoints(float* kpts, float* kscores, int32_t* counts, int B, int cap, const uint8_t* mask,

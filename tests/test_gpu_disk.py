@@ -54,6 +54,49 @@ def test_disk_nms_select_vs_oracle(h, w, n, window, cutoff):
                                    nat.ptr(ws), ws.numel(), None) == 1  # even window: invalid, as kornia raises
 
 
+def planted_heatmaps(c, seed, h=56, w=64):
+    """[2,1,h,w], -1 except c seeded pixels above the cutoff 0: image 0 with c distinct scores, image 1 the same with
+    its lowest five equal."""
+    g = torch.Generator().manual_seed(seed)
+    heat = torch.full((2, 1, h * w), -1.0)
+    for i in range(2):
+        v = (torch.randperm(c, generator=g) + 1).float() / 4096  # exact in fp32, all different
+        if i == 1:
+            v[v <= 5 / 4096] = 5 / 4096
+        heat[i, 0, torch.randperm(h * w, generator=g)[:c]] = v
+    return heat.reshape(2, 1, h, w)
+
+
+@pytest.mark.parametrize("c", [1, 64, 65, 1024, 1025, 3000])
+def test_disk_select_counts_at_wave_and_chunk_boundaries(c):
+    """Window 1 (the NMS is the identity), exactly c survivors, n = c - 1, c, c + 1 and unlimited: the survivor list, the
+    (n + 1)-th-score threshold (an exact score: the ties at the bottom fall with it) and the ordered filter where a wave
+    or a 1024-chunk is exactly full, one short and one over."""
+    lib = nat.lib()
+    h, w = 56, 64
+    heat = planted_heatmaps(c, c, h, w)
+    assert ((heat > 0).sum((1, 2, 3)) == c).all()
+    hd = heat.reshape(2, h, w).contiguous().to(DEV)
+    ws = torch.empty(lib.gfc_disk_select_workspace_bytes(2, h, w), dtype=torch.uint8, device=DEV)
+    for n in (c - 1, c, c + 1, None):
+        ref = odisk.heatmap_to_keypoints(heat, n, 1, 0.0)
+        cap = max(n, 1) if n is not None else h * w
+        kp = torch.full((2, cap, 2), -7.0, device=DEV)
+        sc = torch.full((2, cap), -7.0, device=DEV)
+        cnt = torch.empty((2,), dtype=torch.int32, device=DEV)
+        nat.check(lib.gfc_disk_nms_select(nat.ptr(hd), 2, h, w, 1, 0.0, -1 if n is None else n, cap, nat.ptr(kp),
+                                          nat.ptr(sc), nat.ptr(cnt), nat.ptr(ws), ws.numel(),
+                                          nat.stream_ptr(torch.device(DEV))), "disk_nms_select")
+        torch.cuda.synchronize()
+        for i, (xy, s) in enumerate(ref):
+            k = int(cnt[i])
+            assert k == xy.shape[0], (n, i, k, xy.shape)
+            assert torch.equal(kp[i, :k].cpu(), xy.float()) and torch.equal(sc[i, :k].cpu(), s), (n, i)
+        # what kornia's rule keeps: everything without n; with n the scores above the (n + 1)-th, or above the minimum
+        # (for n >= c - 1; the five equal scores at the bottom of image 1 fall together)
+        assert [r[0].shape[0] for r in ref] == ([c, c] if n is None else [c - 1, max(c - 5, 0)]), n
+
+
 def test_disk_gather_descriptors_vs_oracle():
     lib = nat.lib()
     g = torch.Generator().manual_seed(3)

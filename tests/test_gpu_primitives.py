@@ -855,18 +855,81 @@ def test_select_ties_and_empty():
     assert (sc[1] == 0).all()
 
 
+PLANT_H = PLANT_W = 132  # 66 x 66 sites two pixels apart: isolated under a radius-1 NMS, room for 4097 candidates
+
+
+def planted_scores(values, seed):
+    """[PLANT_H, PLANT_W] map, -1 except len(values) seeded sites (even rows and columns), which hold `values` in
+    row-major order of the sites."""
+    sites = torch.randperm(66 * 66, generator=gen(seed))[: len(values)].sort().values
+    s = torch.full((PLANT_H, PLANT_W), -1.0)
+    s[2 * (sites // 66), 2 * (sites % 66)] = values
+    return s
+
+
+def expected_selection(s, k):
+    """The rule of test_select_ties_and_empty: all candidates row-major when there are at most k, else a stable
+    descending sort (equal scores: lower linear index first) cut at k."""
+    ys, xs = torch.where(s > 0)
+    v = s[ys, xs]
+    if len(v) > k:
+        order = torch.argsort(-v, stable=True)[:k]
+        ys, xs, v = ys[order], xs[order], v[order]
+    return torch.stack([xs, ys], -1).float(), v
+
+
+def check_selection(s, k):
+    """gfc_sp_select on the planted maps and gfc_sp_nms_select (radius 1, which keeps every isolated site and hands the
+    candidates over unordered) against expected_selection; rows beyond the count are zero."""
+    from glue_factory_colon_amd._superpoint_common import SuperPointRunner
+
+    run = SuperPointRunner()
+    sd = D(s)
+    results = {"select": run.select(sd, 0.0, k), "nms_select": run.nms_select(sd, 1, 0, None, 0.0, k)}
+    torch.cuda.synchronize()
+    for name, (kp, sc, cnt) in results.items():
+        for i in range(s.shape[0]):
+            xy, v = expected_selection(s[i], k)
+            c = int(cnt[i])
+            assert c == len(v), (name, i, k, c, len(v))
+            assert torch.equal(kp[i, :c].cpu(), xy) and torch.equal(sc[i, :c].cpu(), v), (name, i, k)
+            assert not kp[i, c:].any() and not sc[i, c:].any(), (name, i, k)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1023, 1024, 1025, 4097])
+def test_select_counts_at_wave_and_chunk_boundaries(n):
+    """Exactly n candidates, k = n - 1, n, n + 1: image 0 with n distinct scores (the radix select stops as soon as a
+    bin holds exactly what is wanted), image 1 with n equal scores (n > k sends it through all eight passes, into the
+    index word).  n <= k returns all candidates row-major: through the scan of the dense map in gfc_sp_select, through
+    the second sort in gfc_sp_nms_select."""
+    distinct = (torch.randperm(n, generator=gen(n)) + 1).float() / 8192  # exact in fp32, all different, in (0, 1)
+    s = torch.stack([planted_scores(distinct, n), planted_scores(torch.full((n,), 0.5), n + 1)])
+    for k in (n - 1, n, n + 1):
+        if 1 <= k <= 8192:
+            check_selection(s, k)
+
+
+def test_select_tie_group_that_straddles_k():
+    """k - 3 distinct higher scores, then ten equal ones: the three with the lowest linear index complete the k."""
+    k = 100
+    values = torch.cat([0.5 + torch.arange(1, k - 2).float() / 1024, torch.full((10,), 0.25)])
+    values = values[torch.randperm(len(values), generator=gen(5))]
+    check_selection(planted_scores(values, 6)[None], k)
+
+
 def test_specular_filter_kernels_vs_oracle():
-    """gfc_sp_filter_keypoints (stable compaction over several 1024-chunks, fractional key points with the
-    reference's default offset 0.5, image_size crop) and gfc_sp_mask_scores against extractors/utils.py restated."""
+    """gfc_sp_filter_keypoints (stable compaction over several 1024-chunks, counts on both sides of a wave and of a
+    chunk, fractional key points with the reference's default offset 0.5, image_size crop) and gfc_sp_mask_scores
+    against extractors/utils.py restated."""
     lib = nat.lib()
     g = gen(91)
-    b, cap, hm, wm = 3, 2500, 70, 90
+    b, cap, hm, wm = 8, 2500, 70, 90
     mask = torch.rand((b, hm, wm), generator=g) > 0.3
     kp = torch.rand((b, cap, 2), generator=g) * torch.tensor([wm + 4.0, hm + 4.0]) - 2.0  # some outside
     kp[:, ::3] = kp[:, ::3].round() + 0.5                                              # exact pixel centres too
     sc = torch.rand((b, cap), generator=g)
-    counts = torch.tensor([cap, 1700, 0], dtype=torch.int32)
-    wh = torch.tensor([[90, 70], [80, 60], [90, 70]], dtype=torch.int32)
+    counts = torch.tensor([cap, 1700, 0, 1, 64, 65, 1024, 1025], dtype=torch.int32)
+    wh = torch.tensor([[90, 70], [80, 60], [90, 70], [90, 70], [90, 70], [85, 66], [90, 70], [80, 60]], dtype=torch.int32)
     kd, sd_, cd = kp.clone().to(DEV), sc.clone().to(DEV), counts.clone().to(DEV)
     nat.check(lib.gfc_sp_filter_keypoints(nat.ptr(kd), nat.ptr(sd_), nat.ptr(cd), b, cap, nat.ptr(D(mask.to(torch.uint8))),
                                           hm, wm, nat.ptr(D(wh)), 0.5, st()), "filter")

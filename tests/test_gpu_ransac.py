@@ -166,6 +166,22 @@ def test_many_key_points():
     assert cases == 8 and flips <= 0.10 * cases, (flips, cases)
 
 
+def test_every_match_valid_around_one_chunk_of_the_compaction():
+    """No row unmatched, M one short of, equal to and one over the 256 rows the compaction takes per step: every row is a
+    correspondence, in its own order (the inlier masks are compared by row).  30 % outliers, sigma 0.5 px, 512
+    hypotheses, two scenes each: conditions 2 and 3 again."""
+    cases = flips = 0
+    stats = {"gap": 0.0, "band": 0.0, "err": 0.0}
+    for m in (255, 256, 257):
+        members = [(m, k, rr.make_case(m, 0.3, 0.5, seed=8000 + m + k, unmatched_share=0.0)) for k in range(2)]
+        for rec in make_records(members, [1.0, 3.0], 512, [m, m + 1]):
+            assert len(rec["corr"]) == m and np.array_equal(rec["idx"], np.arange(m))
+            c, f = compare_with_restatement(rec, stats)
+            cases, flips = cases + c, flips + f
+    print(f"every match valid: cases {cases}, flips {flips}, worst score gap / bound {stats['gap']:.3g}")
+    assert cases == 12 and flips <= 0.10 * cases, (flips, cases)
+
+
 def test_self_consistency(records):
     """4. no reference involved: inliers == {r^2 < t^2} of the returned H outside the band; the returned model's MSAC
     score is not above H_minimal's (both recomputed in float64 from the fp64 models the kernel returns)."""

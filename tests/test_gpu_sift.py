@@ -127,6 +127,36 @@ def test_detect_on_a_whole_pyramid_with_two_valid_sizes():
         _compare_raw(refs[b], raw_f, raw_i, counts, b)
 
 
+def test_detect_compacts_more_than_1024_accepted_records_and_none():
+    """The bumps of the detection fixture, 7 samples apart on cleared ground.  Image 0: 1800 candidates of which more
+    than 1024 are accepted, the rejected ones (under the threshold after refinement) among them on both sides of the
+    1024th record; image 1: candidates of which none is accepted."""
+    sift = _sift()
+    thr = sr.DETECT_THR
+    rows, cols = 36, 50
+    h, w = 7 * rows + 2, 7 * cols + 2
+    amp = np.random.RandomState(3).choice([0.81, 1.5, -2.0, 3.0], size=(rows, cols), p=[0.3, 0.3, 0.2, 0.2])
+    vols = np.zeros((2, 5, h, w), np.float32)
+    for r in range(rows):
+        for c in range(cols):
+            for b, value in ((0, amp[r, c] * thr), (1, 0.81 * thr)):
+                if b == 1 and r >= 3:
+                    continue
+                l, y, x = 1 + (r + c) % 3, 7 * r + 4, 7 * c + 4
+                vols[b, l - 1: l + 2, y - 1: y + 2, x - 1: x + 2] = 0.5 * value
+                vols[b, l, y, x] = value
+    refs = [sr.detect([v], 0, thr) for v in vols]
+    assert refs[0]["n_candidates"] == rows * cols and 1024 < len(refs[0]["idx"]) < rows * cols - 200
+    assert refs[1]["n_candidates"] == 3 * cols and len(refs[1]["idx"]) == 0
+    lay = sift.pyramid_layout(h, w, 0, 1)
+    dog = torch.cat([_upload(sift, [v], lay, True) for v in vols])
+    raw_f, raw_i, counts = sift.detect(dog, h, w, None, 0, 1, thr, 10.0, cap=2048)
+    _compare_raw(refs[0], raw_f, raw_i, counts, 0)
+    got = gc.compare_raw(refs[1], raw_f, raw_i, counts, 1)
+    assert got["equal"] and got["n"] == 0, got
+    assert not raw_i[0, int(counts[0, 0]):].any() and not raw_i[1].any()  # nothing is written beyond the count
+
+
 # ----------------------------------------------------------------------------------------------- orient and describe
 @pytest.fixture(scope="module")
 def stage_case():
@@ -163,6 +193,39 @@ def test_orientations_match_the_restatement(stage_case):
     assert diff.max() <= allow, (diff.max(), allow)
     assert np.array_equal(got[:, 4:7], np.array([rec[i, :3] for i, _ in want]))  # the record travels unchanged
     assert max(len(a) for a in ref64) >= 2  # the fixture has key points with a secondary peak
+
+
+def test_orient_compacts_across_1024_records_and_reports_the_overflow(stage_case):
+    """The fixture's records and one on a constant level (no gradient, so no orientation), repeated beyond 1024: key
+    points with 0, 1 and several orientations on both sides of the 1024th record, and an oriented list 37 rows too
+    short: the rows that fit are the first ones, the rest is counted."""
+    sift = _sift()
+    levels, rec, ref64, ref32 = stage_case
+    h, w = sr.STAGE_SHAPE
+    lay = sift.pyramid_layout(h, w, 0, 2)
+    assert not ((rec[:, 3] == 1) & (rec[:, 4] == 5)).any()  # no record of the fixture reads the level made constant
+    flat = [lv.copy() for lv in levels]
+    flat[1][5][:] = 0.5
+    assert sr.orientations(flat[1][5], 16.0, 16.0, 1.7)[0] == []
+    unit = np.concatenate([rec, np.array([[16.0, 16.0, 1.7, 1, 5]], np.float32).astype(np.float64)])
+    angles = list(ref64) + [[]]
+    n = 1024 + 2 * len(unit)
+    which = np.arange(n) % len(unit)
+    for part in (which[:1024], which[1024:]):
+        assert {min(len(angles[u]), 2) for u in part} == {0, 1, 2}
+    want = [(i, j, th) for i, u in enumerate(which) for j, th in enumerate(angles[u])]
+    ocap = len(want) - 37
+    raw_f, raw_i, counts = _records(unit[which], n)
+    ori_f, ori_i, ocounts = sift.orient(_upload(sift, flat, lay, False), h, w, raw_f, raw_i, counts, None, 0, 2, ocap=ocap)
+    assert ocounts[0].tolist() == [ocap, 37]
+    got_i, got = ori_i[0].cpu().numpy(), ori_f[0].cpu().double().numpy()
+    assert np.array_equal(got_i[:, 0], [i for i, _, _ in want[:ocap]])  # the key point of every row ...
+    assert np.array_equal(got_i[:, 3], [j for _, j, _ in want[:ocap]])  # ... and which of its orientations
+    allow = 4 * max(abs(x - y) for a, c in zip(ref64, ref32) for x, y in zip(a, c))
+    diff = np.abs(got[:, 7] - np.array([th for _, _, th in want[:ocap]]))
+    diff = np.minimum(diff, 2 * np.pi - diff)
+    assert diff.max() <= allow, (diff.max(), allow)
+    assert np.array_equal(got[:, 4:7], np.array([unit[which[i], :3] for i, _, _ in want[:ocap]]))
 
 
 def test_descriptors_match_the_restatement(stage_case):
