@@ -5,218 +5,188 @@ there is no PyTorch / CPU fallback for any arithmetic on the path.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_longlong, c_size_t, c_void_p
+import re
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint, c_uint64,
+                    c_void_p)
 
 import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # GFC_AMD_LIB: another build of the same library (same-box A/B of kernel variants: tools/ab_build.sh)
 LIB_PATH = os.environ.get("GFC_AMD_LIB") or os.path.join(_PKG, "libgfc_amd.so")
-GFC_LG_MAX_LAYERS = 16
-GFC_LG_MAX_RAGGED_PAIRS = 128
-
-STATUS = {0: "GFC_OK", 1: "GFC_ERR_INVALID", 2: "GFC_ERR_WORKSPACE", 3: "GFC_ERR_UNSUPPORTED", 4: "GFC_ERR_LAUNCH"}
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd.h")
 
 
 class NativeError(RuntimeError):
     pass
 
 
-class SpParams(Structure):
-    _fields_ = [("w", c_void_p * 8), ("bias", c_void_p * 8), ("scale", c_void_p * 8), ("shift", c_void_p * 8),
-                ("wh", c_void_p), ("bias_h", c_void_p), ("scale_h", c_void_p), ("shift_h", c_void_p),
-                ("wp", c_void_p), ("bias_p", c_void_p), ("scale_p", c_void_p), ("shift_p", c_void_p),
-                ("wd", c_void_p), ("bias_d", c_void_p), ("scale_d", c_void_p), ("shift_d", c_void_p),
-                ("desc_dim", c_int), ("conv_mode", c_int),
-                ("w_wino", c_void_p * 8), ("wh_wino", c_void_p), ("w_stem_wino43", c_void_p)]
+# ---- the header is the single source: functions, structs and constants are parsed from it ----
+_TYPE = r"(?:const\s+)?(?:unsigned\s+int|unsigned\s+char|long\s+long|\w+)\s*\**"
+_DECL = re.compile(r"""\s*(?:
+      \#\s*define\s+(?P<def>GFC_\w+)[ \t]+(?P<defval>-?\d+)[ \t]*$
+    | \#\s*ifdef\s+__cplusplus\s+(?:extern\s+"C"\s*\{|\})\s+\#\s*endif\b[^\n]*$
+    | \#\s*(?:ifndef|endif|include|define\s+GFC_AMD_H\b)[^\n]*$
+    | (?:typedef\s+)?enum\s*\{(?P<enum>[^{}]*)\}\s*(?P<ename>\w*)\s*;
+    | typedef\s+struct\s*\{(?P<fields>[^{}]*)\}\s*(?P<sname>\w+)\s*;
+    | (?P<ret>%s)\s*\b(?P<fname>gfc_\w+)\s*\((?P<params>[^()]*)\)\s*;
+    )""" % _TYPE, re.X | re.M)
+_VAR = re.compile(r"\s*(?P<type>%s)\s*\b(?P<name>\w+)\s*(?:\[\s*(?P<len>\w+)\s*\])?\s*$" % _TYPE)
 
 
-class Trace(Structure):
-    _fields_ = [("start", POINTER(c_void_p)), ("stop", POINTER(c_void_p)), ("capacity", c_int), ("count", c_int)]
+def _var(text, consts, what):
+    m = _VAR.match(text)
+    if m is None:
+        raise NativeError(f"{HEADER_PATH}: cannot parse {what} '{text.strip()}'")
+    ctype = re.sub(r"\s*\*", "*", " ".join(m["type"].split()))
+    n = m["len"]
+    if n is not None and not n.isdigit() and n not in consts:
+        raise NativeError(f"{HEADER_PATH}: cannot parse {what} '{text.strip()}': {n} is not defined before it")
+    return m["name"], ctype, (None if n is None else int(n) if n.isdigit() else consts[n])
 
 
-_LG_ARRAYS = ["wqkv", "bqkv", "s_out_w", "s_out_b", "s_ffn0_w", "s_ffn0_b", "s_ln_g", "s_ln_b", "s_ffn3_w",
-              "s_ffn3_b", "c_qkv_w", "c_qkv_b", "c_out_w", "c_out_b", "c_ffn0_w", "c_ffn0_b", "c_ln_g", "c_ln_b",
-              "c_ffn3_w", "c_ffn3_b"]
+def parse_header(text):
+    """The declarations of include/gfc_amd.h: functions {name: (return type, [(parameter, C type)])}, structs
+    {name: [(field, C type, array length or None)]}, enums {typedef name: {member: value}} and every integer constant
+    (#define and enum member).  Only the forms that header uses; anything else raises."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    funcs, structs, enums, consts, pos = {}, {}, {}, {}, 0
+    while text[pos:].strip():
+        m = _DECL.match(text, pos)
+        if m is None:
+            raise NativeError(f"{HEADER_PATH}: cannot parse the declaration at '{text[pos:].strip()[:80]}'")
+        pos = m.end()
+        if m["def"]:
+            consts[m["def"]] = int(m["defval"])
+        elif m["enum"] is not None:
+            members = {}
+            for item in m["enum"].split(","):
+                k = re.fullmatch(r"\s*(GFC_\w+)\s*=\s*(-?\d+)\s*", item)
+                if k is None:
+                    raise NativeError(f"{HEADER_PATH}: cannot parse the enum member '{item.strip()}'")
+                members[k[1]] = int(k[2])
+            enums[m["ename"]] = members
+            consts.update(members)
+        elif m["sname"]:
+            structs[m["sname"]] = [_var(f, consts, "the field") for f in m["fields"].split(";") if f.strip()]
+        elif m["fname"]:
+            params = [] if m["params"].strip() == "void" else [_var(p, consts, "the parameter")[:2]
+                                                               for p in m["params"].split(",")]
+            funcs[m["fname"]] = (_var(m["ret"] + " _", consts, "the return type")[1], params)
+    return funcs, structs, enums, consts
 
 
-GFC_LG_FP32, GFC_LG_FP16 = 0, 1
-GFC_LG_ADAPTIVE_LIVE, GFC_LG_ADAPTIVE_STOPPED, GFC_LG_ADAPTIVE_EMPTIED = 0, 1, 2  # report[b][0] of gfc_lg_adaptive_step
-# the fp16 copies of the per-layer matrices (gfc_lg_params.precision = GFC_LG_FP16), in the order of the header
-_LG_ARRAYS_F16 = ["wqkv16", "s_out_w16", "s_ffn0_w16", "s_ffn3_w16", "c_qkv_w16", "c_out_w16", "c_ffn0_w16",
-                  "c_ffn3_w16", "final_proj_w16"]
+def _load_header():
+    if not os.path.exists(HEADER_PATH):
+        raise NativeError(f"{HEADER_PATH} not found: the binding is derived from the C header")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
 
 
-class LgParams(Structure):
-    _fields_ = ([("n_layers", c_int), ("input_dim", c_int), ("input_proj_w", c_void_p), ("input_proj_b", c_void_p),
-                 ("posenc_wr", c_void_p), ("posenc_dim", c_int)]
-                + [(n, c_void_p * GFC_LG_MAX_LAYERS) for n in _LG_ARRAYS]
-                + [(n, c_void_p * GFC_LG_MAX_LAYERS) for n in ("final_proj_w", "final_proj_b", "matchability_w",
-                                                               "matchability_b", "token_w", "token_b")]
-                # appended for the fp16 matcher: a zero-initialised struct is the fp32 path
-                + [("precision", c_int), ("input_proj_w16", c_void_p)]
-                + [(n, c_void_p * GFC_LG_MAX_LAYERS) for n in _LG_ARRAYS_F16])
+FUNCTIONS, STRUCTS, ENUMS, CONSTANTS = _load_header()
+globals().update(CONSTANTS)  # GFC_LG_MAX_LAYERS, GFC_LG_FP16, GFC_CAM_RADIAL, GFC_RS_AREA, ...
+STATUS = {v: k for k, v in ENUMS["gfc_status"].items()}
+
+_SCALARS = {"int": c_int, "float": c_float, "double": c_double, "size_t": c_size_t, "long long": c_longlong,
+            "unsigned int": c_uint, "uint64_t": c_uint64}
+_CLASSES = {}  # C struct name -> ctypes.Structure
 
 
-GFC_SG_MAX_LAYERS = 32
-_SG_ARRAYS = ["wqkv", "bqkv", "merge_w", "merge_b", "mlp0_w", "mlp0_b", "mlp_scale", "mlp_shift", "mlp1_w", "mlp1_b"]
+def _ctype(ctype):
+    """Scalars as themselves, struct pointers and void** typed, every data pointer a c_void_p."""
+    if ctype in _SCALARS:
+        return _SCALARS[ctype]
+    if not ctype.endswith("*"):
+        raise NativeError(f"{HEADER_PATH}: no ctypes mapping for '{ctype}'")
+    pointee = ctype[:-1].replace("const ", "")
+    if pointee in _CLASSES:
+        return POINTER(_CLASSES[pointee])
+    return POINTER(c_void_p) if pointee == "void*" else c_void_p
 
 
-class SgParams(Structure):
-    _fields_ = ([("n_layers", c_int), ("use_scores", c_int), ("cross", c_int * GFC_SG_MAX_LAYERS),
-                 ("kenc_w", c_void_p * 5), ("kenc_b", c_void_p * 5), ("kenc_scale", c_void_p * 4),
-                 ("kenc_shift", c_void_p * 4)]
-                + [(n, c_void_p * GFC_SG_MAX_LAYERS) for n in _SG_ARRAYS]
-                + [("final_proj_w", c_void_p), ("final_proj_b", c_void_p), ("bin_score", c_float)])
+def _structure(cname):
+    fields = [(f, _ctype(t) if n is None else _ctype(t) * n) for f, t, n in STRUCTS[cname]]
+    _CLASSES[cname] = type("".join(w.capitalize() for w in cname[4:].split("_")), (Structure,), {"_fields_": fields})
+    return _CLASSES[cname]
 
+
+SpParams, Trace, LgParams, SgParams = map(_structure, ("gfc_sp_params", "gfc_trace", "gfc_lg_params", "gfc_sg_params"))
+assert set(_CLASSES) == set(STRUCTS), "a struct of the header has no class here"
+
+
+def _layer_arrays(cname, length, ctype):
+    """The fields of a parameter struct that hold one `ctype` per layer, in the header's order."""
+    return [f for f, t, n in STRUCTS[cname] if n == length and t == ctype]
+
+
+# For code outside the package that fills a parameter struct field by field: the per-layer fp32 arrays of LightGlue,
+# its fp16 copies (declared const void*) and SuperGlue's per-layer arrays, by declared type -- no list is kept here.
+_LG_ARRAYS = _layer_arrays("gfc_lg_params", GFC_LG_MAX_LAYERS, "const float*")  # noqa: F821
+_LG_ARRAYS_F16 = _layer_arrays("gfc_lg_params", GFC_LG_MAX_LAYERS, "const void*")  # noqa: F821
+_SG_ARRAYS = _layer_arrays("gfc_sg_params", GFC_SG_MAX_LAYERS, "const float*")  # noqa: F821
+
+# name -> (restype, argtypes); every symbol declared in include/gfc_amd.h
+SIGNATURES = {name: (c_char_p if ret == "const char*" else _ctype(ret), [_ctype(t) for _, t in params])
+              for name, (ret, params) in FUNCTIONS.items()}
+
+_DTYPES = {"float": (torch.float32,), "int32_t": (torch.int32,), "int": (torch.int32,), "int64_t": (torch.int64,),
+           "double": (torch.float64,), "uint8_t": (torch.uint8, torch.bool), "unsigned char": (torch.uint8, torch.bool),
+           "void": None}
+
+
+def _call_spec(params):
+    """([(parameter, C type, dtypes a tensor may have there)] without a trailing `void* stream`, whether there is one).
+    The dtypes: () = no tensor (scalar, struct pointer, void**), None = any (void*), else those of the pointee."""
+    has_stream = params[-1:] == [("stream", "void*")]
+    return [(p, t, _DTYPES.get(t[:-1].replace("const ", ""), ()) if t.endswith("*") else ())
+            for p, t in (params[:-1] if has_stream else params)], has_stream
+
+
+_CALLS = {name: _call_spec(params) for name, (_, params) in FUNCTIONS.items()}
 
 _lib = None
 
-# name -> (restype, argtypes); every symbol declared in include/gfc_amd.h
-SIGNATURES = {
-    "gfc_version": (c_char_p, []),
-    "gfc_pack_conv3x3": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gfc_conv3x3": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
-    "gfc_sp_stem": (c_int, [c_void_p] * 10 + [c_int] * 3 + [c_void_p]),
-    "gfc_linear": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                           c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
-                           c_void_p]),
-    "gfc_batched_nt": (c_int, [c_void_p, c_int, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_int, c_longlong,
-                               c_int, c_int, c_int, c_int, c_void_p]),
-    "gfc_attention": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                              c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
-    "gfc_attention_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_linear_layernorm_gelu": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
-                                          c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "gfc_ffn_fused": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gfc_linear_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
-                               c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
-                               c_int, c_void_p]),
-    "gfc_batched_nt_f16": (c_int, [c_void_p, c_int, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_int,
-                                   c_longlong, c_int, c_int, c_int, c_int, c_void_p]),
-    "gfc_attention_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                  c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
-    "gfc_layernorm_gelu": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "gfc_sp_workspace_bytes": (c_size_t, [c_int] * 4),
-    "gfc_sp_dense": (c_int, [POINTER(SpParams), c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                             c_size_t, POINTER(Trace), c_void_p]),
-    "gfc_probe_mfma_peak": (c_int, [c_int, POINTER(c_float), POINTER(c_float), c_void_p]),
-    "gfc_event_create": (c_int, [POINTER(c_void_p)]),
-    "gfc_event_destroy": (c_int, [c_void_p]),
-    "gfc_event_elapsed_ms": (c_int, [c_void_p, c_void_p, POINTER(c_float)]),
-    "gfc_sp_detector_head": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "gfc_sp_nms": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "gfc_sp_select_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_sp_select": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_size_t, c_void_p]),
-    "gfc_sp_nms_select_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_sp_nms_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float, c_int, c_int]
-                          + [c_void_p] * 5 + [c_size_t, c_void_p]),
-    "gfc_sp_sample": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                              c_void_p, c_void_p]),
-    "gfc_sp_pad_keypoints": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int,
-                                     c_float, ctypes.c_uint, c_void_p]),
-    "gfc_l2norm_rows": (c_int, [c_void_p, c_longlong, c_int, c_void_p]),
-    "gfc_lg_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_lg_posenc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
-                              c_void_p, c_void_p, c_void_p]),
-    "gfc_lg_log_assignment": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
-                                      c_void_p]),
-    "gfc_lg_filter_matches": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_size_t, c_void_p]),
-    "gfc_nn_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_nn_match": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_int] + [c_void_p] * 7
-                     + [c_size_t, c_void_p]),
-    "gfc_eval_matches_homography_lds_bytes": (c_size_t, [c_int] * 2),
-    "gfc_eval_matches_depth_lds_bytes": (c_size_t, [c_int] * 2),
-    "gfc_eval_matches_homography": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float] * 2 + [c_void_p] * 3),
-    "gfc_pack_conv3x3_wino": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gfc_conv3x3_wino": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
-    "gfc_sp_stem_wino": (c_int, [c_void_p] * 10 + [c_int] * 3 + [c_void_p]),
-    "gfc_pack_conv3x3_wino43": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gfc_sp_stem_wino43": (c_int, [c_void_p] * 10 + [c_int] * 3 + [c_void_p]),
-    "gfc_disk_select_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_disk_nms_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_size_t, c_void_p]),
-    "gfc_disk_gather_descriptors": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "gfc_disk_gather_descriptors_nhwc": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "gfc_disk_conv5x5_packed_floats": (c_size_t, [c_int] * 2),
-    "gfc_disk_pack_conv5x5": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "gfc_disk_conv5x5": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_void_p]),
-    "gfc_disk_instnorm_workspace_bytes": (c_size_t, [c_int] * 2),
-    "gfc_disk_instnorm_stats": (c_int, [c_void_p] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "gfc_disk_avgpool2": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p]),
-    "gfc_disk_upsample2": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_int, c_void_p]),
-    "gfc_disk_nchw3_to_nhwc4": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p]),
-    "gfc_sp_refine_keypoints": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
-    "gfc_sp_mask_scores": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 2),
-    "gfc_sp_filter_keypoints": (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] + [c_int] * 2 + [c_void_p, c_float, c_void_p]),
-    "gfc_eval_homography_dlt": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p] * 3),
-    "gfc_eval_homography_ransac_workspace_bytes": (c_size_t, [c_int] * 4),
-    "gfc_eval_homography_ransac": (c_int, [c_void_p] * 6 + [c_int] * 3 + [POINTER(c_float)] + [c_int] * 3
-                                   + [ctypes.c_uint64] + [c_void_p] * 8 + [c_size_t, c_void_p]),
-    "gfc_eval_pose_image2cam": (c_int, [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p, c_void_p]),
-    "gfc_eval_relative_pose_ransac_workspace_bytes": (c_size_t, [c_int] * 4),
-    "gfc_eval_relative_pose_ransac": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int, c_void_p] + [c_int] * 3
-                                      + [POINTER(c_float)] + [c_int] * 3 + [ctypes.c_uint64, ctypes.c_double]
-                                      + [c_void_p] * 12 + [c_size_t, c_void_p]),
-    "gfc_eval_pose_project": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p] * 5),
-    "gfc_eval_matches_depth": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 7
-                               + [c_float] * 2 + [c_void_p] * 4),
-    "gfc_eval_matches_epipolar": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_void_p] + [c_int] * 3
-                                  + [c_void_p] * 2),
-    "gfc_preprocess_resize": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] + [c_int] * 4 + [c_void_p]),
-    "gfc_preprocess_resample": (c_int, [c_void_p] + [c_int] * 11 + [c_float] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
-    "gfc_warp_perspective": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] + [c_int] * 2
-                             + [c_void_p]),
-    "gfc_sift_pyramid_layout": (c_int, [c_int] * 4 + [POINTER(c_int64)]),
-    "gfc_sift_pyramid": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 3),
-    "gfc_sift_detect_workspace_bytes": (c_size_t, [c_int] * 2),
-    "gfc_sift_detect": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_double] * 2 + [c_int]
-                        + [c_void_p] * 4 + [c_size_t, c_void_p]),
-    "gfc_sift_orient_workspace_bytes": (c_size_t, [c_int] * 2),
-    "gfc_sift_orient": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 3 + [c_int] * 2
-                        + [c_void_p] * 4 + [c_size_t, c_void_p]),
-    "gfc_sift_describe": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 3 + [c_int]
-                          + [c_void_p] * 2),
-    "gfc_sift_gray": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
-    "gfc_sift_filter_workspace_bytes": (c_size_t, [c_int] * 4),
-    "gfc_sift_filter": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 8
-                        + [c_size_t, c_void_p]),
-    "gfc_sift_extract_workspace_bytes": (c_size_t, [c_int] * 7),
-    "gfc_sift_extract": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 2 + [c_int] * 2 + [c_double] * 2 + [c_int] * 7
-                         + [c_void_p] * 10 + [c_size_t, c_void_p]),
-    "gfc_lg_layer_workspace_bytes": (c_size_t, [c_int]),
-    "gfc_lg_layer": (c_int, [POINTER(LgParams), c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                             c_int, c_void_p, c_size_t, c_void_p]),
-    "gfc_lg_rowdot": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "gfc_lg_assign_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_lg_assign": (c_int, [POINTER(LgParams), c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float]
-                      + [c_void_p] * 6 + [c_size_t, c_void_p]),
-    "gfc_lg_packed_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_lg_forward_packed": (c_int, [POINTER(LgParams)] + [c_void_p] * 5 + [c_int] * 3 + [c_float] + [c_void_p] * 7
-                              + [c_size_t, POINTER(Trace), c_void_p]),
-    "gfc_lg_forward": (c_int, [POINTER(LgParams)] + [c_void_p] * 8 + [c_int] * 3 + [c_float] + [c_void_p] * 8
-                       + [c_size_t, c_void_p]),
-    "gfc_lg_ragged_workspace_bytes": (c_size_t, [c_int, POINTER(c_int32), POINTER(c_int32)]),
-    "gfc_lg_forward_ragged": (c_int, [POINTER(LgParams)] + [c_void_p] * 5 + [c_int, POINTER(c_int32), POINTER(c_int32),
-                                                                            c_float] + [c_void_p] * 7
-                              + [c_size_t, POINTER(Trace), c_void_p]),
-    "gfc_lg_adaptive_step_workspace_bytes": (c_size_t, [c_int] * 2),
-    "gfc_lg_adaptive_step": (c_int, [POINTER(LgParams), c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 3
-                             + [c_int] * 3 + [c_float, c_float, c_double, c_int, c_int] + [c_void_p] * 5 + [c_int]
-                             + [c_void_p] * 6 + [c_size_t, c_void_p]),
-    "gfc_sg_keypoint_encoder_workspace_bytes": (c_size_t, [c_int]),
-    "gfc_sg_keypoint_encoder": (c_int, [POINTER(SgParams), c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                        c_void_p, c_size_t, c_void_p]),
-    "gfc_sg_mlp": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 8 + [c_int, c_int, c_void_p]),
-    "gfc_sg_sinkhorn_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_sg_sinkhorn": (c_int, [c_void_p, c_float] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "gfc_sg_workspace_bytes": (c_size_t, [c_int] * 3),
-    "gfc_sg_forward": (c_int, [POINTER(SgParams)] + [c_void_p] * 8 + [c_int] * 4 + [c_float] + [c_void_p] * 8
-                       + [c_size_t, c_void_p]),
-}
+
+def convert(name, args):
+    """Check `args` against the header's parameters of `name` (the stream left out) and turn tensors into device
+    addresses.  Returns (arguments, device of the tensors or None).  No library call: a violation raises first."""
+    params, _ = _CALLS[name]
+    if len(args) != len(params):
+        raise NativeError(f"{name} takes {len(params)} arguments ({', '.join(p for p, _, _ in params)}), got {len(args)}")
+    out, device = [], None
+    for a, (pname, ctype, rule) in zip(args, params):
+        if isinstance(a, torch.Tensor):
+            if rule == ():
+                raise NativeError(f"{name}: '{pname}' is declared {ctype}, got a tensor")
+            d = a.device
+            if d.type != "cuda":
+                raise NativeError(f"{name}: '{pname}' ({ctype}) is on {d}; it must be on a 'cuda' (ROCm) device")
+            if device is None:
+                device = d
+            elif d != device:
+                raise NativeError(f"{name}: '{pname}' ({ctype}) is on {d}, earlier tensors are on {device}")
+            if rule is not None and a.dtype not in rule:
+                raise NativeError(f"{name}: '{pname}' is declared {ctype} and needs {' or '.join(map(str, rule))}, "
+                                  f"got {a.dtype}")
+            if not a.is_contiguous():
+                raise NativeError(f"{name}: '{pname}' ({ctype}) must be contiguous, got strides {tuple(a.stride())}")
+            a = a.data_ptr()
+        out.append(a)
+    return out, device
+
+
+def call(name, *args, device=None):
+    """One checked native call: tensors are verified against the header (device, dtype, contiguity), a trailing
+    `void* stream` is filled in with the current stream of their device (of `device` without tensors), a non-zero
+    gfc_status raises; size_t and const char* results are returned."""
+    converted, dev = convert(name, args)
+    if _CALLS[name][1]:
+        converted.append(torch.cuda.current_stream(dev if dev is not None else device).cuda_stream)
+    result = getattr(lib(), name)(*converted)
+    if FUNCTIONS[name][0] != "int":
+        return result
+    if result != 0:
+        raise NativeError(f"{name} failed: {STATUS.get(result, result)}")
 
 
 def lib():

@@ -10,7 +10,7 @@ import torch
 
 from . import _native as nat
 
-SAMPLE_OPEN, SAMPLE_LEGACY, SAMPLE_FIXED = 0, 1, 2
+SAMPLE_OPEN, SAMPLE_LEGACY, SAMPLE_FIXED = nat.GFC_SAMPLE_OPEN, nat.GFC_SAMPLE_LEGACY, nat.GFC_SAMPLE_FIXED
 
 
 class RaggedCounts(RuntimeError):
@@ -33,8 +33,6 @@ class PackedSuperPoint:
         """layers: 8 tuples (w_oihw, bias, scale|None, shift|None) for conv1a..conv4b;
         head_p / head_d: 3x3 128->256 of detector / descriptor (same tuple form);
         pb / db: 1x1 heads (w [C,256,1,1], bias, scale|None, shift|None)."""
-        lib = nat.lib()
-        st = nat.stream_ptr(device)
         self.keep = []  # tensors referenced by raw pointers in the struct
         self.params = nat.SpParams()
 
@@ -47,7 +45,7 @@ class PackedSuperPoint:
             w = dev(w)
             cout, cin = w.shape[0], w.shape[1]
             out = torch.empty((9, cout, cin), device=device, dtype=torch.float32)
-            nat.check(lib.gfc_pack_conv3x3(nat.ptr(w), nat.ptr(out), cout, cin, st), "gfc_pack_conv3x3")
+            nat.call("gfc_pack_conv3x3", w, out, cout, cin)
             self.keep.append(out)
             return out
 
@@ -67,8 +65,7 @@ class PackedSuperPoint:
             """Filters transformed for Winograd F(2x2,3x3) (G g G^T in float64, done by the library) in fragment order."""
             w = w.detach().to(device=device, dtype=torch.float32).contiguous()
             out = torch.empty((16 * w.shape[0] * w.shape[1],), device=device, dtype=torch.float32)
-            nat.check(lib.gfc_pack_conv3x3_wino(nat.ptr(w), nat.ptr(out), w.shape[0], w.shape[1], st),
-                      "gfc_pack_conv3x3_wino")
+            nat.call("gfc_pack_conv3x3_wino", w, out, w.shape[0], w.shape[1])
             self.keep.extend([w, out])
             return out
 
@@ -80,7 +77,7 @@ class PackedSuperPoint:
                 # the stem's conv1b additionally as F(4x4,3x3) (csrc/conv_wino43.hip; $GFC_STEM_F43=0 selects F(2x2,3x3))
                 w32 = w.detach().to(device=device, dtype=torch.float32).contiguous()
                 w43 = torch.empty((36 * 64 * 64,), device=device, dtype=torch.float32)
-                nat.check(lib.gfc_pack_conv3x3_wino43(nat.ptr(w32), nat.ptr(w43), 64, 64, st), "gfc_pack_conv3x3_wino43")
+                nat.call("gfc_pack_conv3x3_wino43", w32, w43, 64, 64)
                 self.keep.extend([w32, w43])
                 self.params.w_stem_wino43 = w43.data_ptr()
             self.params.bias[i] = dev(b).data_ptr()
@@ -114,7 +111,6 @@ class PackedSuperPoint:
 def pad_keypoints_native(kpts, scores, counts, k, low, data, image):
     """`pad_random_c` as ONE launch (gfc_sp_pad_keypoints), in place on the selection kernel's [B,cap] outputs; returns
     the [B,k] views."""
-    lib = nat.lib()
     b, cap, _ = kpts.shape
     sizes = None
     if "image_size" in data:
@@ -125,10 +121,8 @@ def pad_keypoints_native(kpts, scores, counts, k, low, data, image):
     offset = gen.get_offset()
     gen.set_offset(offset + 4)
     seed = (gen.initial_seed() * 0x9E3779B1 + offset * 0x85EBCA77 + 1) & 0xFFFFFFFF
-    nat.check(lib.gfc_sp_pad_keypoints(nat.ptr(kpts), nat.ptr(scores), nat.ptr(counts), b, cap, int(k), float(low),
-                                       nat.ptr(sizes), 0 if sizes is None else sizes.numel(),
-                                       float(min(image.shape[-2:])), seed, nat.stream_ptr(kpts.device)),
-              "gfc_sp_pad_keypoints")
+    nat.call("gfc_sp_pad_keypoints", kpts, scores, counts, b, cap, int(k), float(low), sizes,
+             0 if sizes is None else sizes.numel(), float(min(image.shape[-2:])), seed)
     if cap == k:
         return kpts, scores
     return kpts[:, :k].contiguous(), scores[:, :k].contiguous()
@@ -169,96 +163,76 @@ class SuperPointRunner:
         self.trace = None  # optional nat.KernelTrace (bench.py): per-launch events of the dominant kernel
 
     def dense(self, packed, image):
-        lib = nat.lib()
         b, c, h, w = image.shape
         dev = image.device
         h8, w8 = h // 8, w // 8
         heat = torch.empty((b, h8 * 8, w8 * 8), device=dev, dtype=torch.float32)
         desc = torch.empty((b, h8, w8, packed.desc_dim), device=dev, dtype=torch.float32)
-        need = lib.gfc_sp_workspace_bytes(b, c, h, w)
-        ws = self.ws.get(need, dev)
-        nat.check(lib.gfc_sp_dense(ctypes.byref(packed.params), nat.ptr(image), b, c, h, w, nat.ptr(heat),
-                                   nat.ptr(desc), nat.ptr(ws), ws.numel(),
-                                   ctypes.byref(self.trace.c) if self.trace is not None else None,
-                                   nat.stream_ptr(dev)), "gfc_sp_dense")
+        ws = self.ws.get(nat.call("gfc_sp_workspace_bytes", b, c, h, w), dev)
+        nat.call("gfc_sp_dense", ctypes.byref(packed.params), image, b, c, h, w, heat, desc, ws, ws.numel(),
+                 ctypes.byref(self.trace.c) if self.trace is not None else None)
         return heat, desc
 
     def nms(self, heat, radius, border, valid_wh=None):
-        lib = nat.lib()
         b, h, w = heat.shape
         out = torch.empty_like(heat)
-        nat.check(lib.gfc_sp_nms(nat.ptr(heat), b, h, w, int(radius), int(border), nat.ptr(valid_wh), nat.ptr(out),
-                                 nat.stream_ptr(heat.device)), "gfc_sp_nms")
+        nat.call("gfc_sp_nms", heat, b, h, w, int(radius), int(border), valid_wh, out)
         return out
 
     def select(self, scores, threshold, k):
         """k: int >= 1, or None for unlimited.  Returns kpts [B,cap,2], kscores [B,cap], counts [B]."""
-        lib = nat.lib()
         b, h, w = scores.shape
         dev = scores.device
         cap = int(k) if k is not None else h * w
         kpts = torch.empty((b, cap, 2), device=dev, dtype=torch.float32)
         ksc = torch.empty((b, cap), device=dev, dtype=torch.float32)
         counts = torch.empty((b,), device=dev, dtype=torch.int32)
-        need = lib.gfc_sp_select_workspace_bytes(b, h, w)
-        ws = self.ws_sel.get(need, dev)
-        nat.check(lib.gfc_sp_select(nat.ptr(scores), b, h, w, float(threshold), int(k) if k is not None else -1, cap,
-                                    nat.ptr(kpts), nat.ptr(ksc), nat.ptr(counts), nat.ptr(ws), ws.numel(),
-                                    nat.stream_ptr(dev)), "gfc_sp_select")
+        ws = self.ws_sel.get(nat.call("gfc_sp_select_workspace_bytes", b, h, w), dev)
+        nat.call("gfc_sp_select", scores, b, h, w, float(threshold), int(k) if k is not None else -1, cap, kpts, ksc,
+                 counts, ws, ws.numel())
         return kpts, ksc, counts
 
     def nms_select(self, heat, radius, border, valid_wh, threshold, k):
         """Fused NMS + top-k (finite k <= 8192): no dense suppressed map, no scan in the selection kernel."""
-        lib = nat.lib()
         b, h, w = heat.shape
         dev = heat.device
         k = int(k)
         kpts = torch.empty((b, k, 2), device=dev, dtype=torch.float32)
         ksc = torch.empty((b, k), device=dev, dtype=torch.float32)
         counts = torch.empty((b,), device=dev, dtype=torch.int32)
-        ws = self.ws_sel.get(lib.gfc_sp_nms_select_workspace_bytes(b, h, w), dev)
-        nat.check(lib.gfc_sp_nms_select(nat.ptr(heat), b, h, w, int(radius), int(border), nat.ptr(valid_wh),
-                                        float(threshold), k, k, None, nat.ptr(kpts), nat.ptr(ksc), nat.ptr(counts),
-                                        nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)), "gfc_sp_nms_select")
+        ws = self.ws_sel.get(nat.call("gfc_sp_nms_select_workspace_bytes", b, h, w), dev)
+        nat.call("gfc_sp_nms_select", heat, b, h, w, int(radius), int(border), valid_wh, float(threshold), k, k, None,
+                 kpts, ksc, counts, ws, ws.numel())
         return kpts, ksc, counts
 
     def refine_keypoints(self, heat, kpts, counts, radius):
-        lib = nat.lib()
         b, h, w = heat.shape
-        nat.check(lib.gfc_sp_refine_keypoints(nat.ptr(heat), b, h, w, nat.ptr(kpts), nat.ptr(counts), kpts.shape[1],
-                                              int(radius), nat.stream_ptr(heat.device)), "gfc_sp_refine_keypoints")
+        nat.call("gfc_sp_refine_keypoints", heat, b, h, w, kpts, counts, kpts.shape[1], int(radius))
         return kpts
 
     def mask_scores(self, scores, mask, image_wh):
         """Open-variant order: pixels outside the specular mask can no longer be selected (in place)."""
-        lib = nat.lib()
         b, h, w = scores.shape
-        nat.check(lib.gfc_sp_mask_scores(nat.ptr(scores), b, h, w, nat.ptr(mask), mask.shape[-2], mask.shape[-1],
-                                         nat.ptr(image_wh), nat.stream_ptr(scores.device)), "gfc_sp_mask_scores")
+        nat.call("gfc_sp_mask_scores", scores, b, h, w, mask, mask.shape[-2], mask.shape[-1], image_wh)
         return scores
 
     def filter_keypoints(self, kpts, ksc, counts, mask, image_wh, offset=0.0):
         """Official-variant order: compact the selected key points that lie on the mask (in place, counts updated)."""
-        lib = nat.lib()
-        nat.check(lib.gfc_sp_filter_keypoints(nat.ptr(kpts), nat.ptr(ksc), nat.ptr(counts), kpts.shape[0], kpts.shape[1],
-                                              nat.ptr(mask), mask.shape[-2], mask.shape[-1], nat.ptr(image_wh),
-                                              float(offset), nat.stream_ptr(kpts.device)), "gfc_sp_filter_keypoints")
+        nat.call("gfc_sp_filter_keypoints", kpts, ksc, counts, kpts.shape[0], kpts.shape[1], mask, mask.shape[-2],
+                 mask.shape[-1], image_wh, float(offset))
         return kpts, ksc, counts
 
     def sample(self, desc_raw, kpts, counts, mode):
-        lib = nat.lib()
         b, h8, w8, d = desc_raw.shape
         cap = kpts.shape[1]
         out = torch.empty((b, cap, d), device=kpts.device, dtype=torch.float32)
         kout = torch.empty_like(kpts)
-        nat.check(lib.gfc_sp_sample(nat.ptr(desc_raw), b, h8, w8, d, nat.ptr(kpts), nat.ptr(counts), cap, int(mode),
-                                    nat.ptr(out), nat.ptr(kout), nat.stream_ptr(kpts.device)), "gfc_sp_sample")
+        nat.call("gfc_sp_sample", desc_raw, b, h8, w8, d, kpts, counts, cap, int(mode), out, kout)
         return out, kout
 
     def l2norm_rows(self, x):
-        lib = nat.lib()
         rows = x.numel() // x.shape[-1]
-        nat.check(lib.gfc_l2norm_rows(nat.ptr(x), rows, x.shape[-1], nat.stream_ptr(x.device)), "gfc_l2norm_rows")
+        nat.call("gfc_l2norm_rows", x, rows, x.shape[-1])
         return x
 
 

@@ -103,7 +103,7 @@ class DISK(BaseModel):
         if not self.are_weights_initialized:
             raise RuntimeError("DISK: the network has no weights (conf.weights = 'synthetic' or a local file, "
                                "load_state_dict with kornia's DISK parameters, or an explicit dense_fn); nothing is downloaded")
-        conf, lib = self.conf, nat.lib()
+        conf = self.conf
         image = data["image"]
         nat.require_cuda(image, "data['image']")
         dev, b = image.device, image.shape[0]
@@ -116,28 +116,24 @@ class DISK(BaseModel):
         ksc = torch.empty((b, cap), device=dev, dtype=torch.float32)
         counts = torch.empty((b,), device=dev, dtype=torch.int32)
         dense_all = []
-        st = nat.stream_ptr(dev)
         core_ms = 0.0
         with torch.no_grad():
             for i in range(0, b, chunk):  # disk_kornia.py:62-83
                 start = time.perf_counter()
                 heat, dense, layout = self._dense(image[i:i + chunk].float())
                 n_i = heat.shape[0]
-                ws = self._ws.get(lib.gfc_disk_select_workspace_bytes(n_i, h, w), dev)
-                nat.check(lib.gfc_disk_nms_select(nat.ptr(heat), n_i, h, w, window, cutoff, -1 if k is None else int(k),
-                                                  cap, nat.ptr(kpts[i:i + n_i]), nat.ptr(ksc[i:i + n_i]),
-                                                  nat.ptr(counts[i:i + n_i]), nat.ptr(ws), ws.numel(), st),
-                          "gfc_disk_nms_select")
+                ws = self._ws.get(nat.call("gfc_disk_select_workspace_bytes", n_i, h, w), dev)
+                nat.call("gfc_disk_nms_select", heat, n_i, h, w, window, cutoff, -1 if k is None else int(k), cap,
+                         kpts[i:i + n_i], ksc[i:i + n_i], counts[i:i + n_i], ws, ws.numel())
                 core_ms += (time.perf_counter() - start) * 1e3
                 dense_all.append(dense)
             if conf_get(conf, "filter_specular_keypoints") and "specular_mask" in data:
                 # disk_kornia.py:84-107: filter(k + 0.5, offset 0.5) on integer pixels == the four-corner test at k
                 smask, swh = specular_mask_bytes(data, b, dev)
-                nat.check(lib.gfc_sp_filter_keypoints(nat.ptr(kpts), nat.ptr(ksc), nat.ptr(counts), b, cap, nat.ptr(smask),
-                                                      smask.shape[-2], smask.shape[-1], nat.ptr(swh), 0.0, st),
-                          "gfc_sp_filter_keypoints")
+                nat.call("gfc_sp_filter_keypoints", kpts, ksc, counts, b, cap, smask, smask.shape[-2], smask.shape[-1], swh,
+                         0.0)
             d = int(dense_all[0].shape[1] if layout == "nchw" else dense_all[0].shape[3])
-            gather = lib.gfc_disk_gather_descriptors if layout == "nchw" else lib.gfc_disk_gather_descriptors_nhwc
+            gather = "gfc_disk_gather_descriptors" if layout == "nchw" else "gfc_disk_gather_descriptors_nhwc"
             force = conf_get(conf, "force_num_keypoints")
             if force:
                 if k is None:
@@ -158,9 +154,8 @@ class DISK(BaseModel):
             if n_out > 0:
                 for j, i in enumerate(range(0, b, chunk)):  # slots >= count: zeros (pad_and_stack "zeros")
                     dn = dense_all[j]
-                    nat.check(gather(nat.ptr(dn), dn.shape[0], d, h, w, nat.ptr(kpts[i:i + dn.shape[0]]),
-                                     nat.ptr(counts[i:i + dn.shape[0]]), n_out, nat.ptr(desc[i:i + dn.shape[0]]), st),
-                              "gfc_disk_gather_descriptors")
+                    nat.call(gather, dn, dn.shape[0], d, h, w, kpts[i:i + dn.shape[0]], counts[i:i + dn.shape[0]], n_out,
+                             desc[i:i + dn.shape[0]])
             if force:
                 kpts, ksc = pad_keypoints_native(kpts, ksc, counts, n_out, 0, data, image)  # disk_kornia.py:109-124
         pred = {

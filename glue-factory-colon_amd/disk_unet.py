@@ -59,8 +59,7 @@ class _Unet(nn.Module):
 
 
 class _PackedLayer:
-    def __init__(self, conv_holder, cin_run, device, st):
-        lib = nat.lib()
+    def __init__(self, conv_holder, cin_run, device):
         conv = conv_holder[3]
         gate = conv_holder[1]
         w = conv.weight.detach().to(device=device, dtype=torch.float32)
@@ -69,8 +68,9 @@ class _PackedLayer:
             w = torch.cat([w, w.new_zeros((cout, cin_run - cin, 5, 5))], 1)
         w = w.contiguous()
         self.cin, self.cout = cin_run, cout
-        self.w = torch.empty((lib.gfc_disk_conv5x5_packed_floats(cout, cin_run),), device=device, dtype=torch.float32)
-        nat.check(lib.gfc_disk_pack_conv5x5(nat.ptr(w), nat.ptr(self.w), cout, cin_run, st), "gfc_disk_pack_conv5x5")
+        self.w = torch.empty((nat.call("gfc_disk_conv5x5_packed_floats", cout, cin_run),), device=device,
+                             dtype=torch.float32)
+        nat.call("gfc_disk_pack_conv5x5", w, self.w, cout, cin_run)
         self.bias = conv.bias.detach().to(device=device, dtype=torch.float32).contiguous()
         self.slope = (gate.weight.detach().to(device=device, dtype=torch.float32).contiguous()
                       if isinstance(gate, nn.PReLU) else None)
@@ -102,10 +102,9 @@ class DiskUnet(nn.Module):
         return super()._apply(fn, *args, **kwargs)
 
     def _pack(self, device):
-        st = nat.stream_ptr(device)
         cin_run = (4,) + DOWN[:4]  # the first layer runs on RGB + a zero channel
-        layers = [_PackedLayer(self.unet.path_down[i][1], cin_run[i], device, st) for i in range(5)]
-        layers += [_PackedLayer(self.unet.path_up[i].conv, int(self.unet.path_up[i].conv[3].weight.shape[1]), device, st)
+        layers = [_PackedLayer(self.unet.path_down[i][1], cin_run[i], device) for i in range(5)]
+        layers += [_PackedLayer(self.unet.path_up[i].conv, int(self.unet.path_up[i].conv[3].weight.shape[1]), device)
                    for i in range(4)]
         return {"device": device, "layers": layers}
 
@@ -116,18 +115,16 @@ class DiskUnet(nn.Module):
         return self._packed
 
     # ---- one Conv of the network: [statistics ->] convolution with normalisation + gate fused into its input stage ----
-    def _conv(self, layer, x, b, h, w, y, ldy, gated, st):
-        lib = nat.lib()
+    def _conv(self, layer, x, b, h, w, y, ldy, gated):
+        """y may be a channel slice of a wider tensor (channel stride ldy): only then does its raw address go in."""
         mean = rstd = None
         if gated:
             stats = torch.empty((2, b, layer.cin), device=x.device, dtype=torch.float32)
             mean, rstd = stats[0], stats[1]
-            ws = self._ws.get(lib.gfc_disk_instnorm_workspace_bytes(b, layer.cin), x.device)
-            nat.check(lib.gfc_disk_instnorm_stats(nat.ptr(x), b, h, w, layer.cin, 1e-5, nat.ptr(mean), nat.ptr(rstd),
-                                                  nat.ptr(ws), ws.numel(), st), "gfc_disk_instnorm_stats")
-        nat.check(lib.gfc_disk_conv5x5(nat.ptr(x), nat.ptr(mean), nat.ptr(rstd), nat.ptr(layer.slope if gated else None),
-                                       nat.ptr(layer.w), nat.ptr(layer.bias), y.data_ptr(), ldy, b, h, w, layer.cin,
-                                       layer.cout, 0, layer.cout, st), "gfc_disk_conv5x5")
+            ws = self._ws.get(nat.call("gfc_disk_instnorm_workspace_bytes", b, layer.cin), x.device)
+            nat.call("gfc_disk_instnorm_stats", x, b, h, w, layer.cin, 1e-5, mean, rstd, ws, ws.numel())
+        nat.call("gfc_disk_conv5x5", x, mean, rstd, layer.slope if gated else None, layer.w, layer.bias,
+                 y if y.is_contiguous() else y.data_ptr(), ldy, b, h, w, layer.cin, layer.cout, 0, layer.cout)
 
     def dense_nhwc(self, images):
         """images [b,3,H,W] on the GPU (H, W divisible by 16) -> heat-map [b,H,W], descriptors [b,H,W,desc_dim]."""
@@ -142,61 +139,55 @@ class DiskUnet(nn.Module):
                              "1 spatial element")
         dev = images.device
         L = self.ensure_packed(dev)["layers"]
-        lib, st = nat.lib(), nat.stream_ptr(dev)
         images = images.contiguous().float()
         new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
         d = self.desc_dim
         with torch.no_grad():
             x0 = new(b, H, W, 4)
-            nat.check(lib.gfc_disk_nchw3_to_nhwc4(nat.ptr(images), b, H, W, nat.ptr(x0), st), "gfc_disk_nchw3_to_nhwc4")
+            nat.call("gfc_disk_nchw3_to_nhwc4", images, b, H, W, x0)
             # concatenated tensors of the up path, [bottom_big (64) | horizontal]: cat[j] is read by up block j
             hor_c = (64, 64, 32, 16)
             cat = [new(b, H >> (3 - j), W >> (3 - j), 64 + hor_c[j]) for j in range(4)]
             # ---- down path: f_{i+1} goes into the slice of the tensor its up block reads ----
-            self._conv(L[0], x0, b, H, W, cat[3][..., 64:], cat[3].shape[-1], False, st)  # f1
+            self._conv(L[0], x0, b, H, W, cat[3][..., 64:], cat[3].shape[-1], False)  # f1
             src, src_ld, c = cat[3][..., 64:], cat[3].shape[-1], 16
             f5 = None
             for i in range(1, 5):
                 h, w = H >> i, W >> i
                 pooled = new(b, h, w, c)
-                nat.check(lib.gfc_disk_avgpool2(src.data_ptr(), src_ld, b, h * 2, w * 2, c, nat.ptr(pooled), st),
-                          "gfc_disk_avgpool2")
+                nat.call("gfc_disk_avgpool2", src.data_ptr(), src_ld, b, h * 2, w * 2, c, pooled)  # src: a channel slice
                 if i < 4:
                     dst = cat[3 - i]
-                    self._conv(L[i], pooled, b, h, w, dst[..., 64:], dst.shape[-1], True, st)
+                    self._conv(L[i], pooled, b, h, w, dst[..., 64:], dst.shape[-1], True)
                     src, src_ld, c = dst[..., 64:], dst.shape[-1], L[i].cout
                 else:
                     f5 = new(b, h, w, 64)
-                    self._conv(L[4], pooled, b, h, w, f5, 64, True, st)
+                    self._conv(L[4], pooled, b, h, w, f5, 64, True)
             # ---- up path ----
             bot, bh, bw = f5, H >> 4, W >> 4
             heat = desc = None
             for j in range(4):
-                nat.check(lib.gfc_disk_upsample2(nat.ptr(bot), b, bh, bw, 64, nat.ptr(cat[j]), cat[j].shape[-1], st),
-                          "gfc_disk_upsample2")
+                nat.call("gfc_disk_upsample2", bot, b, bh, bw, 64, cat[j], cat[j].shape[-1])
                 bh, bw = bh * 2, bw * 2
                 if j < 3:
                     out = new(b, bh, bw, 64)
-                    self._conv(L[5 + j], cat[j], b, bh, bw, out, 64, True, st)
+                    self._conv(L[5 + j], cat[j], b, bh, bw, out, 64, True)
                     bot = out
                 else:
                     # desc_dim + 1 output channels: descriptors and heat-map go to two arrays (two launches over the same
                     # statistics: the heat-map channel is a 32-wide block of its own either way)
                     desc, heat = new(b, H, W, d), new(b, H, W)
-                    self._conv_split(L[8], cat[3], b, H, W, desc, heat, st)
+                    self._conv_split(L[8], cat[3], b, H, W, desc, heat)
         return heat, desc
 
-    def _conv_split(self, layer, x, b, h, w, desc, heat, st):
-        lib = nat.lib()
+    def _conv_split(self, layer, x, b, h, w, desc, heat):
         d = self.desc_dim
         stats = torch.empty((2, b, layer.cin), device=x.device, dtype=torch.float32)
-        ws = self._ws.get(lib.gfc_disk_instnorm_workspace_bytes(b, layer.cin), x.device)
-        nat.check(lib.gfc_disk_instnorm_stats(nat.ptr(x), b, h, w, layer.cin, 1e-5, nat.ptr(stats[0]), nat.ptr(stats[1]),
-                                              nat.ptr(ws), ws.numel(), st), "gfc_disk_instnorm_stats")
+        ws = self._ws.get(nat.call("gfc_disk_instnorm_workspace_bytes", b, layer.cin), x.device)
+        nat.call("gfc_disk_instnorm_stats", x, b, h, w, layer.cin, 1e-5, stats[0], stats[1], ws, ws.numel())
         for y, ldy, first, count in ((desc, d, 0, d), (heat, 1, d, 1)):  # descriptors [0,d), heat-map channel d
-            nat.check(lib.gfc_disk_conv5x5(nat.ptr(x), nat.ptr(stats[0]), nat.ptr(stats[1]), nat.ptr(layer.slope),
-                                           nat.ptr(layer.w), nat.ptr(layer.bias), nat.ptr(y), ldy, b, h, w, layer.cin,
-                                           layer.cout, first, count, st), "gfc_disk_conv5x5")
+            nat.call("gfc_disk_conv5x5", x, stats[0], stats[1], layer.slope, layer.w, layer.bias, y, ldy, b, h, w,
+                     layer.cin, layer.cout, first, count)
 
     def heatmap_and_dense_descriptors(self, images):
         """kornia's contract: (heat-maps [b,1,H,W], descriptors [b,desc_dim,H,W]) -- views of the NHWC arrays."""

@@ -21,7 +21,6 @@ def match_metrics(H_0to1, kp0, kp1, matches0, pos_th=3.0, neg_th=3.0, return_gt=
     """Batched tensors on the device: H [B,3,3], kp0 [B,M,2], kp1 [B,N,2], matches0 [B,M] -> [B,6]
     (RESULT_KEYS order) and optionally the ground-truth matches [B,M] (-1 unmatched, -2 ignore)."""
     nat.require_cuda(kp0, "keypoints0")
-    lib = nat.lib()
     dev = kp0.device
     b, m, n = kp0.shape[0], kp0.shape[1], kp1.shape[1]
     H = H_0to1.to(device=dev, dtype=torch.float32).reshape(b, 3, 3).contiguous()
@@ -30,9 +29,7 @@ def match_metrics(H_0to1, kp0, kp1, matches0, pos_th=3.0, neg_th=3.0, return_gt=
     m0 = matches0.to(torch.long).contiguous()
     out = torch.empty((b, 6), device=dev, dtype=torch.float32)
     gt = torch.empty((b, m), device=dev, dtype=torch.long) if return_gt else None
-    nat.check(lib.gfc_eval_matches_homography(nat.ptr(k0), nat.ptr(k1), nat.ptr(m0), nat.ptr(H), nat.ptr(Hinv), b, m,
-                                              n, float(pos_th), float(neg_th), nat.ptr(out), nat.ptr(gt),
-                                              nat.stream_ptr(dev)), "gfc_eval_matches_homography")
+    nat.call("gfc_eval_matches_homography", k0, k1, m0, H, Hinv, b, m, n, float(pos_th), float(neg_th), out, gt)
     return (out, gt) if return_gt else out
 
 
@@ -60,7 +57,6 @@ def eval_matches_homography(data: dict, pred: dict) -> dict:
 def homography_dlt(H_0to1, kp0, kp1, matches0, scores0, image_size0):
     """Batched device tensors -> (H_dlt [B,3,3], corner error [B]); +inf where a pair has < 4 matches."""
     nat.require_cuda(kp0, "keypoints0")
-    lib = nat.lib()
     dev = kp0.device
     b, m, n = kp0.shape[0], kp0.shape[1], kp1.shape[1]
     H = H_0to1.to(device=dev, dtype=torch.float32).reshape(b, 9).contiguous()
@@ -70,9 +66,7 @@ def homography_dlt(H_0to1, kp0, kp1, matches0, scores0, image_size0):
     sc = scores0.to(device=dev, dtype=torch.float32).contiguous()
     Hout = torch.empty((b, 3, 3), device=dev, dtype=torch.float32)
     err = torch.empty((b,), device=dev, dtype=torch.float32)
-    nat.check(lib.gfc_eval_homography_dlt(nat.ptr(k0), nat.ptr(k1), nat.ptr(m0), nat.ptr(sc), nat.ptr(H), nat.ptr(size),
-                                          b, m, n, nat.ptr(Hout), nat.ptr(err), nat.stream_ptr(dev)),
-              "gfc_eval_homography_dlt")
+    nat.call("gfc_eval_homography_dlt", k0, k1, m0, sc, H, size, b, m, n, Hout, err)
     return Hout, err
 
 
@@ -205,19 +199,17 @@ def homography_ransac(H_0to1, kp0, kp1, matches0, image_size0, ransac_th, *, num
     if (H_0to1 is None) != (image_size0 is None):
         raise ValueError("H_0to1 and image_size0 are given together or not at all")
     c = _RansacCall(kp0, kp1, matches0, ransac_th, stream_id)
-    lib, dev, b, t = nat.lib(), c.dev, c.b, c.t
+    dev, b, t = c.dev, c.b, c.t
     H = size = err = None
     if H_0to1 is not None:
         H = H_0to1.to(device=dev, dtype=torch.float32).reshape(b, 9).contiguous()
         size = image_size0.to(device=dev, dtype=torch.float32).reshape(b, 2).contiguous()
         err = c.empty(torch.float32)
     Hout, Hmin = c.empty(torch.float64, 3, 3), c.empty(torch.float64, 3, 3)
-    ws = c.workspace(_ransac_ws, lib.gfc_eval_homography_ransac_workspace_bytes(b, c.m, t, int(num_hypotheses)))
-    nat.check(lib.gfc_eval_homography_ransac(nat.ptr(c.k0), nat.ptr(c.k1), nat.ptr(c.m0), nat.ptr(c.sid), nat.ptr(H),
-                                             nat.ptr(size), b, c.m, c.n, c.th_host, t, int(num_hypotheses), int(lo_iters),
-                                             int(seed) & _M64, nat.ptr(Hout), nat.ptr(c.inl), nat.ptr(c.ninl),
-                                             nat.ptr(c.succ), nat.ptr(c.besth), nat.ptr(Hmin), nat.ptr(err), nat.ptr(ws),
-                                             ws.numel(), nat.stream_ptr(dev)), "gfc_eval_homography_ransac")
+    ws = c.workspace(_ransac_ws, nat.call("gfc_eval_homography_ransac_workspace_bytes", b, c.m, t, int(num_hypotheses)))
+    nat.call("gfc_eval_homography_ransac", c.k0, c.k1, c.m0, c.sid, H, size, b, c.m, c.n, c.th_host, t,
+             int(num_hypotheses), int(lo_iters), int(seed) & _M64, Hout, c.inl, c.ninl, c.succ, c.besth, Hmin, err, ws,
+             ws.numel())
     out = {"H": Hout, **c.common(), "H_minimal": Hmin, "thresholds": c.thresholds()}
     if err is not None:
         out["error"] = err
@@ -295,10 +287,8 @@ def pose_project(kp, depth_i, camera_i, camera_j, T_itoj):
     proj = torch.empty((b, k, 2), device=dev, dtype=torch.float32)
     valid = torch.empty((b, k), device=dev, dtype=torch.uint8)
     visible = torch.empty((b, k), device=dev, dtype=torch.uint8)
-    nat.check(nat.lib().gfc_eval_pose_project(nat.ptr(pts), nat.ptr(depth), nat.ptr(cam_i), model_i, nat.ptr(cam_j),
-                                              model_j, nat.ptr(T), b, k, depth.shape[1], depth.shape[2], nat.ptr(d),
-                                              nat.ptr(valid), nat.ptr(proj), nat.ptr(visible), nat.stream_ptr(dev)),
-              "gfc_eval_pose_project")
+    nat.call("gfc_eval_pose_project", pts, depth, cam_i, model_i, cam_j, model_j, T, b, k, depth.shape[1], depth.shape[2],
+             d, valid, proj, visible)
     return d, valid.bool(), proj, visible.bool()
 
 
@@ -317,11 +307,8 @@ def pose_depth_metrics(kp0, kp1, matches0, depth0, depth1, camera0, camera1, T_0
     out = torch.empty((b, 7), device=dev, dtype=torch.float32)
     gt0 = torch.empty((b, m), device=dev, dtype=torch.long) if return_gt else None
     gt1 = torch.empty((b, n), device=dev, dtype=torch.long) if return_gt else None
-    nat.check(nat.lib().gfc_eval_matches_depth(nat.ptr(k0), nat.ptr(k1), nat.ptr(m0), nat.ptr(d0), nat.ptr(d1),
-                                               nat.ptr(cam0), model0, nat.ptr(cam1), model1, nat.ptr(T01), nat.ptr(T10),
-                                               b, m, n, d0.shape[1], d0.shape[2], d1.shape[1], d1.shape[2],
-                                               float(pos_th), float(neg_th), nat.ptr(out), nat.ptr(gt0), nat.ptr(gt1),
-                                               nat.stream_ptr(dev)), "gfc_eval_matches_depth")
+    nat.call("gfc_eval_matches_depth", k0, k1, m0, d0, d1, cam0, model0, cam1, model1, T01, T10, b, m, n, d0.shape[1],
+             d0.shape[2], d1.shape[1], d1.shape[2], float(pos_th), float(neg_th), out, gt0, gt1)
     return (out, gt0, gt1) if return_gt else out
 
 
@@ -334,9 +321,7 @@ def pose_epipolar_metrics(kp0, kp1, matches0, camera0, camera1, T_0to1):
     k0, k1 = kp0.float().contiguous(), kp1.float().contiguous()
     m0 = matches0.to(device=dev, dtype=torch.long).contiguous()
     out = torch.empty((b, 5), device=dev, dtype=torch.float32)
-    nat.check(nat.lib().gfc_eval_matches_epipolar(nat.ptr(k0), nat.ptr(k1), nat.ptr(m0), nat.ptr(cam0), model0,
-                                                  nat.ptr(cam1), model1, nat.ptr(T01), b, m, n, nat.ptr(out),
-                                                  nat.stream_ptr(dev)), "gfc_eval_matches_epipolar")
+    nat.call("gfc_eval_matches_epipolar", k0, k1, m0, cam0, model0, cam1, model1, T01, b, m, n, out)
     return out
 
 
@@ -443,8 +428,7 @@ def pose_image2cam(kp, camera):
     cam, model = geometry.camera_args(camera, b, dev)
     pts = kp.float().contiguous()
     out = torch.empty((b, k, 2), device=dev, dtype=torch.float32)
-    nat.check(nat.lib().gfc_eval_pose_image2cam(nat.ptr(pts), nat.ptr(cam), model, b, k, nat.ptr(out), nat.stream_ptr(dev)),
-              "gfc_eval_pose_image2cam")
+    nat.call("gfc_eval_pose_image2cam", pts, cam, model, b, k, out)
     return out
 
 
@@ -461,7 +445,7 @@ def relative_pose_ransac(kp0, kp1, matches0, camera0, camera1, ransac_th, T_0to1
     from . import geometry
 
     c = _RansacCall(kp0, kp1, matches0, ransac_th, stream_id)
-    lib, dev, b, t = nat.lib(), c.dev, c.b, c.t
+    dev, b, t = c.dev, c.b, c.t
     cam0, model0 = geometry.camera_args(camera0, b, dev)
     cam1, model1 = geometry.camera_args(camera1, b, dev)
     T01 = rerr = terr = None
@@ -471,13 +455,11 @@ def relative_pose_ransac(kp0, kp1, matches0, camera0, camera1, ransac_th, T_0to1
     R, tv = c.empty(torch.float64, 3, 3), c.empty(torch.float64, 3)
     E, Emin = c.empty(torch.float64, 3, 3), c.empty(torch.float64, 3, 3)
     bestk = c.empty(torch.int32)
-    ws = c.workspace(_relpose_ws, lib.gfc_eval_relative_pose_ransac_workspace_bytes(b, c.m, t, int(num_hypotheses)))
-    nat.check(lib.gfc_eval_relative_pose_ransac(
-        nat.ptr(c.k0), nat.ptr(c.k1), nat.ptr(c.m0), nat.ptr(c.sid), nat.ptr(cam0), model0, nat.ptr(cam1), model1,
-        nat.ptr(T01), b, c.m, c.n, c.th_host, t, int(num_hypotheses), int(lo_iters), int(seed) & _M64,
-        float(ignore_gt_t_thr), nat.ptr(R), nat.ptr(tv), nat.ptr(E), nat.ptr(Emin), nat.ptr(c.inl), nat.ptr(c.ninl),
-        nat.ptr(c.succ), nat.ptr(c.besth), nat.ptr(bestk), nat.ptr(rerr), nat.ptr(terr), nat.ptr(ws), ws.numel(),
-        nat.stream_ptr(dev)), "gfc_eval_relative_pose_ransac")
+    ws = c.workspace(_relpose_ws,
+                     nat.call("gfc_eval_relative_pose_ransac_workspace_bytes", b, c.m, t, int(num_hypotheses)))
+    nat.call("gfc_eval_relative_pose_ransac", c.k0, c.k1, c.m0, c.sid, cam0, model0, cam1, model1, T01, b, c.m, c.n,
+             c.th_host, t, int(num_hypotheses), int(lo_iters), int(seed) & _M64, float(ignore_gt_t_thr), R, tv, E, Emin,
+             c.inl, c.ninl, c.succ, c.besth, bestk, rerr, terr, ws, ws.numel())
     out = {"R": R, "t": tv, "E": E, "E_minimal": Emin, **c.common(), "best_solution": bestk,
            "thresholds": c.thresholds()}
     if rerr is not None:

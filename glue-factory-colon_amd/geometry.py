@@ -13,8 +13,9 @@ reference's wrappers, or plain tensors) into the flat fp32 arrays of the C ABI.
 import numpy as np
 import torch
 
+from ._native import GFC_CAM_OPENCV, GFC_CAM_OPENCV_FISHEYE, GFC_CAM_PINHOLE, GFC_CAM_RADIAL
+
 CAMERA_MODELS = ("PINHOLE", "RADIAL", "OPENCV", "OPENCV_FISHEYE")
-GFC_CAM_PINHOLE, GFC_CAM_RADIAL, GFC_CAM_OPENCV, GFC_CAM_OPENCV_FISHEYE = range(4)
 _WIDTH_MODEL = {6: "PINHOLE", 8: "RADIAL", 10: "OPENCV"}
 
 

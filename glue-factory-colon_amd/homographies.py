@@ -142,11 +142,11 @@ def warp_perspective(src, src_index, matrices, size, crop=None, gray=False):
             src = src[None, :, :, None]
         elif src.ndim == 3:
             src = src[None]
-        kind, (s, h, w, c) = 1, src.shape
+        kind, (s, h, w, c) = nat.GFC_RS_U8_HWC, src.shape
     elif src.dtype == torch.float32:
         if src.ndim == 3:
             src = src[None]
-        kind, (s, c, h, w) = 0, src.shape
+        kind, (s, c, h, w) = nat.GFC_RS_F32_CHW, src.shape
     else:
         raise ValueError(f"src: uint8 [S,H,W,C] or float32 [S,C,H,W] expected, got {src.dtype}")
     if src.ndim != 4:
@@ -159,10 +159,8 @@ def warp_perspective(src, src_index, matrices, size, crop=None, gray=False):
     left, top, cw, ch = (0, 0, w, h) if crop is None else (int(v) for v in crop)
     oh, ow = int(size[0]), int(size[1])
     out = torch.empty((max(b, 0), 1 if gray else c, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=src.device)
-    nat.check(nat.lib().gfc_warp_perspective(nat.ptr(src.contiguous()), kind, s, c, h, w, left, top, cw, ch,
-                                             nat.ptr(src_index.contiguous()), nat.ptr(matrices.contiguous()), b,
-                                             1 if gray else 0, nat.ptr(out), oh, ow, nat.stream_ptr(src.device)),
-              "gfc_warp_perspective")
+    nat.call("gfc_warp_perspective", src.contiguous(), kind, s, c, h, w, left, top, cw, ch, src_index.contiguous(),
+             matrices.contiguous(), b, 1 if gray else 0, out, oh, ow)
     return out
 
 

@@ -34,7 +34,6 @@ def resize(img, size, align_corners=None, antialias=True, bgr=False):
     """img: float [C,H,W] / [B,C,H,W] on the GPU, or uint8 [H,W,C] / [H,W] / [B,H,W,C] (decoded image).
     -> float [.., C, size[0], size[1]]."""
     nat.require_cuda(img, "img")
-    lib = nat.lib()
     oh, ow = int(size[0]), int(size[1])
     if img.dtype == torch.uint8:
         x = img if img.ndim != 2 else img[..., None]
@@ -48,14 +47,12 @@ def resize(img, size, align_corners=None, antialias=True, bgr=False):
         b, c, h, w = x.shape
         u8 = 0
     out = torch.empty((b, c, oh, ow), device=img.device, dtype=torch.float32)
-    nat.check(lib.gfc_preprocess_resize(nat.ptr(x), u8, int(bool(bgr)), b, c, h, w, nat.ptr(out), oh, ow,
-                                        int(bool(align_corners)), int(bool(antialias)), nat.stream_ptr(img.device)),
-              "gfc_preprocess_resize")
+    nat.call("gfc_preprocess_resize", x, u8, int(bool(bgr)), b, c, h, w, out, oh, ow, int(bool(align_corners)),
+             int(bool(antialias)))
     return out if batched else out[0]
 
 
-RESAMPLE_MODES = {"nearest": 0, "area": 1}  # GFC_RS_NEAREST / GFC_RS_AREA
-_RS_F32_CHW, _RS_U8_HWC, _RS_U8_PLANE, _RS_BITS = range(4)
+RESAMPLE_MODES = {"nearest": nat.GFC_RS_NEAREST, "area": nat.GFC_RS_AREA}
 
 
 def downscales(in_hw, out_hw):
@@ -76,7 +73,6 @@ def resample(img, size, mode, crop=None, antialias=False, value_scale=1.0, want_
     nat.require_cuda(img, "img")
     if mode not in RESAMPLE_MODES:
         raise NotImplementedError(f"resample mode {mode!r}: 'nearest' and 'area' are built")
-    lib = nat.lib()
     oh, ow = int(size[0]), int(size[1])
     lead = None
     if bits_shape is not None:
@@ -86,32 +82,31 @@ def resample(img, size, mode, crop=None, antialias=False, value_scale=1.0, want_
         x = (img if img.ndim == 2 else img[None]).contiguous()
         if x.shape[1] != (h * w + 7) // 8:
             raise ValueError(f"packed bits: {x.shape[1]} bytes per plane for a {h}x{w} mask")
-        b, c, kind, lead = x.shape[0], 1, _RS_BITS, tuple(img.shape[:-1])
+        b, c, kind, lead = x.shape[0], 1, nat.GFC_RS_BITS, tuple(img.shape[:-1])
     elif img.dtype == torch.bool:
         if img.ndim not in (2, 3):
             raise ValueError(f"mask plane: expected bool [H,W] or [B,H,W], got {tuple(img.shape)}")
         x = (img if img.ndim == 3 else img[None]).contiguous()
-        (b, h, w), c, kind, lead = x.shape, 1, _RS_U8_PLANE, tuple(img.shape[:-2])
+        (b, h, w), c, kind, lead = x.shape, 1, nat.GFC_RS_U8_PLANE, tuple(img.shape[:-2])
     elif img.dtype == torch.uint8:
         x = img if img.ndim != 2 else img[..., None]
         x = (x if x.ndim == 4 else x[None]).contiguous()
-        (b, h, w, c), kind = x.shape, _RS_U8_HWC
+        (b, h, w, c), kind = x.shape, nat.GFC_RS_U8_HWC
         lead = ((b,) if img.ndim == 4 else ()) + (c,)
     else:
         x = (img.float().reshape((-1,) + tuple(img.shape[-3:])) if img.ndim >= 3 else img.float()[None, None]).contiguous()
-        (b, c, h, w), kind, lead = x.shape, _RS_F32_CHW, tuple(img.shape[:-2])
+        (b, c, h, w), kind, lead = x.shape, nat.GFC_RS_F32_CHW, tuple(img.shape[:-2])
     left, top, cw, ch = (0, 0, w, h) if crop is None else (int(v) for v in crop)
     if mode == "area" and antialias and 0 < cw and 0 < ch and downscales((ch, cw), (oh, ow)):
         raise NotImplementedError("interpolation 'area' with antialias=True on a down-scale is not built "
                                   "(the reference's own 'area' configuration sets antialias: False)")
-    is_mask = kind in (_RS_U8_PLANE, _RS_BITS)
+    is_mask = kind in (nat.GFC_RS_U8_PLANE, nat.GFC_RS_BITS)
     if is_mask and want_valid:
         raise ValueError("want_valid with a mask source")
     out = torch.empty((b, c, oh, ow), device=img.device, dtype=torch.uint8 if is_mask else torch.float32)
     valid = torch.empty_like(out) if want_valid else None
-    nat.check(lib.gfc_preprocess_resample(nat.ptr(x), kind, b, c, h, w, left, top, cw, ch, RESAMPLE_MODES[mode],
-                                          int(bool(antialias)), float(value_scale), nat.ptr(out), nat.ptr(valid), oh, ow,
-                                          nat.stream_ptr(img.device)), "gfc_preprocess_resample")
+    nat.call("gfc_preprocess_resample", x, kind, b, c, h, w, left, top, cw, ch, RESAMPLE_MODES[mode], int(bool(antialias)),
+             float(value_scale), out, valid, oh, ow)
     if is_mask:
         out = out.view(torch.bool)
     out = out.reshape(lead + (oh, ow))

@@ -216,17 +216,13 @@ class LightGlue(nn.Module):
 
     # -- small problems: the whole launch sequence as one HIP graph ------------------------
     def _launch_packed(self, kp, de, s0, s1, so, b, m, n, m0, m1, ms0, ms1, scores, rows, ws, trace=None):
-        lib = nat.lib()
-        nat.check(lib.gfc_lg_forward_packed(
-            ctypes.byref(self._packed[0]), nat.ptr(kp), nat.ptr(de), nat.ptr(s0), nat.ptr(s1), nat.ptr(so), b, m, n,
-            float(self.conf.filter_threshold), nat.ptr(m0), nat.ptr(m1), nat.ptr(ms0), nat.ptr(ms1), nat.ptr(scores),
-            nat.ptr(rows), nat.ptr(ws), ws.numel(), ctypes.byref(trace.c) if trace is not None else None,
-            nat.stream_ptr(kp.device)), "gfc_lg_forward_packed")
+        nat.call("gfc_lg_forward_packed", ctypes.byref(self._packed[0]), kp, de, s0, s1, so, b, m, n,
+                 float(self.conf.filter_threshold), m0, m1, ms0, ms1, scores, rows, ws, ws.numel(),
+                 ctypes.byref(trace.c) if trace is not None else None)
 
     def _graph_entry(self, key, kp, de, s0, s1, so, b, m, n):
         """Static buffers + the captured launch sequence of gfc_lg_forward_packed for one problem shape."""
         device, d = kp.device, self.conf.descriptor_dim
-        lib = nat.lib()
         e = {"kp": torch.empty_like(kp), "de": torch.empty_like(de), "s0": torch.empty_like(s0),
              "s1": torch.empty_like(s1), "so": None if so is None else torch.empty_like(so),
              "m0": torch.empty((b, m), device=device, dtype=torch.long),
@@ -234,7 +230,7 @@ class LightGlue(nn.Module):
              "ms0": torch.empty((b, m), device=device), "ms1": torch.empty((b, n), device=device),
              "scores": torch.empty((b, m + 1, n + 1), device=device),
              "rows": torch.empty((b * (m + n), d), device=device),
-             "ws": torch.empty(int(lib.gfc_lg_packed_workspace_bytes(b, m, n)), dtype=torch.uint8, device=device)}
+             "ws": torch.empty(nat.call("gfc_lg_packed_workspace_bytes", b, m, n), dtype=torch.uint8, device=device)}
         for name, src in (("kp", kp), ("de", de), ("s0", s0), ("s1", s1), ("so", so)):
             if src is not None:
                 e[name].copy_(src)
@@ -403,7 +399,6 @@ class LightGlue(nn.Module):
         d = conf.descriptor_dim
         if m > 0 and n > 0:
             self.ensure_packed(device)
-            lib = nat.lib()
             s0 = torch.as_tensor(size0, device=device, dtype=torch.float32).expand(b, 2).contiguous()
             s1 = torch.as_tensor(size1, device=device, dtype=torch.float32).expand(b, 2).contiguous()
             # side-0 rows then side-1 rows: zero-copy when both views came out of ONE extractor call (adjacent
@@ -433,7 +428,7 @@ class LightGlue(nn.Module):
                 # one row buffer [b*m + b*n, 256]: the library's layers work in place on it and leave the last layer's
                 # descriptors there; ref_descriptors0/1 are its two halves (no copy out)
                 rows = torch.empty((b * (m + n), d), device=device)
-                ws = self._ws.get(lib.gfc_lg_packed_workspace_bytes(b, m, n), device)
+                ws = self._ws.get(nat.call("gfc_lg_packed_workspace_bytes", b, m, n), device)
                 self._launch_packed(kp, de, s0, s1, so, b, m, n, m0, m1, ms0, ms1, scores, rows, ws, self.trace)
         else:  # the reference's early return (lightglue.py:298-303): all -1 / zeros
             m0 = torch.full((b, m), -1, device=device, dtype=torch.long)
@@ -466,17 +461,15 @@ class LightGlue(nn.Module):
         so = torch.cat([v[2] for v in views], 0).contiguous() if self.conf.add_scale_ori else None
         return kp, de, so
 
-    def _input_proj(self, params, xin, out, rows, stream):
+    def _input_proj(self, params, xin, out, rows):
         """out [rows,256] = input_proj(xin [rows,input_dim]) in the matcher's precision (lightglue.py:352-355,464-465)."""
-        lib, din, d = nat.lib(), self.conf.input_dim, self.conf.descriptor_dim
+        din, d = self.conf.input_dim, self.conf.descriptor_dim
         if params.precision == nat.GFC_LG_FP16:
-            status = lib.gfc_linear_f16(nat.ptr(xin), 0, din, din, None, 0, 0, 0, params.input_proj_w16, din,
-                                        params.input_proj_b, 1.0, None, None, None, None, 0, nat.ptr(out), 0, d, rows, d,
-                                        stream)
+            nat.call("gfc_linear_f16", xin, 0, din, din, None, 0, 0, 0, params.input_proj_w16, din, params.input_proj_b,
+                     1.0, None, None, None, None, 0, out, 0, d, rows, d)
         else:
-            status = lib.gfc_linear(nat.ptr(xin), din, din, None, 0, 0, params.input_proj_w, din, params.input_proj_b,
-                                    None, None, 1.0, None, None, None, 0, nat.ptr(out), d, rows, d, stream)
-        nat.check(status, "input_proj")
+            nat.call("gfc_linear", xin, din, din, None, 0, 0, params.input_proj_w, din, params.input_proj_b, None, None,
+                     1.0, None, None, None, 0, out, d, rows, d)
 
     # -- several pairs of DIFFERENT sizes through one launch sequence -----------------------------
     def forward_pairs(self, items: list) -> list:
@@ -509,7 +502,7 @@ class LightGlue(nn.Module):
         return outs
 
     def _forward_ragged(self, items):
-        conf, lib = self.conf, nat.lib()
+        conf = self.conf
         device = items[0]["keypoints0"].device
         nat.require_cuda(items[0]["keypoints0"], "data['keypoints0']")
         self.ensure_packed(device)
@@ -532,12 +525,10 @@ class LightGlue(nn.Module):
         sc0, sc1 = torch.empty((sm,), device=device), torch.empty((sn,), device=device)
         scores = torch.empty((sum((a + 1) * (c + 1) for a, c in zip(ms, ns)),), device=device)
         rows = torch.empty((sm + sn, d), device=device)
-        ws = self._ws.get(lib.gfc_lg_ragged_workspace_bytes(b, cm, cn), device)
-        nat.check(lib.gfc_lg_forward_ragged(
-            ctypes.byref(self._packed[0]), nat.ptr(kp), nat.ptr(de), nat.ptr(size0), nat.ptr(size1), nat.ptr(so), b, cm,
-            cn, float(conf.filter_threshold), nat.ptr(m0), nat.ptr(m1), nat.ptr(sc0), nat.ptr(sc1), nat.ptr(scores),
-            nat.ptr(rows), nat.ptr(ws), ws.numel(), ctypes.byref(self.trace.c) if self.trace is not None else None,
-            nat.stream_ptr(device)), "gfc_lg_forward_ragged")
+        ws = self._ws.get(nat.call("gfc_lg_ragged_workspace_bytes", b, cm, cn), device)
+        nat.call("gfc_lg_forward_ragged", ctypes.byref(self._packed[0]), kp, de, size0, size1, so, b, cm, cn,
+                 float(conf.filter_threshold), m0, m1, sc0, sc1, scores, rows, ws, ws.numel(),
+                 ctypes.byref(self.trace.c) if self.trace is not None else None)
         # per-pair views of the flat outputs; rows: group after group, side 0 then side 1 inside a group
         outs = [None] * b
         o0 = o1 = os_ = r = 0
@@ -560,13 +551,12 @@ class LightGlue(nn.Module):
         the stop / prune decisions on the token confidences and matchabilities computed by `gfc_lg_rowdot`
         (one small device->host read per layer, as `check_if_stop` does in the reference) and re-packs the
         surviving rows between layers (index_select: plumbing)."""
-        conf, lib = self.conf, nat.lib()
+        conf = self.conf
         b, m, _ = data["keypoints0"].shape
         n = data["keypoints1"].shape[1]
         assert b == 1
         device = data["keypoints0"].device
         params = self.ensure_packed(device)[0]
-        st = nat.stream_ptr(device)
         d = conf.descriptor_dim
         do_early_stop, do_prune = conf.depth_confidence > 0, conf.width_confidence > 0
         # packed rows: image 0 first
@@ -574,15 +564,14 @@ class LightGlue(nn.Module):
         kp, x, so = self._pack_views(views)
         if conf.input_dim != d:
             xin, x = x, torch.empty((m + n, d), device=device, dtype=torch.float32)
-            self._input_proj(params, xin, x, m + n, st)
+            self._input_proj(params, xin, x, m + n)
         sizes = torch.cat([v[3] for v in views], 0).contiguous()
         row0 = torch.tensor([0, m], dtype=torch.int32, device=device)
         cnt = torch.tensor([m, n], dtype=torch.int32, device=device)
         cos = torch.empty((m + n, 64), device=device)
         sin = torch.empty((m + n, 64), device=device)
-        nat.check(lib.gfc_lg_posenc(nat.ptr(kp), nat.ptr(so), nat.ptr(sizes), nat.ptr(row0), nat.ptr(cnt), 2, max(m, n),
-                                    params.posenc_wr, 4 if so is not None else 2, nat.ptr(cos), nat.ptr(sin), st),
-                  "gfc_lg_posenc")
+        nat.call("gfc_lg_posenc", kp, so, sizes, row0, cnt, 2, max(m, n), params.posenc_wr, 4 if so is not None else 2,
+                 cos, sin)
         ind0 = torch.arange(m, device=device)
         ind1 = torch.arange(n, device=device)
         prune0 = torch.ones((1, m), device=device, dtype=torch.long)
@@ -593,26 +582,23 @@ class LightGlue(nn.Module):
         for i in range(conf.n_layers):
             self_p = torch.tensor([[0, cm, 0, cm], [cm, cn, cm, cn]], dtype=torch.int32, device=device)
             cross_p = torch.tensor([[0, cm, cm, cn], [cm, cn, 0, cm]], dtype=torch.int32, device=device)
-            ws = self._ws.get(lib.gfc_lg_layer_workspace_bytes(cm + cn), device)
-            nat.check(lib.gfc_lg_layer(ctypes.byref(params), i, nat.ptr(x), nat.ptr(cos), nat.ptr(sin), cm + cn,
-                                       nat.ptr(self_p), nat.ptr(cross_p), 2, max(cm, cn), nat.ptr(ws), ws.numel(), st),
-                      "gfc_lg_layer")
+            ws = self._ws.get(nat.call("gfc_lg_layer_workspace_bytes", cm + cn), device)
+            nat.call("gfc_lg_layer", ctypes.byref(params), i, x, cos, sin, cm + cn, self_p, cross_p, 2, max(cm, cn), ws,
+                     ws.numel())
             last = i
             if i == conf.n_layers - 1:
                 break
             tok = None
             if do_early_stop:
                 tok = torch.empty((cm + cn,), device=device)
-                nat.check(lib.gfc_lg_rowdot(nat.ptr(x), d, cm + cn, params.token_w[i], params.token_b[i], 1,
-                                            nat.ptr(tok), st), "gfc_lg_rowdot")
+                nat.call("gfc_lg_rowdot", x, d, cm + cn, params.token_w[i], params.token_b[i], 1, tok)
                 # check_if_stop (lightglue.py:569-580): the ratio is taken over the ORIGINAL m + n points
                 ratio = 1.0 - (tok < thresholds[i]).float().sum() / (m + n)
                 if ratio.item() > conf.depth_confidence:
                     break
             if do_prune:
                 sc = torch.empty((cm + cn,), device=device)
-                nat.check(lib.gfc_lg_rowdot(nat.ptr(x), d, cm + cn, params.matchability_w[i],
-                                            params.matchability_b[i], 1, nat.ptr(sc), st), "gfc_lg_rowdot")
+                nat.call("gfc_lg_rowdot", x, d, cm + cn, params.matchability_w[i], params.matchability_b[i], 1, sc)
                 keep = sc > (1 - conf.width_confidence)  # get_pruning_mask, lightglue.py:560-567
                 if tok is not None:
                     keep = keep | (tok <= thresholds[i])
@@ -628,14 +614,14 @@ class LightGlue(nn.Module):
                     break
         if not do_prune:
             ind0 = ind1 = prune0 = prune1 = None  # every point ran through all n_layers
-        return self._finish_adaptive(params, last, x, cm, cn, m, n, ind0, ind1, prune0, prune1, st)
+        return self._finish_adaptive(params, last, x, cm, cn, m, n, ind0, ind1, prune0, prune1)
 
-    def _finish_adaptive(self, params, layer, x, cm, cn, m, n, ind0, ind1, prune0, prune1, st):
+    def _finish_adaptive(self, params, layer, x, cm, cn, m, n, ind0, ind1, prune0, prune1):
         """The end of both adaptive paths for one pair of m and n points: the assignment head of `layer` on its surviving
         rows x [cm + cn, 256] (side 0 first), matches and scores scattered back through ind0 / ind1 (the survivors'
         un-pruned indices, int64; None when nothing is pruned), and the result dict with prune0/1 [1,m] / [1,n] (None:
         every point ran through all layers).  ref_descriptors0/1 are views of x."""
-        conf, lib, device = self.conf, nat.lib(), x.device
+        conf, device = self.conf, x.device
         m0 = torch.full((1, m), -1, device=device, dtype=torch.long)
         m1 = torch.full((1, n), -1, device=device, dtype=torch.long)
         ms0 = torch.zeros((1, m), device=device)
@@ -645,10 +631,9 @@ class LightGlue(nn.Module):
             pm0 = torch.empty((1, cm), device=device, dtype=torch.long)
             pm1 = torch.empty((1, cn), device=device, dtype=torch.long)
             ps0, ps1 = torch.empty((1, cm), device=device), torch.empty((1, cn), device=device)
-            ws = self._ws.get(lib.gfc_lg_assign_workspace_bytes(1, cm, cn), device)
-            nat.check(lib.gfc_lg_assign(ctypes.byref(params), layer, nat.ptr(x), ctypes.c_void_p(x[cm:].data_ptr()), 1,
-                                        cm, cn, float(conf.filter_threshold), nat.ptr(pm0), nat.ptr(pm1), nat.ptr(ps0),
-                                        nat.ptr(ps1), nat.ptr(scores), nat.ptr(ws), ws.numel(), st), "gfc_lg_assign")
+            ws = self._ws.get(nat.call("gfc_lg_assign_workspace_bytes", 1, cm, cn), device)
+            nat.call("gfc_lg_assign", ctypes.byref(params), layer, x, x[cm:], 1, cm, cn, float(conf.filter_threshold),
+                     pm0, pm1, ps0, ps1, scores, ws, ws.numel())
             if ind0 is not None:  # scatter back to the un-pruned indexing (lightglue.py:527-536)
                 m0[:, ind0] = torch.where(pm0 == -1, -1, ind1[pm0.clamp(min=0)])
                 m1[:, ind1] = torch.where(pm1 == -1, -1, ind0[pm1.clamp(min=0)])
@@ -669,11 +654,10 @@ class LightGlue(nn.Module):
         layer; it tells which pairs finished and where every pair's rows went.  A pair that finishes at a layer gets that
         layer's assignment head on its rows, which the step has put behind the live region; both paths end a pair in
         `_finish_adaptive`."""
-        conf, lib = self.conf, nat.lib()
+        conf = self.conf
         device = items[0]["keypoints0"].device
         nat.require_cuda(items[0]["keypoints0"], "data['keypoints0']")
         params = self.ensure_packed(device)[0]
-        st = nat.stream_ptr(device)
         d, din, nb = conf.descriptor_dim, conf.input_dim, len(items)
         assert 0 < nb <= nat.GFC_LG_MAX_RAGGED_PAIRS
         do_stop, do_prune = conf.depth_confidence > 0, conf.width_confidence > 0
@@ -686,7 +670,7 @@ class LightGlue(nn.Module):
         sizes = torch.cat([v[3] for v in views], 0).contiguous()
         if din != d:
             xin, xa = xa, torch.empty((total, d), device=device)
-            self._input_proj(params, xin, xa, total, st)
+            self._input_proj(params, xin, xa, total)
         xb = torch.empty((total, d), device=device)
         # host tables of the first layer, one upload: segments, pairs, prune offsets, problems, un-pruned indices
         seg, pairs, self_p, cross_p, ind_parts = [], [], [], [], []
@@ -716,9 +700,8 @@ class LightGlue(nn.Module):
         indb = torch.empty_like(inda)
         cosa, sina = torch.empty((total, 64), device=device), torch.empty((total, 64), device=device)
         cosb, sinb = torch.empty_like(cosa), torch.empty_like(sina)
-        nat.check(lib.gfc_lg_posenc(nat.ptr(kp), nat.ptr(so), nat.ptr(sizes), nat.ptr(row0), nat.ptr(cnt), 2 * nb,
-                                    max(ms + ns), params.posenc_wr, 4 if so is not None else 2, nat.ptr(cosa),
-                                    nat.ptr(sina), st), "gfc_lg_posenc")
+        nat.call("gfc_lg_posenc", kp, so, sizes, row0, cnt, 2 * nb, max(ms + ns), params.posenc_wr,
+                 4 if so is not None else 2, cosa, sina)
         prune = torch.ones((total,), dtype=torch.int32, device=device) if do_prune else None
         report = torch.empty((nb, 4), dtype=torch.int32, device=device)
         if self._report_host is None:
@@ -726,7 +709,7 @@ class LightGlue(nn.Module):
         report_host = self._report_host
         thresholds = self.confidence_thresholds.tolist()
         keep_thr = float(1 - conf.width_confidence)
-        step_ws_bytes = lib.gfc_lg_adaptive_step_workspace_bytes(nb, total)
+        step_ws_bytes = nat.call("gfc_lg_adaptive_step_workspace_bytes", nb, total)
         bufs = [(xa, cosa, sina, inda), (xb, cosb, sinb, indb)]
         cur = 0
         # live pairs in buffer order: (slot, first row, rows of side 0, rows of side 1)
@@ -746,28 +729,25 @@ class LightGlue(nn.Module):
                 ind0, ind1 = ind[r0:r0 + cm].long(), ind[r0 + cm:r0 + cm + cn].long()
                 o = sum(ms[:slot]) + sum(ns[:slot])
                 prune0, prune1 = prune[o:o + m].long()[None], prune[o + m:o + m + n].long()[None]
-            outs[slot] = self._finish_adaptive(params, layer, rows, cm, cn, m, n, ind0, ind1, prune0, prune1, st)
+            outs[slot] = self._finish_adaptive(params, layer, rows, cm, cn, m, n, ind0, ind1, prune0, prune1)
 
         for i in range(conf.n_layers):
             x, cos, sin, ind = bufs[cur]
             _, _, self_t, cross_t = tables(cur)
             rows = sum(cm + cn for _, _, cm, cn in live)
             max_n = max(max(cm, cn) for _, _, cm, cn in live)
-            ws = self._ws.get(max(lib.gfc_lg_layer_workspace_bytes(rows), step_ws_bytes), device)
-            nat.check(lib.gfc_lg_layer(ctypes.byref(params), i, nat.ptr(x), nat.ptr(cos), nat.ptr(sin), rows,
-                                       nat.ptr(self_t), nat.ptr(cross_t), 2 * len(live), max_n, nat.ptr(ws), ws.numel(),
-                                       st), "gfc_lg_layer")
+            ws = self._ws.get(max(nat.call("gfc_lg_layer_workspace_bytes", rows), step_ws_bytes), device)
+            nat.call("gfc_lg_layer", ctypes.byref(params), i, x, cos, sin, rows, self_t, cross_t, 2 * len(live), max_n,
+                     ws, ws.numel())
             if i == conf.n_layers - 1:
                 break
             seg_t, pairs_t, _, _ = tables(cur)
             seg_o, pairs_o, self_o, cross_o = tables(1 - cur)
             xo, coso, sino, indo = bufs[1 - cur]
-            nat.check(lib.gfc_lg_adaptive_step(
-                ctypes.byref(params), i, nat.ptr(x), nat.ptr(cos), nat.ptr(sin), nat.ptr(ind), rows, nat.ptr(seg_t),
-                nat.ptr(pairs_t), nat.ptr(prune_off), nb, len(live), max_n, thresholds[i], keep_thr,
-                float(conf.depth_confidence), int(do_stop), int(do_prune), nat.ptr(xo), nat.ptr(coso), nat.ptr(sino),
-                nat.ptr(indo), nat.ptr(prune), total, nat.ptr(self_o), nat.ptr(cross_o), nat.ptr(seg_o),
-                nat.ptr(pairs_o), nat.ptr(report), nat.ptr(ws), ws.numel(), st), "gfc_lg_adaptive_step")
+            nat.call("gfc_lg_adaptive_step", ctypes.byref(params), i, x, cos, sin, ind, rows, seg_t, pairs_t, prune_off,
+                     nb, len(live), max_n, thresholds[i], keep_thr, float(conf.depth_confidence), int(do_stop),
+                     int(do_prune), xo, coso, sino, indo, prune, total, self_o, cross_o, seg_o, pairs_o, report, ws,
+                     ws.numel())
             report_host[:len(live)].copy_(report[:len(live)], non_blocking=True)
             stream.synchronize()  # the one device->host read of the layer
             rep = report_host[:len(live)].tolist()

@@ -34,13 +34,10 @@ class NearestNeighborMatcher(BaseModel):
         sim = torch.zeros((b, m, n), device=dev)
         la = torch.zeros((b, m + 1, n + 1), device=dev)
         if m > 0 and n > 0:
-            lib = nat.lib()
-            ws = self._ws.get(lib.gfc_nn_workspace_bytes(b, m, n), dev)
-            nat.check(lib.gfc_nn_match(nat.ptr(d0), nat.ptr(d1), b, m, n, d, float(conf_get(self.conf, "ratio_thresh") or 0),
-                                       float(conf_get(self.conf, "distance_thresh") or 0),
-                                       int(bool(conf_get(self.conf, "mutual_check"))), nat.ptr(m0), nat.ptr(m1),
-                                       nat.ptr(ms0), nat.ptr(ms1), nat.ptr(sim), nat.ptr(la), nat.ptr(ws), ws.numel(),
-                                       nat.stream_ptr(dev)), "gfc_nn_match")
+            ws = self._ws.get(nat.call("gfc_nn_workspace_bytes", b, m, n), dev)
+            nat.call("gfc_nn_match", d0, d1, b, m, n, d, float(conf_get(self.conf, "ratio_thresh") or 0),
+                     float(conf_get(self.conf, "distance_thresh") or 0), int(bool(conf_get(self.conf, "mutual_check"))),
+                     m0, m1, ms0, ms1, sim, la, ws, ws.numel())
         return {"matches0": m0, "matches1": m1, "matching_scores0": ms0, "matching_scores1": ms1, "similarity": sim,
                 "log_assignment": la}
 

@@ -29,7 +29,7 @@ _ws = nat.Workspace()
 def pyramid_layout(h, w, first_octave=-1, num_octaves=4):
     """Where the levels of an H x W batch live (floats, per image): see include/gfc_amd.h."""
     out = (ctypes.c_int64 * 35)()
-    nat.check(nat.lib().gfc_sift_pyramid_layout(h, w, first_octave, num_octaves, out), "gfc_sift_pyramid_layout")
+    nat.call("gfc_sift_pyramid_layout", h, w, first_octave, num_octaves, out)
     octs = [Octave(*(int(out[3 + 4 * o + i]) for i in range(4))) for o in range(int(out[0]))]
     return Layout(octs, int(out[1]), int(out[2]))
 
@@ -56,8 +56,7 @@ def pyramid(image, valid_wh=None, first_octave=-1, num_octaves=4):
     gauss = torch.empty(b, lay.gauss_floats, device=image.device)
     dog = torch.empty(b, lay.dog_floats, device=image.device)
     v = _valid(valid_wh, image.device)
-    nat.check(nat.lib().gfc_sift_pyramid(nat.ptr(image), b, h, w, nat.ptr(v), first_octave, num_octaves, nat.ptr(gauss),
-                                         nat.ptr(dog), nat.stream_ptr(image.device)), "gfc_sift_pyramid")
+    nat.call("gfc_sift_pyramid", image, b, h, w, v, first_octave, num_octaves, gauss, dog)
     return gauss, dog, lay
 
 
@@ -69,13 +68,11 @@ def detect(dog, h, w, valid_wh=None, first_octave=-1, num_octaves=4, detection_t
     raw_f = torch.zeros(b, cap, 8, device=dev)
     raw_i = torch.zeros(b, cap, 8, dtype=torch.int32, device=dev)
     counts = torch.zeros(b, 4, dtype=torch.int32, device=dev)
-    need = nat.lib().gfc_sift_detect_workspace_bytes(b, cap)
+    need = nat.call("gfc_sift_detect_workspace_bytes", b, cap)
     ws = _ws.get(need, dev)
     v = _valid(valid_wh, dev)
-    nat.check(nat.lib().gfc_sift_detect(nat.ptr(dog), b, h, w, nat.ptr(v), first_octave, num_octaves,
-                                        float(detection_threshold), float(edge_threshold), cap, nat.ptr(raw_f),
-                                        nat.ptr(raw_i), nat.ptr(counts), nat.ptr(ws), need, nat.stream_ptr(dev)),
-              "gfc_sift_detect")
+    nat.call("gfc_sift_detect", dog, b, h, w, v, first_octave, num_octaves, float(detection_threshold),
+             float(edge_threshold), cap, raw_f, raw_i, counts, ws, need)
     return raw_f, raw_i, counts
 
 
@@ -87,12 +84,11 @@ def orient(gauss, h, w, raw_f, raw_i, counts, valid_wh=None, first_octave=-1, nu
     ori_f = torch.zeros(b, ocap, 8, device=dev)
     ori_i = torch.zeros(b, ocap, 4, dtype=torch.int32, device=dev)
     ocounts = torch.zeros(b, 2, dtype=torch.int32, device=dev)
-    need = nat.lib().gfc_sift_orient_workspace_bytes(b, cap)
+    need = nat.call("gfc_sift_orient_workspace_bytes", b, cap)
     ws = _ws.get(need, dev)
     v = _valid(valid_wh, dev)
-    nat.check(nat.lib().gfc_sift_orient(nat.ptr(gauss), b, h, w, nat.ptr(v), first_octave, num_octaves, nat.ptr(raw_f),
-                                        nat.ptr(raw_i), nat.ptr(counts), cap, ocap, nat.ptr(ori_f), nat.ptr(ori_i),
-                                        nat.ptr(ocounts), nat.ptr(ws), need, nat.stream_ptr(dev)), "gfc_sift_orient")
+    nat.call("gfc_sift_orient", gauss, b, h, w, v, first_octave, num_octaves, raw_f, raw_i, counts, cap, ocap, ori_f,
+             ori_i, ocounts, ws, need)
     return ori_f, ori_i, ocounts
 
 
@@ -102,9 +98,7 @@ def describe(gauss, h, w, ori_f, ori_i, ocounts, valid_wh=None, first_octave=-1,
     b, ocap, dev = ori_f.shape[0], ori_f.shape[1], gauss.device
     desc = torch.zeros(b, ocap, 128, device=dev)
     v = _valid(valid_wh, dev)
-    nat.check(nat.lib().gfc_sift_describe(nat.ptr(gauss), b, h, w, nat.ptr(v), first_octave, num_octaves, nat.ptr(ori_f),
-                                          nat.ptr(ori_i), nat.ptr(ocounts), ocap, nat.ptr(desc), nat.stream_ptr(dev)),
-              "gfc_sift_describe")
+    nat.call("gfc_sift_describe", gauss, b, h, w, v, first_octave, num_octaves, ori_f, ori_i, ocounts, ocap, desc)
     return desc
 
 
@@ -127,7 +121,7 @@ def gray(image):
     image = image.contiguous().float()
     b, _, h, w = image.shape
     out = torch.empty(b, h, w, device=image.device)
-    nat.check(nat.lib().gfc_sift_gray(nat.ptr(image), nat.ptr(out), b, h, w, nat.stream_ptr(image.device)), "gfc_sift_gray")
+    nat.call("gfc_sift_gray", image, out, b, h, w)
     return out
 
 
@@ -145,17 +139,15 @@ def filter_list(ori_f, desc, ocounts, h, w, valid_wh=None, specular=None, nms_ra
                descriptors=torch.zeros(b, out_cap, 128, device=dev),
                index=torch.zeros(b, out_cap, dtype=torch.int32, device=dev),
                counts=torch.zeros(b, dtype=torch.int32, device=dev))
-    need = nat.lib().gfc_sift_filter_workspace_bytes(b, h, w, ocap)
+    need = nat.call("gfc_sift_filter_workspace_bytes", b, h, w, ocap)
     ws = _ws.get(need, dev)
     v = _valid(valid_wh, dev)
     if specular is not None:
         specular = specular.to(device=dev).reshape(b, h, w).ne(0).to(torch.uint8).contiguous()
-    nat.check(nat.lib().gfc_sift_filter(
-        nat.ptr(ori_f), nat.ptr(desc), nat.ptr(ocounts), b, ocap, h, w, nat.ptr(v), nat.ptr(specular),
-        -1 if nms_radius is None else int(nms_radius), int(bool(scale_weighting)), kk, int(bool(rootsift)), out_cap,
-        nat.ptr(out["keypoints"]), nat.ptr(out["scales"]), nat.ptr(out["oris"]), nat.ptr(out["keypoint_scores"]),
-        nat.ptr(out["descriptors"]), nat.ptr(out["index"]), nat.ptr(out["counts"]), nat.ptr(ws), need,
-        nat.stream_ptr(dev)), "gfc_sift_filter")
+    nat.call("gfc_sift_filter", ori_f, desc, ocounts, b, ocap, h, w, v, specular,
+             -1 if nms_radius is None else int(nms_radius), int(bool(scale_weighting)), kk, int(bool(rootsift)), out_cap,
+             out["keypoints"], out["scales"], out["oris"], out["keypoint_scores"], out["descriptors"], out["index"],
+             out["counts"], ws, need)
     return out
 
 
@@ -178,7 +170,7 @@ def extract(image, valid_wh=None, specular=None, first_octave=-1, num_octaves=4,
                counts=torch.zeros(b, dtype=torch.int32, device=dev),
                stage_counts=torch.zeros(b, 4, dtype=torch.int32, device=dev),
                ocounts=torch.zeros(b, 2, dtype=torch.int32, device=dev))
-    need = nat.lib().gfc_sift_extract_workspace_bytes(b, h, w, first_octave, num_octaves, cap, ocap)
+    need = nat.call("gfc_sift_extract_workspace_bytes", b, h, w, first_octave, num_octaves, cap, ocap)
     if need == 0:
         # the call itself says why (unsupported shape or invalid argument)
         need = 1
@@ -186,12 +178,10 @@ def extract(image, valid_wh=None, specular=None, first_octave=-1, num_octaves=4,
     v = _valid(valid_wh, dev)
     if specular is not None:
         specular = specular.to(device=dev).reshape(b, h, w).ne(0).to(torch.uint8).contiguous()
-    nat.check(nat.lib().gfc_sift_extract(
-        nat.ptr(image), b, h, w, nat.ptr(v), nat.ptr(specular), first_octave, num_octaves, float(detection_threshold),
-        float(edge_threshold), cap, ocap, -1 if nms_radius is None else int(nms_radius), int(bool(scale_weighting)), kk,
-        int(bool(rootsift)), out_cap, nat.ptr(out["keypoints"]), nat.ptr(out["scales"]), nat.ptr(out["oris"]),
-        nat.ptr(out["keypoint_scores"]), nat.ptr(out["descriptors"]), nat.ptr(out["index"]), nat.ptr(out["counts"]),
-        nat.ptr(out["stage_counts"]), nat.ptr(out["ocounts"]), nat.ptr(ws), need, nat.stream_ptr(dev)), "gfc_sift_extract")
+    nat.call("gfc_sift_extract", image, b, h, w, v, specular, first_octave, num_octaves, float(detection_threshold),
+             float(edge_threshold), cap, ocap, -1 if nms_radius is None else int(nms_radius), int(bool(scale_weighting)),
+             kk, int(bool(rootsift)), out_cap, out["keypoints"], out["scales"], out["oris"], out["keypoint_scores"],
+             out["descriptors"], out["index"], out["counts"], out["stage_counts"], out["ocounts"], ws, need)
     return out
 
 

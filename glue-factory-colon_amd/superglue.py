@@ -209,7 +209,7 @@ class SuperGlue(BaseModel):
     def _run(self, kp0, kp1, sc0, sc1, d0, d1, s0, s1, taps=False):
         """The batched core: B pairs of (m, n) key points through gfc_sg_forward.  taps: also return `desc_taps`
         [4, B*m + B*n, 256], the packed rows after the encoder, layer 0, layer 1 and the last layer."""
-        conf, lib = self.conf, nat.lib()
+        conf = self.conf
         device = kp0.device
         b, m = kp0.shape[:2]
         n = kp1.shape[1]
@@ -221,15 +221,13 @@ class SuperGlue(BaseModel):
         cost = torch.empty((b, m, n), device=device)
         la = torch.empty((b, m + 1, n + 1), device=device)
         tap = torch.zeros((4, b * (m + n), _D), device=device) if taps else None
-        need = lib.gfc_sg_workspace_bytes(b, m, n)
+        need = nat.call("gfc_sg_workspace_bytes", b, m, n)
         if need == 0:
             raise nat.NativeError(f"gfc_sg_forward cannot run a batch of {b} x ({m}, {n}) key points")
         ws = self._ws.get(need, device)
-        nat.check(lib.gfc_sg_forward(
-            ctypes.byref(p), nat.ptr(kp0), nat.ptr(kp1), nat.ptr(sc0), nat.ptr(sc1), nat.ptr(d0), nat.ptr(d1),
-            nat.ptr(s0), nat.ptr(s1), b, m, n, int(conf.num_sinkhorn_iterations), float(conf.filter_threshold),
-            nat.ptr(cost), nat.ptr(la), nat.ptr(m0), nat.ptr(m1), nat.ptr(ms0), nat.ptr(ms1), nat.ptr(tap), nat.ptr(ws),
-            ws.numel(), nat.stream_ptr(device)), "gfc_sg_forward")
+        nat.call("gfc_sg_forward", ctypes.byref(p), kp0, kp1, sc0, sc1, d0, d1, s0, s1, b, m, n,
+                 int(conf.num_sinkhorn_iterations), float(conf.filter_threshold), cost, la, m0, m1, ms0, ms1, tap, ws,
+                 ws.numel())
         out = {"sinkhorn_cost": cost, "log_assignment": la, "matches0": m0, "matches1": m1, "matching_scores0": ms0,
                "matching_scores1": ms1}
         if taps:

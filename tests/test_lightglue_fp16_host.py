@@ -97,14 +97,26 @@ def test_attention_f16_refuses_invalid_arguments():
         assert call(**kw) == INVALID, kw
 
 
+LG_ARRAYS = ["wqkv", "bqkv", "s_out_w", "s_out_b", "s_ffn0_w", "s_ffn0_b", "s_ln_g", "s_ln_b", "s_ffn3_w", "s_ffn3_b",
+             "c_qkv_w", "c_qkv_b", "c_out_w", "c_out_b", "c_ffn0_w", "c_ffn0_b", "c_ln_g", "c_ln_b", "c_ffn3_w", "c_ffn3_b"]
+LG_ARRAYS_F16 = ["wqkv16", "s_out_w16", "s_ffn0_w16", "s_ffn3_w16", "c_qkv_w16", "c_out_w16", "c_ffn0_w16", "c_ffn3_w16",
+                 "final_proj_w16"]
+LG_HEADS = ["final_proj_w", "final_proj_b", "matchability_w", "matchability_b", "token_w", "token_b"]
+
+
+def _pointer_arrays(struct):
+    """The fields of a parameter struct that are arrays of pointers, as the header declares them."""
+    return [name for name, t in struct._fields_ if issubclass(t, ctypes.Array) and t._type_ is ctypes.c_void_p]
+
+
 def _fp16_params(drop=None):
     """A params struct that asks for fp16 with every matrix present (never-dereferenced addresses), minus `drop`."""
+    assert _pointer_arrays(nat.LgParams) == LG_ARRAYS + LG_HEADS + LG_ARRAYS_F16
     p = nat.LgParams()
     p.n_layers, p.input_dim, p.posenc_dim, p.precision = 2, 256, 2, nat.GFC_LG_FP16
     p.posenc_wr = 0x1000
-    for name, _ in nat.LgParams._fields_:
-        if name in nat._LG_ARRAYS or name in nat._LG_ARRAYS_F16 or name in ("final_proj_w", "final_proj_b",
-                                                                             "matchability_w", "matchability_b"):
+    for name in _pointer_arrays(nat.LgParams):
+        if name not in ("token_w", "token_b"):
             if name in ("s_out_w", "s_out_b", "c_out_w", "c_out_b", "s_out_w16", "c_out_w16"):
                 continue  # folded
             arr = getattr(p, name)

@@ -138,7 +138,17 @@ def f(n):
     return ctypes.c_void_p(0x1000 * n)
 
 
+SG_ARRAYS = ["wqkv", "bqkv", "merge_w", "merge_b", "mlp0_w", "mlp0_b", "mlp_scale", "mlp_shift", "mlp1_w", "mlp1_b"]
+
+
+def _layer_arrays():
+    """The per-layer fields of gfc_sg_params: its arrays of GFC_SG_MAX_LAYERS pointers, as the header declares them."""
+    return [name for name, t in nat.SgParams._fields_ if issubclass(t, ctypes.Array) and t._type_ is ctypes.c_void_p
+            and t._length_ == nat.GFC_SG_MAX_LAYERS]
+
+
 def _params():
+    assert _layer_arrays() == SG_ARRAYS
     p = nat.SgParams()
     p.n_layers, p.use_scores = 2, 1
     p.cross[1] = 1
@@ -146,7 +156,7 @@ def _params():
         p.kenc_w[i] = p.kenc_b[i] = 0x1000
     for i in range(4):
         p.kenc_scale[i] = p.kenc_shift[i] = 0x1000
-    for name in nat._SG_ARRAYS:
+    for name in _layer_arrays():
         for i in range(2):
             getattr(p, name)[i] = 0x2000
     p.final_proj_w = p.final_proj_b = 0x3000

@@ -161,15 +161,28 @@ B, M, N = 2, 65, 130
 R = B * (M + N)
 
 
+# every per-layer pointer array of gfc_lg_params, in the header's order
+LG_ARRAYS = ["wqkv", "bqkv", "s_out_w", "s_out_b", "s_ffn0_w", "s_ffn0_b", "s_ln_g", "s_ln_b", "s_ffn3_w", "s_ffn3_b",
+             "c_qkv_w", "c_qkv_b", "c_out_w", "c_out_b", "c_ffn0_w", "c_ffn0_b", "c_ln_g", "c_ln_b", "c_ffn3_w", "c_ffn3_b",
+             "final_proj_w", "final_proj_b", "matchability_w", "matchability_b", "token_w", "token_b",
+             "wqkv16", "s_out_w16", "s_ffn0_w16", "s_ffn3_w16", "c_qkv_w16", "c_out_w16", "c_ffn0_w16", "c_ffn3_w16",
+             "final_proj_w16"]
+
+
+def _pointer_arrays(struct):
+    """The fields of a parameter struct that are arrays of pointers, as the header declares them."""
+    return [name for name, t in struct._fields_ if issubclass(t, ctypes.Array) and t._type_ is ctypes.c_void_p]
+
+
 def _lg_params(precision=nat.GFC_LG_FP32, input_dim=256):
     """2 layers, every matrix of either precision 'present' (folded out_proj), decision heads on every layer."""
+    assert _pointer_arrays(nat.LgParams) == LG_ARRAYS
     p = nat.LgParams()
     p.n_layers, p.input_dim, p.posenc_dim, p.precision = 2, input_dim, 2, precision
     p.posenc_wr = 0x1000
     if input_dim != 256:
         p.input_proj_w = p.input_proj_b = p.input_proj_w16 = 0x3000
-    for name in nat._LG_ARRAYS + nat._LG_ARRAYS_F16 + ["final_proj_w", "final_proj_b", "matchability_w",
-                                                       "matchability_b", "token_w", "token_b"]:
+    for name in _pointer_arrays(nat.LgParams):
         if name not in ("s_out_w", "s_out_b", "c_out_w", "c_out_b", "s_out_w16", "c_out_w16"):
             for i in range(2):
                 getattr(p, name)[i] = 0x2000
