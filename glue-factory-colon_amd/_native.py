@@ -1,4 +1,5 @@
-"""ctypes binding of libgfc_amd.so (the C ABI declared in include/gfc_amd.h).
+"""ctypes binding of libgfc_amd.so (the C ABI declared in include/gfc_amd.h and, for the validation pass,
+include/gfc_amd_validation.h).
 
 The library is the product: if it is missing or a call fails, this module raises --
 there is no PyTorch / CPU fallback for any arithmetic on the path.
@@ -15,6 +16,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # GFC_AMD_LIB: another build of the same library (same-box A/B of kernel variants: tools/ab_build.sh)
 LIB_PATH = os.environ.get("GFC_AMD_LIB") or os.path.join(_PKG, "libgfc_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd.h")
+VALIDATION_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_validation.h")
 
 
 class NativeError(RuntimeError):
@@ -26,7 +28,7 @@ _TYPE = r"(?:const\s+)?(?:unsigned\s+int|unsigned\s+char|long\s+long|\w+)\s*\**"
 _DECL = re.compile(r"""\s*(?:
       \#\s*define\s+(?P<def>GFC_\w+)[ \t]+(?P<defval>-?\d+)[ \t]*$
     | \#\s*ifdef\s+__cplusplus\s+(?:extern\s+"C"\s*\{|\})\s+\#\s*endif\b[^\n]*$
-    | \#\s*(?:ifndef|endif|include|define\s+GFC_AMD_H\b)[^\n]*$
+    | \#\s*(?:ifndef|endif|include|define\s+GFC_AMD(?:_\w+)?_H\b)[^\n]*$
     | (?:typedef\s+)?enum\s*\{(?P<enum>[^{}]*)\}\s*(?P<ename>\w*)\s*;
     | typedef\s+struct\s*\{(?P<fields>[^{}]*)\}\s*(?P<sname>\w+)\s*;
     | (?P<ret>%s)\s*\b(?P<fname>gfc_\w+)\s*\((?P<params>[^()]*)\)\s*;
@@ -84,6 +86,21 @@ def _load_header():
 
 
 FUNCTIONS, STRUCTS, ENUMS, CONSTANTS = _load_header()
+
+
+def _load_validation_header():
+    """The functions of include/gfc_amd_validation.h (the validation pass: same library, same grammar; it declares
+    functions only and takes its types from gfc_amd.h)."""
+    if not os.path.exists(VALIDATION_HEADER_PATH):
+        raise NativeError(f"{VALIDATION_HEADER_PATH} not found: the binding is derived from the C headers")
+    with open(VALIDATION_HEADER_PATH) as f:
+        funcs, structs, enums, consts = parse_header(f.read())
+    if structs or enums or consts or set(funcs) & set(FUNCTIONS):
+        raise NativeError(f"{VALIDATION_HEADER_PATH}: only new function declarations belong there")
+    return funcs
+
+
+VALIDATION_FUNCTIONS = _load_validation_header()
 globals().update(CONSTANTS)  # GFC_LG_MAX_LAYERS, GFC_LG_FP16, GFC_CAM_RADIAL, GFC_RS_AREA, ...
 STATUS = {v: k for k, v in ENUMS["gfc_status"].items()}
 
@@ -125,9 +142,15 @@ _LG_ARRAYS = _layer_arrays("gfc_lg_params", GFC_LG_MAX_LAYERS, "const float*")  
 _LG_ARRAYS_F16 = _layer_arrays("gfc_lg_params", GFC_LG_MAX_LAYERS, "const void*")  # noqa: F821
 _SG_ARRAYS = _layer_arrays("gfc_sg_params", GFC_SG_MAX_LAYERS, "const float*")  # noqa: F821
 
+def _signatures(functions):
+    return {name: (c_char_p if ret == "const char*" else _ctype(ret), [_ctype(t) for _, t in params])
+            for name, (ret, params) in functions.items()}
+
+
 # name -> (restype, argtypes); every symbol declared in include/gfc_amd.h
-SIGNATURES = {name: (c_char_p if ret == "const char*" else _ctype(ret), [_ctype(t) for _, t in params])
-              for name, (ret, params) in FUNCTIONS.items()}
+SIGNATURES = _signatures(FUNCTIONS)
+VALIDATION_SIGNATURES = _signatures(VALIDATION_FUNCTIONS)  # include/gfc_amd_validation.h
+_ALL_FUNCTIONS = {**FUNCTIONS, **VALIDATION_FUNCTIONS}
 
 _DTYPES = {"float": (torch.float32,), "int32_t": (torch.int32,), "int": (torch.int32,), "int64_t": (torch.int64,),
            "double": (torch.float64,), "uint8_t": (torch.uint8, torch.bool), "unsigned char": (torch.uint8, torch.bool),
@@ -142,7 +165,7 @@ def _call_spec(params):
             for p, t in (params[:-1] if has_stream else params)], has_stream
 
 
-_CALLS = {name: _call_spec(params) for name, (_, params) in FUNCTIONS.items()}
+_CALLS = {name: _call_spec(params) for name, (_, params) in _ALL_FUNCTIONS.items()}
 
 _lib = None
 
@@ -183,7 +206,7 @@ def call(name, *args, device=None):
     if _CALLS[name][1]:
         converted.append(torch.cuda.current_stream(dev if dev is not None else device).cuda_stream)
     result = getattr(lib(), name)(*converted)
-    if FUNCTIONS[name][0] != "int":
+    if _ALL_FUNCTIONS[name][0] != "int":
         return result
     if result != 0:
         raise NativeError(f"{name} failed: {STATUS.get(result, result)}")
@@ -198,7 +221,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python glue-factory-colon_amd/csrc/build.py` "
                 "(or __graft_entry__.build()).  There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **VALIDATION_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

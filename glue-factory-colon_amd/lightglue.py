@@ -772,7 +772,32 @@ class LightGlue(nn.Module):
         return outs
 
     def loss(self, pred, data):
-        raise NotImplementedError("training loss (lightglue.py:588-637) is out of scope")
+        """The reference's `loss` (lightglue.py:588-637) in eval mode: (losses, metrics) of a full-depth prediction and
+        the labels `gt_matches0/1` (and `gt_assignment`, when the ground truth made one) in `data`.  In eval mode the
+        reference keeps the last layer only, so its layer loop runs zero times and total = last = the NLL of the final
+        assignment; it recomputes that assignment from ref_descriptors[:, -1] with the last head, which is
+        pred["log_assignment"] here.  One launch (gfc_lg_validation_metrics) gives the loss terms, row_norm and the
+        four matcher metrics; every value is a [B] tensor."""
+        if self.training:
+            raise NotImplementedError("the training loss (per-layer terms, token confidence, backward) is out of scope")
+        conf = self.conf
+        if conf.depth_confidence > 0 or conf.width_confidence > 0:
+            raise NotImplementedError(
+                "loss of an early-stopped / pruned prediction (depth_confidence / width_confidence > 0): the reference "
+                "applies the LAST head to the stop layer's descriptors there, which this prediction does not hold")
+        if conf_get(conf.loss, "fn", "nll") != "nll":
+            raise NotImplementedError(f"loss.fn {conf.loss.fn!r}: only 'nll' is built")
+        from .losses import OUT_KEYS, as_dict, validation_metrics
+        from .metrics import KEYS
+
+        out = validation_metrics(pred["log_assignment"], data["gt_matches0"], data["gt_matches1"],
+                                 data.get("gt_assignment"), pred["matches0"], pred["matching_scores0"],
+                                 conf_get(conf.loss, "nll_balancing", 0.5))
+        d = as_dict(out, OUT_KEYS)
+        losses = {"total": d["assignment_nll"], "last": d["assignment_nll"].clone(),
+                  **{k: d[k] for k in ("assignment_nll", "nll_pos", "nll_neg", "num_matchable", "num_unmatchable")},
+                  "row_norm": d["row_norm"]}
+        return losses, {k: d[k] for k in KEYS}
 
 
 __main_model__ = LightGlue

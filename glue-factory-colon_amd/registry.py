@@ -18,6 +18,12 @@ ALIASES = {
     "lightglue_pretrained": "lightglue_pretrained",
     "matchers.nearest_neighbor_matcher": "nearest_neighbor_matcher",
     "nearest_neighbor_matcher": "nearest_neighbor_matcher",
+    "matchers.homography_matcher": "homography_matcher",
+    "homography_matcher": "homography_matcher",
+    "gluefactory.models.matchers.homography_matcher": "homography_matcher",
+    "matchers.depth_matcher": "depth_matcher",
+    "depth_matcher": "depth_matcher",
+    "gluefactory.models.matchers.depth_matcher": "depth_matcher",
     "gluefactory_nonfree.superglue": "superglue",
     "superglue": "superglue",
     "extractors.disk_kornia": "disk_kornia",

@@ -1,8 +1,8 @@
 """Two-view pipeline: extractor on both views, key suffixing, matcher, timing keys.
 
 Counterpart of gluefactory/models/two_view_pipeline.py:278-405 (`TwoViewPipeline._forward`)
-for the components that are in scope (extractor + matcher; filter / solver / ground truth /
-key-point rotation augmentation are outside the hot path and rejected).  The real
+for the components that are in scope (extractor + matcher + ground truth, with the forward-only `loss` of
+two_view_pipeline.py:407-429; filter / solver / key-point rotation augmentation are outside the hot path and rejected).  The real
 `gluefactory.models.two_view_pipeline.TwoViewPipeline` works unchanged with this package's
 modules selected by name; this look-alike exists because the reference does not travel to the
 GPU box.  Convention (two_view_pipeline.py:9-10): m0[i] = index in image 1 matched to keypoint
@@ -41,7 +41,7 @@ class TwoViewPipeline(BaseModel):
     components = ["extractor", "matcher", "filter", "solver", "ground_truth"]
 
     def _init(self, conf):
-        for comp in ("filter", "solver", "ground_truth"):
+        for comp in ("filter", "solver"):
             if conf_get(conf_get(conf, comp, {}), "name"):
                 raise NotImplementedError(f"pipeline component {comp!r} is outside the accelerated hot path")
         rot = conf_get(conf, "keypoint_rotation", {})
@@ -53,6 +53,18 @@ class TwoViewPipeline(BaseModel):
         mat = conf_get(conf, "matcher")
         if conf_get(mat, "name"):
             self.matcher = get_model(conf_get(mat, "name"))(to_plain(mat))
+        gt = conf_get(conf, "ground_truth")
+        if conf_get(gt, "name"):
+            self.ground_truth = get_model(conf_get(gt, "name"))(to_plain(gt))
+
+    def _with_gt(self, pred, data):
+        """two_view_pipeline.py:318-320: the labels of the ground-truth component as `gt_*` keys of the prediction."""
+        gt_pred = self.ground_truth({**data, **pred})
+        pred.update({f"gt_{k}": v for k, v in gt_pred.items()})
+        return pred
+
+    def _gt_in_forward(self):
+        return hasattr(self, "ground_truth") and bool(conf_get(self.conf, "run_gt_in_forward"))
 
     def is_initialized(self):
         ok = True
@@ -117,6 +129,8 @@ class TwoViewPipeline(BaseModel):
             pred0, t0, c0, mem0 = self.extract_view(data, "0")
             pred1, t1, c1, mem1 = self.extract_view(data, "1")
         pred = {**{k + "0": v for k, v in pred0.items()}, **{k + "1": v for k, v in pred1.items()}}
+        if self._gt_in_forward():
+            pred = self._with_gt(pred, data)
         t_match = mem_match = None
         if hasattr(self, "matcher"):
             out, t_match, mem_match = self._timed(device, lambda: self.matcher({**data, **pred}))
@@ -203,6 +217,8 @@ class TwoViewPipeline(BaseModel):
         for j, d in enumerate(datas):
             p0, p1 = vpreds[2 * j], vpreds[2 * j + 1]
             preds.append({**{k + "0": v for k, v in p0.items()}, **{k + "1": v for k, v in p1.items()}})
+        if self._gt_in_forward():
+            preds = [self._with_gt(p, d) for d, p in zip(datas, preds)]
         t_match = mem_match = None
         if mat is not None:
             outs, t_match, mem_match = self._timed(device, lambda: mat.forward_pairs(
@@ -218,7 +234,23 @@ class TwoViewPipeline(BaseModel):
                 for j, (d, p) in enumerate(zip(datas, preds))]
 
     def loss(self, pred, data):
-        raise NotImplementedError("training is out of scope")
+        """two_view_pipeline.py:407-429: the labels (unless `forward` made them), then every component's `loss`; a
+        component whose `loss` raises NotImplementedError is skipped; `total` is the sum of the totals."""
+        losses, metrics, total = {}, {}, 0
+        if hasattr(self, "ground_truth") and not conf_get(self.conf, "run_gt_in_forward"):
+            pred = self._with_gt(pred, data)
+        for k in self.components:
+            comp_conf = conf_get(self.conf, k, {})
+            if not conf_get(comp_conf, "name") or not conf_get(comp_conf, "apply_loss", True) or not hasattr(self, k):
+                continue
+            try:
+                losses_, metrics_ = getattr(self, k).loss(pred, {**pred, **data})
+            except NotImplementedError:
+                continue
+            losses = {**losses, **losses_}
+            metrics = {**metrics, **metrics_}
+            total = losses_["total"] + total
+        return {**losses, "total": total}, metrics
 
 
 __main_model__ = TwoViewPipeline
