@@ -1,5 +1,5 @@
 """ctypes binding of libgfc_amd.so (the C ABI declared in include/gfc_amd.h and, for the validation pass,
-include/gfc_amd_validation.h).
+include/gfc_amd_validation.h and include/gfc_amd_sparse_map.h).
 
 The library is the product: if it is missing or a call fails, this module raises --
 there is no PyTorch / CPU fallback for any arithmetic on the path.
@@ -17,6 +17,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GFC_AMD_LIB") or os.path.join(_PKG, "libgfc_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd.h")
 VALIDATION_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_validation.h")
+SPARSE_MAP_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_sparse_map.h")
 
 
 class NativeError(RuntimeError):
@@ -88,19 +89,26 @@ def _load_header():
 FUNCTIONS, STRUCTS, ENUMS, CONSTANTS = _load_header()
 
 
-def _load_validation_header():
-    """The functions of include/gfc_amd_validation.h (the validation pass: same library, same grammar; it declares
-    functions only and takes its types from gfc_amd.h)."""
-    if not os.path.exists(VALIDATION_HEADER_PATH):
-        raise NativeError(f"{VALIDATION_HEADER_PATH} not found: the binding is derived from the C headers")
-    with open(VALIDATION_HEADER_PATH) as f:
+def _load_functions_header(path, known):
+    """The functions of a header that declares functions only and takes its types from gfc_amd.h (same library, same
+    grammar); `known`: the functions declared before it."""
+    if not os.path.exists(path):
+        raise NativeError(f"{path} not found: the binding is derived from the C headers")
+    with open(path) as f:
         funcs, structs, enums, consts = parse_header(f.read())
-    if structs or enums or consts or set(funcs) & set(FUNCTIONS):
-        raise NativeError(f"{VALIDATION_HEADER_PATH}: only new function declarations belong there")
+    if structs or enums or consts or set(funcs) & set(known):
+        raise NativeError(f"{path}: only new function declarations belong there")
     return funcs
 
 
+def _load_validation_header():
+    """include/gfc_amd_validation.h: the validation pass."""
+    return _load_functions_header(VALIDATION_HEADER_PATH, FUNCTIONS)
+
+
 VALIDATION_FUNCTIONS = _load_validation_header()
+# include/gfc_amd_sparse_map.h: ground-truth labels from Endomapper sparse maps
+SPARSE_MAP_FUNCTIONS = _load_functions_header(SPARSE_MAP_HEADER_PATH, {**FUNCTIONS, **VALIDATION_FUNCTIONS})
 globals().update(CONSTANTS)  # GFC_LG_MAX_LAYERS, GFC_LG_FP16, GFC_CAM_RADIAL, GFC_RS_AREA, ...
 STATUS = {v: k for k, v in ENUMS["gfc_status"].items()}
 
@@ -150,7 +158,8 @@ def _signatures(functions):
 # name -> (restype, argtypes); every symbol declared in include/gfc_amd.h
 SIGNATURES = _signatures(FUNCTIONS)
 VALIDATION_SIGNATURES = _signatures(VALIDATION_FUNCTIONS)  # include/gfc_amd_validation.h
-_ALL_FUNCTIONS = {**FUNCTIONS, **VALIDATION_FUNCTIONS}
+SPARSE_MAP_SIGNATURES = _signatures(SPARSE_MAP_FUNCTIONS)  # include/gfc_amd_sparse_map.h
+_ALL_FUNCTIONS = {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS}
 
 _DTYPES = {"float": (torch.float32,), "int32_t": (torch.int32,), "int": (torch.int32,), "int64_t": (torch.int64,),
            "double": (torch.float64,), "uint8_t": (torch.uint8, torch.bool), "unsigned char": (torch.uint8, torch.bool),
@@ -221,7 +230,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python glue-factory-colon_amd/csrc/build.py` "
                 "(or __graft_entry__.build()).  There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **VALIDATION_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **VALIDATION_SIGNATURES, **SPARSE_MAP_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -173,8 +173,8 @@ class LightGlue(nn.Module):
                 self.load_state_dict(torch.load(str(w), map_location="cpu"), strict=False)
             elif isinstance(w, str) and w.startswith("synthetic"):
                 seed = int(w.split(":")[1]) if ":" in w else 0
-                self.load_state_dict(_weights.lightglue_state_dict(seed, input_dim=conf.input_dim, n_layers=n),
-                                     strict=False)
+                self.load_state_dict(_weights.lightglue_state_dict(seed, input_dim=conf.input_dim, n_layers=n,
+                                                                   add_scale_ori=bool(conf.add_scale_ori)), strict=False)
             else:
                 # the reference downloads `{weights}_lightglue.pth` here (lightglue.py:385-392); no network
                 raise FileNotFoundError(f"weights {w!r} not found (no download is attempted)")

@@ -24,6 +24,12 @@ ALIASES = {
     "matchers.depth_matcher": "depth_matcher",
     "depth_matcher": "depth_matcher",
     "gluefactory.models.matchers.depth_matcher": "depth_matcher",
+    "matchers.sparse_depth_matcher": "sparse_depth_matcher",
+    "sparse_depth_matcher": "sparse_depth_matcher",
+    "gluefactory.models.matchers.sparse_depth_matcher": "sparse_depth_matcher",
+    "matchers.sparse_dense_depth_matcher": "sparse_dense_depth_matcher",
+    "sparse_dense_depth_matcher": "sparse_dense_depth_matcher",
+    "gluefactory.models.matchers.sparse_dense_depth_matcher": "sparse_dense_depth_matcher",
     "gluefactory_nonfree.superglue": "superglue",
     "superglue": "superglue",
     "extractors.disk_kornia": "disk_kornia",
@@ -42,6 +48,7 @@ DATASETS = {
     "hpatches": ("hpatches", "HPatches"),
     "posed_images": ("posed_images", "PosedImages"),
     "homographies": ("homographies", "HomographyPairs"),
+    "endomapper": ("endomapper", "Endomapper"),
 }
 
 

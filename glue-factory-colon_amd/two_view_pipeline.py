@@ -16,6 +16,16 @@ from .base_model import BaseModel, conf_get, to_plain
 from .registry import get_model
 
 
+def _image_of(view):
+    """The image of a view; a view of cached features without one (Endomapper maps) gets an empty [B,1,0,0] stand-in
+    on the device of its cache, so that the timing keys keep their device and batch size (`pair_resolution` 0)."""
+    image = view.get("image")
+    if image is not None:
+        return image
+    t = next(v for v in view["cache"].values() if isinstance(v, torch.Tensor))
+    return torch.empty((t.shape[0], 1, 0, 0), dtype=torch.float32, device=t.device)
+
+
 class TwoViewPipeline(BaseModel):
     default_conf = {
         "extractor": {"name": None, "trainable": False},
@@ -99,7 +109,7 @@ class TwoViewPipeline(BaseModel):
         t_ms = core_ms = mem = None
         if hasattr(self, "extractor") and not skip:
             inp = data_i if not pred_i else {**data_i, **pred_i}
-            out, t_ms, mem = self._timed(data_i["image"].device, lambda: self.extractor(inp))
+            out, t_ms, mem = self._timed(_image_of(data_i).device, lambda: self.extractor(inp))
             core_ms = out.pop("extractor_core_time_ms", None)
             pred_i = {**pred_i, **out}
         return pred_i, t_ms, core_ms, mem
@@ -119,7 +129,7 @@ class TwoViewPipeline(BaseModel):
         return out0, out1, t_ms, c0, c1, mem
 
     def _forward(self, data):
-        image0, image1 = data["view0"]["image"], data["view1"]["image"]
+        image0, image1 = _image_of(data["view0"]), _image_of(data["view1"])
         device = image0.device
         joint = self.extract_pair(data) if conf_get(self.conf, "joint_extraction", True) else None
         if joint is not None:
