@@ -1,5 +1,5 @@
 """ctypes binding of libgfc_amd.so (the C ABI declared in include/gfc_amd.h and, for the validation pass,
-include/gfc_amd_validation.h and include/gfc_amd_sparse_map.h).
+include/gfc_amd_validation.h, include/gfc_amd_sparse_map.h and include/gfc_amd_dense_warp.h).
 
 The library is the product: if it is missing or a call fails, this module raises --
 there is no PyTorch / CPU fallback for any arithmetic on the path.
@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("GFC_AMD_LIB") or os.path.join(_PKG, "libgfc_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd.h")
 VALIDATION_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_validation.h")
 SPARSE_MAP_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_sparse_map.h")
+DENSE_WARP_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_dense_warp.h")
 
 
 class NativeError(RuntimeError):
@@ -109,6 +110,9 @@ def _load_validation_header():
 VALIDATION_FUNCTIONS = _load_validation_header()
 # include/gfc_amd_sparse_map.h: ground-truth labels from Endomapper sparse maps
 SPARSE_MAP_FUNCTIONS = _load_functions_header(SPARSE_MAP_HEADER_PATH, {**FUNCTIONS, **VALIDATION_FUNCTIONS})
+# include/gfc_amd_dense_warp.h: ground-truth labels from dense warps (RoMa)
+DENSE_WARP_FUNCTIONS = _load_functions_header(DENSE_WARP_HEADER_PATH,
+                                              {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS})
 globals().update(CONSTANTS)  # GFC_LG_MAX_LAYERS, GFC_LG_FP16, GFC_CAM_RADIAL, GFC_RS_AREA, ...
 STATUS = {v: k for k, v in ENUMS["gfc_status"].items()}
 
@@ -159,7 +163,8 @@ def _signatures(functions):
 SIGNATURES = _signatures(FUNCTIONS)
 VALIDATION_SIGNATURES = _signatures(VALIDATION_FUNCTIONS)  # include/gfc_amd_validation.h
 SPARSE_MAP_SIGNATURES = _signatures(SPARSE_MAP_FUNCTIONS)  # include/gfc_amd_sparse_map.h
-_ALL_FUNCTIONS = {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS}
+DENSE_WARP_SIGNATURES = _signatures(DENSE_WARP_FUNCTIONS)  # include/gfc_amd_dense_warp.h
+_ALL_FUNCTIONS = {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS, **DENSE_WARP_FUNCTIONS}
 
 _DTYPES = {"float": (torch.float32,), "int32_t": (torch.int32,), "int": (torch.int32,), "int64_t": (torch.int64,),
            "double": (torch.float64,), "uint8_t": (torch.uint8, torch.bool), "unsigned char": (torch.uint8, torch.bool),
@@ -230,7 +235,8 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python glue-factory-colon_amd/csrc/build.py` "
                 "(or __graft_entry__.build()).  There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **VALIDATION_SIGNATURES, **SPARSE_MAP_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **VALIDATION_SIGNATURES, **SPARSE_MAP_SIGNATURES,
+                                  **DENSE_WARP_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

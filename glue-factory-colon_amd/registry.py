@@ -30,6 +30,9 @@ ALIASES = {
     "matchers.sparse_dense_depth_matcher": "sparse_dense_depth_matcher",
     "sparse_dense_depth_matcher": "sparse_dense_depth_matcher",
     "gluefactory.models.matchers.sparse_dense_depth_matcher": "sparse_dense_depth_matcher",
+    "matchers.roma_gt_matcher": "roma_gt_matcher",
+    "roma_gt_matcher": "roma_gt_matcher",
+    "gluefactory.models.matchers.roma_gt_matcher": "roma_gt_matcher",
     "gluefactory_nonfree.superglue": "superglue",
     "superglue": "superglue",
     "extractors.disk_kornia": "disk_kornia",
