@@ -1,5 +1,6 @@
 """ctypes binding of libgfc_amd.so (the C ABI declared in include/gfc_amd.h and, for the validation pass,
-include/gfc_amd_validation.h, include/gfc_amd_sparse_map.h and include/gfc_amd_dense_warp.h).
+include/gfc_amd_validation.h, include/gfc_amd_sparse_map.h and include/gfc_amd_dense_warp.h; for the cross attention with
+the score matrix evaluated once, include/gfc_amd_cross_attention.h).
 
 The library is the product: if it is missing or a call fails, this module raises --
 there is no PyTorch / CPU fallback for any arithmetic on the path.
@@ -19,6 +20,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd.h")
 VALIDATION_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_validation.h")
 SPARSE_MAP_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_sparse_map.h")
 DENSE_WARP_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_dense_warp.h")
+CROSS_ATTENTION_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_cross_attention.h")
 
 
 class NativeError(RuntimeError):
@@ -113,6 +115,9 @@ SPARSE_MAP_FUNCTIONS = _load_functions_header(SPARSE_MAP_HEADER_PATH, {**FUNCTIO
 # include/gfc_amd_dense_warp.h: ground-truth labels from dense warps (RoMa)
 DENSE_WARP_FUNCTIONS = _load_functions_header(DENSE_WARP_HEADER_PATH,
                                               {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS})
+# include/gfc_amd_cross_attention.h: cross attention with the score matrix evaluated once
+CROSS_ATTENTION_FUNCTIONS = _load_functions_header(
+    CROSS_ATTENTION_HEADER_PATH, {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS, **DENSE_WARP_FUNCTIONS})
 globals().update(CONSTANTS)  # GFC_LG_MAX_LAYERS, GFC_LG_FP16, GFC_CAM_RADIAL, GFC_RS_AREA, ...
 STATUS = {v: k for k, v in ENUMS["gfc_status"].items()}
 
@@ -164,7 +169,9 @@ SIGNATURES = _signatures(FUNCTIONS)
 VALIDATION_SIGNATURES = _signatures(VALIDATION_FUNCTIONS)  # include/gfc_amd_validation.h
 SPARSE_MAP_SIGNATURES = _signatures(SPARSE_MAP_FUNCTIONS)  # include/gfc_amd_sparse_map.h
 DENSE_WARP_SIGNATURES = _signatures(DENSE_WARP_FUNCTIONS)  # include/gfc_amd_dense_warp.h
-_ALL_FUNCTIONS = {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS, **DENSE_WARP_FUNCTIONS}
+CROSS_ATTENTION_SIGNATURES = _signatures(CROSS_ATTENTION_FUNCTIONS)  # include/gfc_amd_cross_attention.h
+_ALL_FUNCTIONS = {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS, **DENSE_WARP_FUNCTIONS,
+                  **CROSS_ATTENTION_FUNCTIONS}
 
 _DTYPES = {"float": (torch.float32,), "int32_t": (torch.int32,), "int": (torch.int32,), "int64_t": (torch.int64,),
            "double": (torch.float64,), "uint8_t": (torch.uint8, torch.bool), "unsigned char": (torch.uint8, torch.bool),
@@ -236,7 +243,7 @@ def lib():
                 "(or __graft_entry__.build()).  There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **VALIDATION_SIGNATURES, **SPARSE_MAP_SIGNATURES,
-                                  **DENSE_WARP_SIGNATURES}.items():
+                                  **DENSE_WARP_SIGNATURES, **CROSS_ATTENTION_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "../../include/gfc_amd_cross_attention.h"
 #include "common.h"
 #include "lg_rowdot.h"
 
@@ -242,8 +243,36 @@ struct LgBatch {
   LgGroups tab;
   size_t stage_bytes;  // one layer's workspace, re-used by every group's assignment head afterwards
   size_t stage, cosb, sinb, csb, tables, total;  // workspace slots
+  int cross_chunk;       // pairs per gfc_attention_cross_stored call (lg_cross_chunk), 0: the cross block is one launch
+  size_t sim, sim_bytes;  // its score array: one chunk's, re-used by every chunk and layer (behind the tables)
   size_t x, kp;  // gfc_lg_forward only, in front: the rows x [R,256] | its separate arrays packed, kp [R,2] + so [R,2]
 };
+
+// The cross block of a batch that is one group of equal pairs evaluates sim once (gfc_attention_cross_stored: one launch
+// per direction and a [pairs, 4, N, M] score array between them) from 8 pairs with min(M, N) >= 128 on.
+//  * Pairs go through in chunks of the smallest count with which each direction's launch alone fills the chip, pairs x
+//    heads x ceil(min(M, N) / 256) >= 2 workgroups on each of 256 CUs (32 pairs at 1024 x 1024: 537 MB of scores; 16 at
+//    2048 x 2048), or all at once when the batch is smaller than that.  The CU count is a constant of the library, not
+//    a device query: the workspace sizes below must come out the same on a host without a GPU.
+//  * Why 8 pairs and not where it starts to pay (1024 x 1024: -0.55 % at 8 pairs, +1.8 % at 16, +2.2 % at 32,
+//    profiles/cross_stored_sim.md): the second direction of the stored path is one rounding per product away from the
+//    one-launch cross block, and the matcher's outputs are bit-identical across batch sizes from 8 pairs up (32 pairs
+//    against the same pairs 8 at a time, tests/test_gpu_batch32.py).  So the arithmetic changes below that range, where
+//    floats already differ in the last bits between batch sizes (key split of 1-3 pairs), and depends on the pair shape
+//    only from there on.
+//  * min(M, N) >= 128: with less than one full 128-query workgroup per (pair, head) the launches are mostly padding
+//    (not measured).  Smaller batches and smaller pairs keep the workspace sizes they have always had.
+// Returns the chunk; 0: the two directions stay in one launch.
+constexpr int GFC_LG_FILL_CUS = 256;
+static int lg_cross_chunk(int B, int M, int N) {
+  if ((M < N ? M : N) < 128) return 0;
+  const long long per_pair = 4LL * (((M < N ? M : N) + 255) / 256);
+  if (B < 8) return 0;
+  long long chunk = (2 * GFC_LG_FILL_CUS + per_pair - 1) / per_pair;
+  if (chunk > B) chunk = B;
+  if (gfc_attention_cross_stored_workspace_bytes((int)chunk, M, N, 4) == 0) return 0;
+  return (int)chunk;
+}
 
 // rows and workspace of the groups in b.tab; false for a non-positive count, or when row offsets x 768 columns would
 // leave the int arithmetic of the kernels
@@ -275,6 +304,9 @@ static bool lg_layout(LgBatch& b, bool staged) {
   b.sinb = s.take(R * 64 * 4);
   b.csb = s.take(R * 64 * 4);  // the same values packed (cos, sin) per frequency: what the QKV epilogue reads
   b.tables = s.take((size_t)b.B * (2 * 4 * 2 + 2 + 2 + 4) * 4 + 256);
+  b.cross_chunk = b.groups == 1 ? lg_cross_chunk(b.B, b.tab.g[0].m, b.tab.g[0].n) : 0;
+  b.sim_bytes = b.cross_chunk ? gfc_attention_cross_stored_workspace_bytes(b.cross_chunk, b.tab.g[0].m, b.tab.g[0].n, 4) : 0;
+  b.sim = s.take(b.sim_bytes);
   b.total = s.off;
   return true;
 }
@@ -344,9 +376,13 @@ __global__ void lg_tables_kernel(LgGroups t, int groups, int B, const float* siz
 
 extern "C" size_t gfc_lg_layer_workspace_bytes(int rows) { return rows <= 0 ? 0 : lg_layer_ws(rows).total; }
 
+// the cross block with sim evaluated once: B pairs of (M, N) in chunks of `chunk`, score array sim (lg_cross_chunk)
+struct LgCrossStored { int B, M, N, chunk; void* sim; size_t sim_bytes; };
+
 static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, const float* csb,
                          int R, const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
-                         size_t ws_bytes, void* stream, const float* x_in = nullptr, gfc_trace* tr = nullptr);
+                         size_t ws_bytes, void* stream, const float* x_in = nullptr, gfc_trace* tr = nullptr,
+                         const LgCrossStored* xst = nullptr);
 
 extern "C" int gfc_lg_layer(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, int R,
                             const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
@@ -395,10 +431,11 @@ static bool lg_f16_layer_ok(const gfc_lg_params* p, int l) {
 // csb (optional): the rotary table packed for the QKV epilogue (one float4 per four channels instead of two)
 // x_in (optional): the rows the SELF block reads (QKV operand, first half of the ffn[0] operand, residual); its result
 // and everything after it live in x.  gfc_lg_forward_packed passes the caller's descriptors for layer 0, so that they
-// are never copied into the row buffer.  tr (optional): event pairs around the two attention launches.
+// are never copied into the row buffer.  tr (optional): event pairs around the two attention launches.  xst (optional,
+// fp32 only): the cross block evaluates sim once; still one event pair around all of its launches.
 static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, const float* csb,
                          int R, const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
-                         size_t ws_bytes, void* stream, const float* x_in, gfc_trace* tr) {
+                         size_t ws_bytes, void* stream, const float* x_in, gfc_trace* tr, const LgCrossStored* xst) {
   if (!p || !x || !cosb || !sinb || !self_p || !cross_p || !ws || R <= 0 || n_problems <= 0 || maxn <= 0)
     return GFC_ERR_INVALID;
   if (l < 0 || l >= p->n_layers) return GFC_ERR_INVALID;
@@ -465,7 +502,22 @@ static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* c
                 P::w(p->s_ffn3_w[l], p->s_ffn3_w16[l]), p->s_ffn3_b[l], xs));
     // ---- cross block (lightglue.py:193-222) ----
     GFC_TRY(proj(x, false, P::w(p->c_qkv_w[l], p->c_qkv_w16[l]), p->c_qkv_b[l], nullptr, nullptr, nullptr, 0, qkv, 512));
-    GFC_TRY(attn(qkv, 512, qkv, 512, qkv + 256, 512, cross_p));
+    bool stored = false;
+    if constexpr (P::fp32) {
+      if (xst) {
+        // the first xst->B problems of cross_p are the pairs' first directions: a chunk of them is a pair table
+        stored = true;
+        const bool rec = trace_begin(tr, st);
+        int s = GFC_OK;
+        for (int b0 = 0; b0 < xst->B && s == GFC_OK; b0 += xst->chunk)
+          s = gfc_attention_cross_stored(qkv, 512, qkv + 256, 512, ctx, D, cross_p + 4 * b0,
+                                         xst->B - b0 < xst->chunk ? xst->B - b0 : xst->chunk, xst->M, xst->N, 4, 0.125f,
+                                         xst->sim, xst->sim_bytes, st);
+        trace_end(tr, st, rec);
+        GFC_TRY(s);
+      }
+    }
+    if (!stored) GFC_TRY(attn(qkv, 512, qkv, 512, qkv + 256, 512, cross_p));
     const T* a1c = ctx;
     if (p->c_out_w[l]) {
       GFC_TRY(proj(ctx, true, P::w(p->c_out_w[l], p->c_out_w16[l]), p->c_out_b[l], nullptr, nullptr, nullptr, 0, msg, D));
@@ -576,9 +628,12 @@ static int lg_forward_core(const gfc_lg_params* p, const LgBatch& bt, const floa
     GFC_TRY(lg_input_proj(p, desc, x, R, st));
     x_in = nullptr;
   }
+  // fp32, one group of equal pairs that passes the gate of lg_cross_chunk: the cross block evaluates sim once
+  const LgCrossStored xst = {B, bt.tab.g[0].m, bt.tab.g[0].n, bt.cross_chunk, base + bt.sim, bt.sim_bytes};
+  const bool stored = bt.cross_chunk > 0 && p->precision == GFC_LG_FP32 && gfc_knobs().cross_stored != 0;
   for (int l = 0; l < p->n_layers; ++l)
     GFC_TRY(lg_layer_impl(p, l, x, cosb, sinb, csb, R, self_p, cross_p, 2 * B, bt.maxn, base + bt.stage, bt.stage_bytes, st,
-                          l == 0 ? x_in : nullptr, tr));
+                          l == 0 ? x_in : nullptr, tr, stored ? &xst : nullptr));
 
   // ---- assignment (lightglue.py:279-288) + filter (lightglue.py:294-319), one batched call per group ----
   size_t o0 = 0, o1 = 0, os = 0;

@@ -23,7 +23,8 @@ SOURCES = ["runtime.hip", "conv.hip", "conv_wino.hip", "conv_wino43.hip", "gemm.
 HEADERS = ["common.h", "block_select.h", "runtime.h", "eval_common.h", "ransac_common.h", "relpose_solver.h", "lg_rowdot.h", os.path.join(PKG, "..", "include", "gfc_amd.h"),
            os.path.join(PKG, "..", "include", "gfc_amd_validation.h"),
            os.path.join(PKG, "..", "include", "gfc_amd_sparse_map.h"),
-           os.path.join(PKG, "..", "include", "gfc_amd_dense_warp.h")]
+           os.path.join(PKG, "..", "include", "gfc_amd_dense_warp.h"),
+           os.path.join(PKG, "..", "include", "gfc_amd_cross_attention.h")]
 LIB = os.path.join(PKG, "libgfc_amd.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 VERSION_UNIT = "api.hip"  # compiled with -DGFC_SOURCE_HASH="<hash>": gfc_version() reports it

@@ -6,7 +6,8 @@
 //    current HIP device, so one process may drive several GPUs.
 // The knobs are for tests and tuning: GFC_GEMM_TILE, GFC_ATTN_CFG and GFC_NMS_MODE force a variant that the automatic
 // choice also takes at some problem size, so that tests can cover it on small inputs; GFC_STEM_F43 = 0 selects the
-// F(2x2,3x3) stem, the fallback for the F(4x4,3x3) numerics.  The variants are held to the same parity tests
+// F(2x2,3x3) stem, the fallback for the F(4x4,3x3) numerics; GFC_CROSS_STORED = 0 keeps the cross block of large uniform
+// LightGlue batches in one launch (tests/test_gpu_cross_stored_sim.py runs a batch both ways).  The variants are held to the same parity tests
 // (tests/test_gpu_primitives.py::test_gemm_tile_variants_via_knob etc.).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@ struct GfcKnobs {
   int attn_cfg;      // GFC_ATTN_CFG: 0 / anything else = by problem size, 1 = 256 queries per workgroup, 2 = 128 queries
   int nms_mode;      // GFC_NMS_MODE: 0 (default) = by problem size, 1 = LDS-image kernel, 2 = streaming kernel (waves walk column bands, rings in registers)
   int stem_f43;      // GFC_STEM_F43: 1 (default) = Winograd F(4x4,3x3) stem when its filters are supplied, 0 = F(2x2,3x3) stem
+  int cross_stored;  // GFC_CROSS_STORED: 1 (default) = large uniform batches evaluate the cross block's sim once (gfc_attention_cross_stored), 0 = never (tests: the same batch both ways)
 };
 const GfcKnobs& gfc_knobs();
 

@@ -19,6 +19,7 @@ const GfcKnobs& gfc_knobs() {
     g_knobs.attn_cfg = env_int("GFC_ATTN_CFG", 0);
     g_knobs.nms_mode = env_int("GFC_NMS_MODE", 0);
     g_knobs.stem_f43 = env_int("GFC_STEM_F43", 1);
+    g_knobs.cross_stored = env_int("GFC_CROSS_STORED", 1);
   });
   return g_knobs;
 }

@@ -218,7 +218,8 @@ typedef enum { GFC_SAMPLE_OPEN = 0, GFC_SAMPLE_LEGACY = 1, GFC_SAMPLE_FIXED = 2 
  * that takes a gfc_trace brackets every launch of ITS traced kernel with hipEventRecord(start[count]) /
  * hipEventRecord(stop[count]) on the call's stream and increments count (while count < capacity):
  *   gfc_sp_dense           -> the stem kernel (conv1a + conv1b + pool, 44 % of the extractor's FLOPs),
- *   gfc_lg_forward_packed  -> the attention launches (2 per layer: self, cross), the largest share of the step.
+ *   gfc_lg_forward_packed  -> the attention launches (2 brackets per layer: self, cross; the cross bracket holds one
+ *                             launch, or every launch of gfc_attention_cross_stored), the largest share of the step.
  * Events come from gfc_event_create().  Used by bench.py for the live roofline figures; NULL in production. */
 typedef struct {
   void** start;
