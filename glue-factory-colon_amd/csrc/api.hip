@@ -5,6 +5,7 @@
 #include <climits>
 
 #include "../../include/gfc_amd_cross_attention.h"
+#include "../../include/gfc_amd_layer_scores.h"
 #include "common.h"
 #include "lg_rowdot.h"
 
@@ -527,6 +528,40 @@ static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* c
                P::w(p->c_ffn3_w[l], p->c_ffn3_w16[l]), p->c_ffn3_b[l], x);
   };
   return p->precision == GFC_LG_FP16 ? layer(LgF16{}) : layer(LgF32{});
+}
+
+// One layer of a uniform batch driven from the host, with the cross attention lg_forward_core takes for that batch
+// (include/gfc_amd_layer_scores.h).  Workspace: one layer's | the score array of one chunk of pairs (lg_cross_chunk).
+struct LgLayerPairsWs { size_t layer, sim, total, layer_bytes, sim_bytes; int chunk; };
+static bool lg_layer_pairs_ws(int B, int M, int N, LgLayerPairsWs& L) {
+  if (B <= 0 || M <= 0 || N <= 0 || (long long)B * ((long long)M + N) > INT_MAX / 768) return false;
+  const int R = B * (M + N);
+  L.chunk = lg_cross_chunk(B, M, N);
+  L.layer_bytes = lg_layer_ws(R).total;
+  L.sim_bytes = L.chunk ? gfc_attention_cross_stored_workspace_bytes(L.chunk, M, N, 4) : 0;
+  gfc_slots s;
+  L.layer = s.take(L.layer_bytes);
+  L.sim = s.take(L.sim_bytes);
+  L.total = s.off;
+  return true;
+}
+
+extern "C" size_t gfc_lg_layer_pairs_workspace_bytes(int B, int M, int N) {
+  LgLayerPairsWs L;
+  return lg_layer_pairs_ws(B, M, N, L) ? L.total : 0;
+}
+
+extern "C" int gfc_lg_layer_pairs(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, int B,
+                                  int M, int N, const int32_t* self_p, const int32_t* cross_p, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  LgLayerPairsWs L;
+  if (!p || !ws || !lg_layer_pairs_ws(B, M, N, L)) return GFC_ERR_INVALID;
+  if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
+  char* base = (char*)ws;
+  const LgCrossStored xst = {B, M, N, L.chunk, base + L.sim, L.sim_bytes};
+  const bool stored = L.chunk > 0 && p->precision == GFC_LG_FP32 && gfc_knobs().cross_stored != 0;
+  return lg_layer_impl(p, l, x, cosb, sinb, nullptr, B * (M + N), self_p, cross_p, 2 * B, M > N ? M : N, base + L.layer,
+                       L.layer_bytes, stream, nullptr, nullptr, stored ? &xst : nullptr);
 }
 
 // token confidence / matchability logits: out[row] = (sigmoid?)(x[row,:256] . w + b)   (lightglue.py:69-80,290-291)

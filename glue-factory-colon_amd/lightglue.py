@@ -165,6 +165,7 @@ class LightGlue(nn.Module):
         self.trace = None  # optional nat.KernelTrace (bench.py): per-launch events of the attention kernel
         self._graphs = {}  # (b, m, n, device, has scale/ori) -> captured launch sequence + its static buffers
         self._report_host = None  # pinned [GFC_LG_MAX_RAGGED_PAIRS, 4] int32: the adaptive step's report lands here
+        self._thresholds_host = None  # (the packed weights they were read with, confidence_thresholds as a list)
         self.are_weights_initialized = False
 
         w = conf.weights
@@ -208,7 +209,7 @@ class LightGlue(nn.Module):
         for k, v in self.__dict__.items():
             if k == "_graphs":
                 new.__dict__[k] = {}
-            elif k in ("_packed", "_report_host"):
+            elif k in ("_packed", "_report_host", "_thresholds_host"):
                 new.__dict__[k] = None
             else:
                 new.__dict__[k] = copy.deepcopy(v, memo)
@@ -372,18 +373,16 @@ class LightGlue(nn.Module):
         return self._packed
 
     # -- forward ------------------------------------------------------------------------
-    def forward(self, data: dict) -> dict:
-        self._check_ready(data)
+    def _uniform_rows(self, data):
+        """A uniform batch as the library reads it: key points [B*M + B*N, 2], descriptors [.., input_dim] and
+        (scale, orientation) [.., 2] (None without add_scale_ori) with the rows of side 0 first, and the image sizes
+        [B,2] of both sides, all float32; the weights are packed for the device.  Five Nones when a side has no key
+        points (the inputs are still checked)."""
         conf = self.conf
-        if self.training:
-            raise NotImplementedError("training (loss, checkpointing) is out of scope: inference path only")
         kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
-        nat.require_cuda(kpts0, "data['keypoints0']")
         b, m, _ = kpts0.shape
-        b, n, _ = kpts1.shape
+        n = kpts1.shape[1]
         device = kpts0.device
-        if (conf.depth_confidence > 0 or conf.width_confidence > 0) and m > 0 and n > 0:
-            return self._forward_adaptive(data)
         size0, size1 = _image_size(data, "0"), _image_size(data, "1")
         desc0 = data["descriptors0"].contiguous().float()
         desc1 = data["descriptors1"].contiguous().float()
@@ -396,16 +395,33 @@ class LightGlue(nn.Module):
                 ori = ori if ori.dim() == 3 else ori[..., None]
                 return torch.cat([sc, ori], -1).to(device=device, dtype=torch.float32).contiguous()
             so0, so1 = pack(data["scales0"], data["oris0"]), pack(data["scales1"], data["oris1"])
+        if m == 0 or n == 0:
+            return None, None, None, None, None
+        self.ensure_packed(device)
+        s0 = torch.as_tensor(size0, device=device, dtype=torch.float32).expand(b, 2).contiguous()
+        s1 = torch.as_tensor(size1, device=device, dtype=torch.float32).expand(b, 2).contiguous()
+        # side-0 rows then side-1 rows: zero-copy when both views came out of ONE extractor call (adjacent
+        # slices of one tensor), otherwise one concatenation each (tensor plumbing)
+        kp = _pack_sides(kpts0.contiguous().float(), kpts1.contiguous().float())
+        de = _pack_sides(desc0, desc1)
+        so = _pack_sides(so0, so1) if so0 is not None else None
+        return kp, de, so, s0, s1
+
+    def forward(self, data: dict) -> dict:
+        self._check_ready(data)
+        conf = self.conf
+        if self.training:
+            raise NotImplementedError("training (loss, checkpointing) is out of scope: inference path only")
+        kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
+        nat.require_cuda(kpts0, "data['keypoints0']")
+        b, m, _ = kpts0.shape
+        b, n, _ = kpts1.shape
+        device = kpts0.device
+        if (conf.depth_confidence > 0 or conf.width_confidence > 0) and m > 0 and n > 0:
+            return self._forward_adaptive(data)
+        kp, de, so, s0, s1 = self._uniform_rows(data)
         d = conf.descriptor_dim
         if m > 0 and n > 0:
-            self.ensure_packed(device)
-            s0 = torch.as_tensor(size0, device=device, dtype=torch.float32).expand(b, 2).contiguous()
-            s1 = torch.as_tensor(size1, device=device, dtype=torch.float32).expand(b, 2).contiguous()
-            # side-0 rows then side-1 rows: zero-copy when both views came out of ONE extractor call (adjacent
-            # slices of one tensor), otherwise one concatenation each (tensor plumbing)
-            kp = _pack_sides(kpts0.contiguous().float(), kpts1.contiguous().float())
-            de = _pack_sides(desc0, desc1)
-            so = _pack_sides(so0, so1) if so0 is not None else None
             use_graph = 0 < b * (m + n) <= int(conf.graph_max_rows or 0) and self.trace is None
             if use_graph:
                 key = (b, m, n, device.index, so is not None, torch.cuda.current_stream(device).cuda_stream)
@@ -798,6 +814,185 @@ class LightGlue(nn.Module):
                   **{k: d[k] for k in ("assignment_nll", "nll_pos", "nll_neg", "num_matchable", "num_unmatchable")},
                   "row_norm": d["row_norm"]}
         return losses, {k: d[k] for k in KEYS}
+
+    # -- every layer kept: the training-mode forward and loss of the reference, forward only ---------------
+    def forward_layers(self, data: dict) -> dict:
+        """The reference's forward under `model.train()` (lightglue.py:495-498,546-547): full depth, every layer's
+        descriptors kept -- `ref_descriptors0` [B,L,M,256], `ref_descriptors1` [B,L,N,256], index l the output of
+        transformer l; every other key as `forward` returns it.  LightGlue has no dropout and no batch norm, so this is
+        the eval forward with the layers kept; it does not look at `self.training`.  Early stopping and pruning are
+        refused, as the reference disables both in training mode (lightglue.py:471-472).
+        The host drives the layers one by one (`gfc_lg_layer_pairs`: `gfc_lg_layer` with the cross attention
+        gfc_lg_forward_packed takes for the batch) and ends with `gfc_lg_assign` on the last head: the launch
+        sequence of gfc_lg_forward_packed.  Layer l works in place on slot l of one stack buffer [L, B*M + B*N, 256],
+        which it enters by one device-to-device copy of slot l - 1; the returned descriptors are permuted views of it."""
+        self._check_ready(data)
+        conf = self.conf
+        if conf.depth_confidence > 0 or conf.width_confidence > 0:
+            raise NotImplementedError(
+                "forward_layers keeps every layer of the full-depth pass: depth_confidence / width_confidence > 0 "
+                "(early stopping, pruning) are disabled in the reference's training mode and refused here")
+        kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
+        nat.require_cuda(kpts0, "data['keypoints0']")
+        b, m, _ = kpts0.shape
+        n = kpts1.shape[1]
+        device = kpts0.device
+        kp, de, so, s0, s1 = self._uniform_rows(data)
+        d, nl = conf.descriptor_dim, conf.n_layers
+        if m == 0 or n == 0:  # the early return of `forward`
+            zeros = torch.zeros
+            return self._result(torch.full((b, m), -1, device=device, dtype=torch.long),
+                                torch.full((b, n), -1, device=device, dtype=torch.long),
+                                zeros((b, m), device=device), zeros((b, n), device=device),
+                                zeros((b, nl, m, d), device=device), zeros((b, nl, n, d), device=device),
+                                zeros((b, m + 1, n + 1), device=device))
+        params = self._packed[0]
+        rows = b * (m + n)
+        stack = torch.empty((nl, rows, d), device=device)
+        if conf.input_dim != d:
+            self._input_proj(params, de, stack[0], rows)
+        else:
+            stack[0].copy_(de)
+        # problem b = side 0 of pair b, b + B = side 1 (the tables of gfc_lg_forward_packed), one upload
+        r0 = torch.arange(b, dtype=torch.int32) * m
+        r1 = b * m + torch.arange(b, dtype=torch.int32) * n
+        cm, cn = torch.full_like(r0, m), torch.full_like(r1, n)
+        self_p = torch.cat([torch.stack([r0, cm, r0, cm], 1), torch.stack([r1, cn, r1, cn], 1)], 0)
+        cross_p = torch.cat([torch.stack([r0, cm, r1, cn], 1), torch.stack([r1, cn, r0, cm], 1)], 0)
+        tabs = torch.cat([self_p.reshape(-1), cross_p.reshape(-1), r0, r1, cm, cn]).to(device)
+        self_p, cross_p = tabs[:8 * b].view(2 * b, 4), tabs[8 * b:16 * b].view(2 * b, 4)
+        row0, cnt = tabs[16 * b:18 * b], tabs[18 * b:20 * b]
+        sizes = torch.cat([s0, s1], 0).contiguous()
+        cos, sin = torch.empty((rows, 64), device=device), torch.empty((rows, 64), device=device)
+        nat.call("gfc_lg_posenc", kp, so, sizes, row0, cnt, 2 * b, max(m, n), params.posenc_wr,
+                 4 if so is not None else 2, cos, sin)
+        # gfc_lg_layer_pairs: gfc_lg_layer with the cross attention `forward` takes for this batch (from 8 large pairs
+        # on it evaluates sim once), so that the last layer is `forward`'s at every batch size
+        ws = self._ws.get(max(nat.call("gfc_lg_layer_pairs_workspace_bytes", b, m, n),
+                              nat.call("gfc_lg_assign_workspace_bytes", b, m, n)), device)
+        for i in range(nl):
+            if i > 0:
+                stack[i].copy_(stack[i - 1])
+            nat.call("gfc_lg_layer_pairs", ctypes.byref(params), i, stack[i], cos, sin, b, m, n, self_p, cross_p, ws,
+                     ws.numel())
+        m0 = torch.empty((b, m), device=device, dtype=torch.long)
+        m1 = torch.empty((b, n), device=device, dtype=torch.long)
+        ms0, ms1 = torch.empty((b, m), device=device), torch.empty((b, n), device=device)
+        scores = torch.empty((b, m + 1, n + 1), device=device)
+        last = stack[nl - 1]
+        nat.call("gfc_lg_assign", ctypes.byref(params), nl - 1, last, last[b * m:], b, m, n,
+                 float(conf.filter_threshold), m0, m1, ms0, ms1, scores, ws, ws.numel())
+        return self._result(m0, m1, ms0, ms1, stack[:, :b * m].view(nl, b, m, d).permute(1, 0, 2, 3),
+                            stack[:, b * m:].view(nl, b, n, d).permute(1, 0, 2, 3), scores)
+
+    def layer_loss(self, pred, data):
+        """The reference's `loss` under `model.train()` (lightglue.py:597-630), forward only, plus a per-layer exit
+        report: (losses, report) of a `forward_layers` prediction and the labels `gt_matches0/1` (and `gt_assignment`,
+        when the ground truth made one) in `data`.  It does not look at `self.training`.
+
+        Every layer l < L - 1 goes through its own head (gfc_lg_assign into ONE re-used log-assignment buffer, so only
+        the final assignment and one layer's are alive), gfc_lg_validation_metrics on that assignment with that
+        layer's own mutual matches, the token logits (gfc_lg_rowdot without the sigmoid) and gfc_lg_layer_scores.  The
+        reference re-uses the weight matrix of the last layer for every layer (`weights=gt_weights`,
+        lightglue.py:598,609); that matrix depends on the labels only, so gfc_lg_validation_metrics on each layer with
+        the same labels is the same arithmetic.
+
+        losses, each [B]: `last`, `assignment_nll`, `nll_pos`, `nll_neg`, `num_matchable`, `num_unmatchable`,
+        `row_norm` of the final layer (what `loss` returns), `confidence` = sum_l (bce0_l + bce1_l) / 2 / (L - 1) and
+        `total` = (nll_{L-1} + sum_l w_l nll_l) / (1 + sum_l w_l) + confidence with w_l = gamma^(L-l-1) for
+        loss.gamma > 0, else l + 1, added in the reference's order.
+        report (MI355X addition), [B,L]: `layer_nll`, `layer_nll_pos`, `layer_nll_neg`, `layer_recall`,
+        `layer_precision` (the matcher metrics of layer l's own mutual matches); [B,L-1]: `layer_agree` = the share of
+        points whose arg-max (dustbin included) is that of the final layer -- the token-confidence target --,
+        `layer_token_bce`, `layer_ratio_confident` = the share of points with !(token < confidence_threshold(l)), the
+        number check_if_stop (lightglue.py:569-580) compares with depth_confidence; [B]: the four matcher metrics of the
+        final layer under the names `loss` gives them."""
+        conf = self.conf
+        nl = conf.n_layers
+        ref0, ref1 = pred["ref_descriptors0"], pred["ref_descriptors1"]
+        if ref0.dim() != 4 or ref0.shape[1] != nl or ref1.shape[1] != nl:
+            raise ValueError(f"layer_loss needs the descriptors of all {nl} layers, ref_descriptors0 is "
+                             f"{tuple(ref0.shape)}: the prediction must come from forward_layers, not forward")
+        b, _, m, d = ref0.shape
+        n = ref1.shape[2]
+        if m == 0 or n == 0:
+            raise ValueError(f"layer_loss of a pair without key points in one view ({m} x {n})")
+        if conf.depth_confidence > 0 or conf.width_confidence > 0:
+            raise NotImplementedError("layer_loss scores the full-depth pass: depth_confidence / width_confidence > 0 "
+                                      "are disabled in the reference's training mode and refused here")
+        if conf_get(conf.loss, "fn", "nll") != "nll":
+            raise NotImplementedError(f"loss.fn {conf.loss.fn!r}: only 'nll' is built")
+        nat.require_cuda(ref0, "pred['ref_descriptors0']")
+        from .losses import OUT_KEYS
+        from .metrics import KEYS
+
+        device = ref0.device
+        packed = self.ensure_packed(device)
+        params = packed[0]
+        if self._thresholds_host is None or self._thresholds_host[0] is not packed:
+            # read with the weights they belong to, once: no device-to-host read in the calls that follow
+            self._thresholds_host = (packed, self.confidence_thresholds.tolist())
+        thresholds = self._thresholds_host[1]
+        la_final = pred["log_assignment"].float().contiguous()
+        gt0 = data["gt_matches0"].to(device=device, dtype=torch.long).contiguous()
+        gt1 = data["gt_matches1"].to(device=device, dtype=torch.long).contiguous()
+        gta = data.get("gt_assignment")
+        if tuple(la_final.shape) != (b, m + 1, n + 1) or tuple(gt0.shape) != (b, m) or tuple(gt1.shape) != (b, n) or (
+                gta is not None and tuple(gta.shape) != (b, m, n)):
+            raise ValueError(f"ref_descriptors {tuple(ref0.shape)} / {tuple(ref1.shape)} do not fit log_assignment "
+                             f"{tuple(la_final.shape)}, gt_matches0 {tuple(gt0.shape)}, gt_matches1 {tuple(gt1.shape)}")
+        if gta is not None:
+            gta = gta.to(device=device).ne(0).contiguous()
+        balancing = float(conf_get(conf.loss, "nll_balancing", 0.5))
+        vm = torch.empty((nl, b, len(OUT_KEYS)), device=device)       # gfc_lg_validation_metrics of every layer
+        sc = torch.empty((max(nl - 1, 0), b, 6), device=device)        # gfc_lg_layer_scores of every layer but the last
+        nat.call("gfc_lg_validation_metrics", la_final, gt0, gt1, gta,
+                 pred["matches0"].to(device=device, dtype=torch.long).contiguous(),
+                 pred["matching_scores0"].to(device=device, dtype=torch.float32).contiguous(), b, m, n, balancing,
+                 vm[nl - 1])
+        rows = b * (m + n)
+        ws_assign = nat.call("gfc_lg_assign_workspace_bytes", b, m, n)
+        ws_scores = nat.call("gfc_lg_layer_scores_workspace_bytes", b, m, n)
+        ws = self._ws.get(max(ws_assign, ws_scores), device)
+        la = torch.empty_like(la_final)  # ONE buffer for every layer's own assignment
+        pm0 = torch.empty((b, m), device=device, dtype=torch.long)
+        pm1 = torch.empty((b, n), device=device, dtype=torch.long)
+        ps0, ps1 = torch.empty((b, m), device=device), torch.empty((b, n), device=device)
+        logits = torch.empty((rows,), device=device)
+        for i in range(nl - 1):
+            # [B*M + B*N, 256], side 0 first: slot i of the stack of forward_layers as it is, else one concatenation
+            x = _pack_sides(ref0[:, i].float().contiguous(), ref1[:, i].float().contiguous())
+            nat.call("gfc_lg_assign", ctypes.byref(params), i, x, x[b * m:], b, m, n, float(conf.filter_threshold),
+                     pm0, pm1, ps0, ps1, la, ws, ws.numel())
+            nat.call("gfc_lg_validation_metrics", la, gt0, gt1, gta, pm0, ps0, b, m, n, balancing, vm[i])
+            nat.call("gfc_lg_rowdot", x, d, rows, params.token_w[i], params.token_b[i], 0, logits)
+            nat.call("gfc_lg_layer_scores", la, la_final, logits, logits[b * m:], float(thresholds[i]), b, m, n, sc[i],
+                     None, None, ws, ws.numel())
+        col = OUT_KEYS.index
+        nll = vm[:, :, col("assignment_nll")]  # [L,B]
+        # lightglue.py:597-630 in its order of additions
+        gamma = float(conf_get(conf.loss, "gamma", 1.0))
+        total, sum_weights = nll[nl - 1], 1.0
+        confidence = torch.zeros((b,), device=device)
+        for i in range(nl - 1):
+            weight = gamma ** (nl - i - 1) if gamma > 0.0 else i + 1
+            sum_weights += weight
+            total = total + nll[i] * weight
+            confidence = confidence + (sc[i, :, 2] + sc[i, :, 3]) / 2.0 / (nl - 1)
+        total = total / sum_weights + confidence
+        final = vm[nl - 1]
+        losses = {"total": total, "last": final[:, col("assignment_nll")].clone(),
+                  **{k: final[:, col(k)] for k in ("assignment_nll", "nll_pos", "nll_neg", "num_matchable",
+                                                   "num_unmatchable")},
+                  "row_norm": final[:, col("row_norm")], "confidence": confidence}
+        report = {"layer_nll": nll.t(), "layer_nll_pos": vm[:, :, col("nll_pos")].t(),
+                  "layer_nll_neg": vm[:, :, col("nll_neg")].t(), "layer_recall": vm[:, :, col("match_recall")].t(),
+                  "layer_precision": vm[:, :, col("match_precision")].t(),
+                  "layer_agree": ((sc[:, :, 0] + sc[:, :, 1]) / (m + n)).t(),
+                  "layer_token_bce": ((sc[:, :, 2] + sc[:, :, 3]) / 2.0).t(),
+                  "layer_ratio_confident": ((sc[:, :, 4] + sc[:, :, 5]) / (m + n)).t(),
+                  **{k: final[:, col(k)] for k in KEYS}}
+        return losses, report
 
 
 __main_model__ = LightGlue

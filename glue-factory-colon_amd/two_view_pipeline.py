@@ -128,7 +128,13 @@ class TwoViewPipeline(BaseModel):
         c0, c1 = out0.pop("extractor_core_time_ms", None), out1.pop("extractor_core_time_ms", None)
         return out0, out1, t_ms, c0, c1, mem
 
-    def _forward(self, data):
+    def forward_layers(self, data):
+        """`forward` with the matcher's `forward_layers`: every layer's descriptors kept, the input of `layer_loss`."""
+        for key in self.required_data_keys:
+            assert key in data, f"Missing key {key} in data"
+        return self._forward(data, match=self.matcher.forward_layers)
+
+    def _forward(self, data, match=None):
         image0, image1 = _image_of(data["view0"]), _image_of(data["view1"])
         device = image0.device
         joint = self.extract_pair(data) if conf_get(self.conf, "joint_extraction", True) else None
@@ -143,7 +149,7 @@ class TwoViewPipeline(BaseModel):
             pred = self._with_gt(pred, data)
         t_match = mem_match = None
         if hasattr(self, "matcher"):
-            out, t_match, mem_match = self._timed(device, lambda: self.matcher({**data, **pred}))
+            out, t_match, mem_match = self._timed(device, lambda: (match or self.matcher)({**data, **pred}))
             pred = {**pred, **out}
         return self._with_timing_keys(pred, image0, image1, (t0, t1), (c0, c1), (mem0, mem1), t_match, mem_match)
 
@@ -188,7 +194,15 @@ class TwoViewPipeline(BaseModel):
         the same image and are extracted once (an HPatches sequence reads its reference image as view 0 of all five of its
         pairs, datasets/hpatches.py:98-99: 32 consecutive pairs hold ~39 distinct images, not 64).  Every pair's
         prediction is what it is without the keys -- an image's features do not depend on what else is in its batch."""
-        ext, mat = getattr(self, "extractor", None), getattr(self, "matcher", None)
+        return self._pairs(datas, view_keys, getattr(self, "matcher", None))
+
+    def extract_pairs(self, datas, view_keys=None):
+        """`forward_pairs` up to the matcher: the extraction (and the labels of `run_gt_in_forward`) of every pair, for a
+        caller that runs the matcher itself, as the per-layer report of the validation pass does with `forward_layers`."""
+        return self._pairs(datas, view_keys, None, extract_only=True)
+
+    def _pairs(self, datas, view_keys, mat, extract_only=False):
+        ext = getattr(self, "extractor", None)
         ok = len(datas) > 1 and ext is not None and (mat is None or hasattr(mat, "forward_pairs"))
         for d in datas:
             for key in self.required_data_keys:
@@ -196,7 +210,7 @@ class TwoViewPipeline(BaseModel):
             ok = ok and not d["view0"].get("cache") and not d["view1"].get("cache") \
                 and d["view0"]["image"].shape[0] == 1 and d["view1"]["image"].shape[0] == 1
         if not ok:
-            return [self(d) for d in datas]
+            return [self._forward(d, match=lambda _: {}) if extract_only else self(d) for d in datas]
         n = len(datas)
         device = datas[0]["view0"]["image"].device
         views = [d[f"view{i}"] for d in datas for i in ("0", "1")]
@@ -261,6 +275,13 @@ class TwoViewPipeline(BaseModel):
             metrics = {**metrics, **metrics_}
             total = losses_["total"] + total
         return {**losses, "total": total}, metrics
+
+    def layer_loss(self, pred, data):
+        """The matcher's `layer_loss` (every layer scored: the reference's training-mode loss values and the per-layer
+        exit report) on a `forward_layers` prediction, with the labels built as `loss` builds them."""
+        if hasattr(self, "ground_truth") and not conf_get(self.conf, "run_gt_in_forward"):
+            pred = self._with_gt(pred, data)
+        return self.matcher.layer_loss(pred, {**pred, **data})
 
 
 __main_model__ = TwoViewPipeline

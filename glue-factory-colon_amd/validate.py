@@ -18,6 +18,11 @@ matchers.sparse_dense_depth_matcher; the label inputs that come out of the cache
 The labels run without the dense matrices, so the sum of `extra_positives` -- positives of the reference's dense
 `assignment` that `matches0` cannot name -- rides in the group's one read and is reported as `gt_extra_positives`.
 `--eval_overlap_bins "0:0.2,0.2:0.4"`: the reference's overlap bins (train.py:123-143, 280-299), returned under "bins".
+`--layer_report`: every group goes through the matcher's `forward_layers` and `layer_loss` instead of its forward and
+`loss` (still one read per group): the summary gains `loss/confidence`, `loss/total_deep` (the reference's training-mode
+total) and a per-layer table -- nll, recall and precision of the layer's own matches, agreement with the final layer,
+token BCE and the share of points confident at the layer (what `depth_confidence` is compared with) -- and the TSV gains
+those columns after the existing ones.  Without the flag nothing changes.
 """
 import argparse
 import math
@@ -38,6 +43,10 @@ DEFAULT_MODEL_CONF = {
     "profile_calls": False,
 }
 TSV_HEADER = "step\tindex\tname\toverlap\tprecision\trecall\taccuracy\tap\n"
+# --layer_report: per layer (all L) and per layer but the last (the token heads), in the TSV and in the summary table
+LAYER_KEYS = ("nll", "recall", "precision")
+TOKEN_KEYS = ("agree", "token_bce", "ratio_confident")
+MATCHER_INPUT_KEYS = ("keypoints0", "keypoints1", "descriptors0", "descriptors1", "scales0", "scales1", "oris0", "oris1")
 GROUP_PRED_KEYS = ("keypoints0", "keypoints1", "log_assignment", "matches0", "matching_scores0")
 # what a view's cache hands to the ground truth (suffixed 0 / 1 in the prediction): stacked with the group when present
 GROUP_LABEL_KEYS = ("sparse_depth", "valid_depth_mask", "valid_3D_mask", "point3D_ids", "depth_keypoints",
@@ -107,22 +116,35 @@ def _overlap(item):
 
 
 class ValidationPipeline:
-    def __init__(self, model_conf=None, pair_batch=32, device="cuda", eval_overlap_bins=None):
+    def __init__(self, model_conf=None, pair_batch=32, device="cuda", eval_overlap_bins=None, layer_report=False):
         self.bins = overlap_bins(eval_overlap_bins)
+        self.layer_report = bool(layer_report)
         self.model = TwoViewPipeline(merge(DEFAULT_MODEL_CONF, dict(model_conf or {}))).eval().to(device)
         if not hasattr(self.model, "ground_truth"):
             raise ValueError("the validation pass needs a ground_truth component")
         self.pair_batch = max(1, int(pair_batch))
         self.device = torch.device(device)
         self.reads = 0  # device-to-host reads so far: one per group
+        # --layer_report: (key of a pair's row, column name) behind the existing TSV columns; none without the flag
+        self._extra = []
+        if self.layer_report:
+            nl = int(self.model.matcher.conf.n_layers)
+            self._extra = [("loss/confidence", "confidence"), ("loss/total_deep", "total_deep")] + [
+                (f"layer/{i}/{k}", f"{k}_{i}") for i in range(nl) for k in LAYER_KEYS] + [
+                (f"layer/{i}/{k}", f"{k}_{i}") for i in range(nl - 1) for k in TOKEN_KEYS]
 
     def _group_loss(self, datas, preds):
         """`model.loss` of pairs with equal (M, N), stacked: ({key: [G] values}, keys) after ONE device-to-host read."""
         label_keys = tuple(k + s for k in GROUP_LABEL_KEYS for s in "01" if k + s in preds[0])
-        pred = {k: torch.cat([p[k] for p in preds], 0) for k in GROUP_PRED_KEYS + label_keys}
+        # (with --layer_report the pairs come without the matcher's keys: `_layer_numbers` runs it on the group)
+        pred = {k: torch.cat([p[k] for p in preds], 0) for k in GROUP_PRED_KEYS + label_keys
+                if not self.layer_report or k in preds[0]}
         data = self._group_data(datas)
-        losses, metrics = self.model.loss(pred, data)
-        numbers = {**metrics, **{"loss/" + k: v for k, v in losses.items()}}
+        if self.layer_report:
+            numbers = self._layer_numbers(datas, preds, pred, data)
+        else:
+            losses, metrics = self.model.loss(pred, data)
+            numbers = {**metrics, **{"loss/" + k: v for k, v in losses.items()}}
         keys = list(numbers)
         rows = [numbers[k].float() for k in keys]
         extra = pred.get("gt_extra_positives")  # the sparse-map matchers without dense outputs
@@ -133,6 +155,29 @@ class ValidationPipeline:
         if extra is not None:
             self.extra_positives = (self.extra_positives or 0) + int(host[-1].sum())
         return {k: host[i].tolist() for i, k in enumerate(keys)}
+
+    def _layer_numbers(self, datas, preds, pred, data):
+        """The numbers of a group with --layer_report: the matcher's `forward_layers` on the stacked key points and
+        descriptors, then `layer_loss`.  `loss/total` keeps its meaning (the final layer's NLL, as without the flag); the
+        training-mode total is `loss/total_deep`; the report's [G,L] entries become `layer/<l>/<key>` vectors."""
+        from .metrics import KEYS
+
+        stacked = {k: torch.cat([p[k] for p in preds], 0) for k in MATCHER_INPUT_KEYS if k in preds[0]}
+        for v in ("view0", "view1"):
+            sizes = [d.get(v, {}).get("image_size") for d in datas]
+            if all(s is not None for s in sizes):
+                stacked[v] = {"image_size": torch.cat([torch.as_tensor(s, dtype=torch.float32).reshape(1, 2)
+                                                       for s in sizes], 0).to(self.device)}
+        pred.update(self.model.matcher.forward_layers(stacked))
+        losses, report = self.model.layer_loss(pred, data)
+        numbers = {k: report[k] for k in KEYS}
+        numbers.update({"loss/" + k: v for k, v in losses.items() if k not in ("total", "confidence")})
+        numbers.update({"loss/total": losses["last"], "loss/confidence": losses["confidence"],
+                        "loss/total_deep": losses["total"]})
+        for k in LAYER_KEYS + TOKEN_KEYS:
+            table = report["layer_" + k]
+            numbers.update({f"layer/{i}/{k}": table[:, i] for i in range(table.shape[1])})
+        return numbers
 
     def _group_data(self, datas):
         """The labels' inputs of a group, stacked: `H_0to1` [G,3,3], or cameras, depth maps and `T_0to1` of G pairs."""
@@ -170,9 +215,16 @@ class ValidationPipeline:
         if log_metrics is not None:
             path = Path(log_metrics)
             header = not path.exists() or path.stat().st_size == 0
+            mine = TSV_HEADER.rstrip("\n") + "".join("\t" + name for _, name in self._extra) + "\n"
+            if not header and self.layer_report:
+                with path.open(encoding="ascii") as f:
+                    found = f.readline()
+                if found != mine:  # (without the flag a file is appended to as it always was)
+                    raise ValueError(f"{path} was written with other columns ({len(found.split(chr(9)))}, this run "
+                                     f"writes {len(mine.split(chr(9)))}): --layer_report needs a log file of its own")
             log_file = path.open("a", encoding="ascii")
             if header:
-                log_file.write(TSV_HEADER)
+                log_file.write(mine)
         try:
             with torch.no_grad():
                 chunk = []
@@ -196,7 +248,10 @@ class ValidationPipeline:
 
     def _run_chunk(self, chunk, first, results, log_file, step, view_key):
         keys = None if view_key is None else [(view_key(d, 0), view_key(d, 1)) for d in chunk]
-        preds = self.model.forward_pairs(chunk, view_keys=keys)
+        if self.layer_report:  # the matcher runs per group, with every layer kept
+            preds = self.model.extract_pairs(chunk, view_keys=keys)
+        else:
+            preds = self.model.forward_pairs(chunk, view_keys=keys)
         groups = {}
         for j, p in enumerate(preds):
             groups.setdefault(self._group_key(chunk[j], p), []).append(j)
@@ -215,8 +270,10 @@ class ValidationPipeline:
                 name = item.get("name", item.get("names", f"{first + j}_0"))
                 name = name[0] if isinstance(name, (list, tuple)) else name
                 overlap = _overlap(item)
+                extra = "".join(f"\t{row[k]:.6f}" for k, _ in self._extra)
                 log_file.write(f"{step}\t{first + j}_0\t{name}\t{overlap:.2f}\t{row['match_precision']:.6f}\t"
-                               f"{row['match_recall']:.6f}\t{row['accuracy']:.6f}\t{row['average_precision']:.6f}\n")
+                               f"{row['match_recall']:.6f}\t{row['accuracy']:.6f}\t{row['average_precision']:.6f}"
+                               f"{extra}\n")
         return len(chunk)
 
 
@@ -237,9 +294,30 @@ def _endomapper_split(data_dir, split):
     return sorted({f.stem.rsplit("_map", 1)[0] for f in (data_dir / "processed_npz").glob("*_map*.npz")})
 
 
+def _layer_table(res):
+    """The per-layer table of --layer_report from the `layer/<l>/<key>` means (nothing without them)."""
+    layers = sorted({int(k.split("/")[1]) for k in res if k.startswith("layer/")})
+    if not layers:
+        return
+    print("layer " + " ".join(["index"] + list(LAYER_KEYS + TOKEN_KEYS)))
+    for i in layers:
+        cells = [f"{res[f'layer/{i}/{k}']:.6f}" if f"layer/{i}/{k}" in res else "-" for k in LAYER_KEYS + TOKEN_KEYS]
+        print(f"layer {i} " + " ".join(cells))
+
+
+def _print(res):
+    for k in sorted(res):
+        if not k.startswith("layer/"):
+            print(f"{k}: {res[k]:.6f}" if isinstance(res[k], float) else f"{k}: {res[k]}")
+    _layer_table(res)
+    return res
+
+
 def _report(res):
     extra = res.get("gt_extra_positives")
     for k in sorted(res):
+        if k.startswith("layer/"):
+            continue
         if k == "bins":
             for name, bucket in res[k].items():
                 print(f"{name}: " + ", ".join(f"{q} {v:.6f}" for q, v in sorted(bucket.items())))
@@ -248,6 +326,7 @@ def _report(res):
     if extra:
         print(f"loss/* saw {extra} fewer positives than the reference's dense assignment (duplicate ids or a distance "
               "positive beside a seed)")
+    _layer_table(res)
     return res
 
 
@@ -271,6 +350,9 @@ def main(argv=None):
     ap.add_argument("--th_negative", type=float, default=10.0, help="endomapper: th_negative")
     ap.add_argument("--max_num_features", type=int, default=2048, help="endomapper: key points per view")
     ap.add_argument("--eval_overlap_bins", default=None, help='overlap bins "low:high,low:high" (reported under bins)')
+    ap.add_argument("--layer_report", action="store_true",
+                    help="score every LightGlue layer (forward_layers + layer_loss): loss/confidence, loss/total_deep, "
+                         "a per-layer table and the same columns in the TSV")
     args = ap.parse_args(argv)
     torch.set_num_threads(max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 16)))
     from .registry import get_dataset
@@ -284,7 +366,8 @@ def main(argv=None):
                                             data_dir.parent, split=args.split)
         pipe = ValidationPipeline(endomapper_model_conf(args.ground_truth, args.th_positive, args.th_negative, args.th_epi,
                                                         args.matcher_weights),
-                                  pair_batch=args.pair_batch, eval_overlap_bins=args.eval_overlap_bins)
+                                  pair_batch=args.pair_batch, eval_overlap_bins=args.eval_overlap_bins,
+                                  layer_report=args.layer_report)
         res = pipe.run(dataset.feeder("cuda", num_workers=args.num_workers, batch=args.pair_batch),
                        log_metrics=args.log_metrics, view_key=dataset.view_key)
         return _report(res)
@@ -296,20 +379,16 @@ def main(argv=None):
             raise NotImplementedError(f"{args.benchmark}: not a posed_images directory")
         dataset = get_dataset("posed_images")(conf, args.data_dir)
         pipe = ValidationPipeline({**model_conf, "ground_truth": {**DEPTH_GROUND_TRUTH, "th_epi": args.th_epi}},
-                                  pair_batch=args.pair_batch)
+                                  pair_batch=args.pair_batch, layer_report=args.layer_report)
         res = pipe.run(dataset.feeder("cuda", num_workers=args.num_workers), log_metrics=args.log_metrics)
-        for k in sorted(res):
-            print(f"{k}: {res[k]:.6f}" if isinstance(res[k], float) else f"{k}: {res[k]}")
-        return res
+        return _print(res)
     data_dir = Path(args.data_dir).resolve()
     dataset = get_dataset("homographies")({"data_dir": data_dir.name, "photometric": {"name": "identity"},
                                            "reseed": True}, data_dir.parent, split=args.split)
-    pipe = ValidationPipeline(model_conf, pair_batch=args.pair_batch)
+    pipe = ValidationPipeline(model_conf, pair_batch=args.pair_batch, layer_report=args.layer_report)
     res = pipe.run(dataset.feeder(batch=args.pair_batch, num_workers=args.num_workers), log_metrics=args.log_metrics,
                    view_key=dataset.view_key)
-    for k in sorted(res):
-        print(f"{k}: {res[k]:.6f}" if isinstance(res[k], float) else f"{k}: {res[k]}")
-    return res
+    return _print(res)
 
 
 if __name__ == "__main__":
