@@ -338,14 +338,22 @@ class LightGlue(nn.Module):
             p.c_ln_g[i], p.c_ln_b[i] = dev(ca.ffn[1].weight), dev(ca.ffn[1].bias)
             p.c_ffn3_w[i], p.c_ffn3_w16[i] = dev2(ca.ffn[3].weight)
             p.c_ffn3_b[i] = dev(ca.ffn[3].bias)
-        for i, head in enumerate(self.log_assignment):
-            p.final_proj_w[i], p.final_proj_w16[i] = dev2(head.final_proj.weight)
-            p.final_proj_b[i] = dev(head.final_proj.bias)
-            p.matchability_w[i] = dev(head.matchability.weight.reshape(-1))
-            p.matchability_b[i] = dev(head.matchability.bias)
+        heads = []  # (parameter, its fp32 device copy, the fp16 copy of that or None): what heads_updated refreshes
+
+        def head(param, flat=False, with_half=False):
+            t = param.reshape(-1) if flat else param
+            ptr, ptr16 = dev2(t) if with_half else (dev(t), None)
+            heads.append((param, keep[-2] if ptr16 is not None else keep[-1], keep[-1] if ptr16 is not None else None))
+            return ptr, ptr16
+
+        for i, la in enumerate(self.log_assignment):
+            p.final_proj_w[i], p.final_proj_w16[i] = head(la.final_proj.weight, with_half=True)
+            p.final_proj_b[i] = head(la.final_proj.bias)[0]
+            p.matchability_w[i] = head(la.matchability.weight, flat=True)[0]
+            p.matchability_b[i] = head(la.matchability.bias)[0]
         for i, tc in enumerate(self.token_confidence):
-            p.token_w[i], p.token_b[i] = dev(tc.token[0].weight.reshape(-1)), dev(tc.token[0].bias)
-        return p, keep, device
+            p.token_w[i], p.token_b[i] = head(tc.token[0].weight, flat=True)[0], head(tc.token[0].bias)[0]
+        return p, keep, device, heads
 
     def _check_ready(self, data=None):
         if data is not None:
@@ -993,6 +1001,133 @@ class LightGlue(nn.Module):
                   "layer_ratio_confident": ((sc[:, :, 4] + sc[:, :, 5]) / (m + n)).t(),
                   **{k: final[:, col(k)] for k in KEYS}}
         return losses, report
+
+    # -- gradients of the training loss with respect to the heads and exit tokens (the trunk frozen) --------
+    def layer_loss_backward(self, pred, data, grad_total=None, descriptor_grads=False, accumulate=True):
+        """The gradients of `layer_loss`'s `total` with respect to the assignment heads and the exit tokens, what
+        `torch.mean(losses["total"]).backward()` (gluefactory/train.py:1114) leaves in their `.grad` in the reference:
+        the parameters of log_assignment[l] enter the loss through head l only (lightglue.py:589-616) and the token
+        reads detached descriptors (lightglue.py:83-85).  The trunk is not followed; `row_norm` and `last` carry no
+        gradient.
+
+        pred: a `forward_layers` prediction; data: the labels, as `layer_loss` takes them; grad_total [B]: the weight of
+        each pair's `total` in the differentiated scalar (default 1 / B each: the mean).  Returns a dict keyed by the
+        reference's state-dict names: `log_assignment.{l}.final_proj.weight` [256,256] / `.bias` [256],
+        `log_assignment.{l}.matchability.weight` [1,256] / `.bias` [1], `token_confidence.{l}.token.0.weight` [1,256] /
+        `.bias` [1].  With `accumulate` the same tensors are added into `.grad` of the module's parameters (created when
+        absent, as Tensor.backward does), so a torch optimizer works unchanged.  With `descriptor_grads` the dict also
+        holds `grad_ref_descriptors0` [B,L,M,256] and `grad_ref_descriptors1` [B,L,N,256], permuted views of one
+        [L, B*M + B*N, 256] buffer (the layout of forward_layers' stack): the DIRECT gradient at every layer's
+        descriptors, where a trunk backward would start.  Without the flag that buffer is never allocated.
+
+        One layer is alive at a time, with one re-used workspace: gfc_lg_head_backward on the layer's rows; for l < L - 1
+        the layer's own assignment (gfc_lg_assign), its token logits, the targets correct0/1 from gfc_lg_layer_scores
+        and gfc_lg_token_backward.  Nothing is read back to the host.  Gradients are built for the fp32 matcher."""
+        conf = self.conf
+        nl = conf.n_layers
+        ref0, ref1 = pred["ref_descriptors0"], pred["ref_descriptors1"]
+        if ref0.dim() != 4 or ref0.shape[1] != nl or ref1.shape[1] != nl:
+            raise ValueError(f"layer_loss_backward needs the descriptors of all {nl} layers, ref_descriptors0 is "
+                             f"{tuple(ref0.shape)}: the prediction must come from forward_layers, not forward")
+        b, _, m, d = ref0.shape
+        n = ref1.shape[2]
+        if m == 0 or n == 0:
+            raise ValueError(f"layer_loss_backward of a pair without key points in one view ({m} x {n})")
+        if conf.depth_confidence > 0 or conf.width_confidence > 0:
+            raise NotImplementedError("layer_loss_backward differentiates the full-depth pass: depth_confidence / "
+                                      "width_confidence > 0 are disabled in the reference's training mode and refused "
+                                      "here")
+        if conf_get(conf.loss, "fn", "nll") != "nll":
+            raise NotImplementedError(f"loss.fn {conf.loss.fn!r}: only 'nll' is built")
+        if conf.matmul_precision != "fp32":
+            raise NotImplementedError("matmul_precision 'fp16': gradients are built for the fp32 matcher")
+        nat.require_cuda(ref0, "pred['ref_descriptors0']")
+        device = ref0.device
+        params = self.ensure_packed(device)[0]
+        la_final = pred["log_assignment"].float().contiguous()
+        gt0 = data["gt_matches0"].to(device=device, dtype=torch.long).contiguous()
+        gt1 = data["gt_matches1"].to(device=device, dtype=torch.long).contiguous()
+        gta = data.get("gt_assignment")
+        if tuple(la_final.shape) != (b, m + 1, n + 1) or tuple(gt0.shape) != (b, m) or tuple(gt1.shape) != (b, n) or (
+                gta is not None and tuple(gta.shape) != (b, m, n)):
+            raise ValueError(f"ref_descriptors {tuple(ref0.shape)} / {tuple(ref1.shape)} do not fit log_assignment "
+                             f"{tuple(la_final.shape)}, gt_matches0 {tuple(gt0.shape)}, gt_matches1 {tuple(gt1.shape)}")
+        if gta is not None:
+            gta = gta.to(device=device).ne(0).contiguous()
+        if grad_total is None:
+            gtot = torch.full((b,), 1.0 / b, device=device)
+        else:
+            gtot = grad_total.to(device=device, dtype=torch.float32).contiguous()
+            if tuple(gtot.shape) != (b,):
+                raise ValueError(f"grad_total must be [{b}], got {tuple(gtot.shape)}")
+        balancing = float(conf_get(conf.loss, "nll_balancing", 0.5))
+        gamma = float(conf_get(conf.loss, "gamma", 1.0))
+        # lightglue.py:597,611-626: the last layer has weight 1; every nll is divided by the sum of the weights
+        weights = [gamma ** (nl - i - 1) if gamma > 0.0 else float(i + 1) for i in range(nl - 1)] + [1.0]
+        g = (torch.tensor(weights, dtype=torch.float64) / sum(weights)).float().to(device)[:, None] * gtot[None]  # [L,B]
+        rows = b * (m + n)
+        dwf, dbf = torch.empty((nl, d, d), device=device), torch.empty((nl, d), device=device)
+        dwm, dbm = torch.empty((nl, 1, d), device=device), torch.empty((nl, 1), device=device)
+        dtw, dtb = torch.empty((max(nl - 1, 0), 1, d), device=device), torch.empty((max(nl - 1, 0), 1), device=device)
+        dx = torch.empty((nl, rows, d), device=device) if descriptor_grads else None
+        ws = self._ws.get(max(nat.call("gfc_lg_head_backward_workspace_bytes", b, m, n),
+                              nat.call("gfc_lg_token_backward_workspace_bytes", b, m, n),
+                              nat.call("gfc_lg_assign_workspace_bytes", b, m, n),
+                              nat.call("gfc_lg_layer_scores_workspace_bytes", b, m, n)), device)
+        la = torch.empty_like(la_final)  # ONE buffer for every layer's own assignment
+        pm0 = torch.empty((b, m), device=device, dtype=torch.long)
+        pm1 = torch.empty((b, n), device=device, dtype=torch.long)
+        ps0, ps1 = torch.empty((b, m), device=device), torch.empty((b, n), device=device)
+        logits = torch.empty((rows,), device=device)
+        correct = torch.empty((rows,), device=device, dtype=torch.uint8)
+        sc = torch.empty((b, 6), device=device)
+        for i in range(nl):
+            x = _pack_sides(ref0[:, i].float().contiguous(), ref1[:, i].float().contiguous())
+            nat.call("gfc_lg_head_backward", ctypes.byref(params), i, x, x[b * m:], gt0, gt1, gta, g[i], balancing, b, m,
+                     n, dwf[i], dbf[i], dwm[i], dbm[i], None if dx is None else dx[i], ws, ws.numel())
+            if i == nl - 1:
+                break
+            nat.call("gfc_lg_assign", ctypes.byref(params), i, x, x[b * m:], b, m, n, float(conf.filter_threshold),
+                     pm0, pm1, ps0, ps1, la, ws, ws.numel())
+            nat.call("gfc_lg_rowdot", x, d, rows, params.token_w[i], params.token_b[i], 0, logits)
+            nat.call("gfc_lg_layer_scores", la, la_final, logits, logits[b * m:], 0.5, b, m, n, sc, correct,
+                     correct[b * m:], ws, ws.numel())
+            nat.call("gfc_lg_token_backward", x, x[b * m:], logits, logits[b * m:], correct, correct[b * m:], gtot, nl,
+                     b, m, n, dtw[i], dtb[i], ws, ws.numel())
+        grads = {}
+        for i in range(nl):
+            grads[f"log_assignment.{i}.final_proj.weight"], grads[f"log_assignment.{i}.final_proj.bias"] = dwf[i], dbf[i]
+            grads[f"log_assignment.{i}.matchability.weight"] = dwm[i]
+            grads[f"log_assignment.{i}.matchability.bias"] = dbm[i]
+        for i in range(nl - 1):
+            grads[f"token_confidence.{i}.token.0.weight"], grads[f"token_confidence.{i}.token.0.bias"] = dtw[i], dtb[i]
+        if accumulate:
+            for name, grad in grads.items():
+                param = self.get_parameter(name)
+                grad = grad.to(device=param.device, dtype=param.dtype)
+                if param.grad is None:
+                    param.grad = grad.clone()
+                else:
+                    param.grad += grad
+        if dx is not None:
+            grads["grad_ref_descriptors0"] = dx[:, :b * m].view(nl, b, m, d).permute(1, 0, 2, 3)
+            grads["grad_ref_descriptors1"] = dx[:, b * m:].view(nl, b, n, d).permute(1, 0, 2, 3)
+        return grads
+
+    def heads_updated(self):
+        """Call after parameters of the assignment heads or exit tokens were changed in place (optimizer.step()): the
+        device copies the kernels read are refreshed IN PLACE, at the addresses captured graphs replay, so `forward`,
+        `forward_pairs` and `forward_layers` give what a fresh module loaded from `state_dict()` gives.  The trunk's
+        packed weights are not rebuilt.  (A parameter that already lives on the device in fp32 is read by the kernels
+        where it is: only its fp16 copy needs the refresh.)"""
+        if self._packed is None:
+            return
+        with torch.no_grad():
+            for param, t32, t16 in self._packed[3]:
+                if t32.data_ptr() != param.data_ptr():
+                    t32.copy_(param.detach().reshape(t32.shape))
+                if t16 is not None:
+                    t16.copy_(t32)
 
 
 __main_model__ = LightGlue

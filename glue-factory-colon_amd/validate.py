@@ -330,13 +330,12 @@ def _report(res):
     return res
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+def data_arguments(ap):
+    """The options that choose the pairs, the model and the labels (shared with finetune_heads)."""
     ap.add_argument("--data_dir", required=True, help="the image tree (train/ val/ test/ inside)")
     ap.add_argument("--dataset", default="homographies", choices=["homographies", "posed_images", "endomapper"])
     ap.add_argument("--split", default="val")
     ap.add_argument("--pair_batch", type=int, default=32)
-    ap.add_argument("--log_metrics", default=None, help="append the per-pair TSV to this file")
     ap.add_argument("--extractor_weights", default="synthetic", help="local .pth (reference key names) or 'synthetic'")
     ap.add_argument("--matcher_weights", default="synthetic")
     ap.add_argument("--max_num_keypoints", type=int, default=512)
@@ -349,11 +348,11 @@ def main(argv=None):
     ap.add_argument("--th_positive", type=float, default=None, help="endomapper: th_positive (default null)")
     ap.add_argument("--th_negative", type=float, default=10.0, help="endomapper: th_negative")
     ap.add_argument("--max_num_features", type=int, default=2048, help="endomapper: key points per view")
-    ap.add_argument("--eval_overlap_bins", default=None, help='overlap bins "low:high,low:high" (reported under bins)')
-    ap.add_argument("--layer_report", action="store_true",
-                    help="score every LightGlue layer (forward_layers + layer_loss): loss/confidence, loss/total_deep, "
-                         "a per-layer table and the same columns in the TSV")
-    args = ap.parse_args(argv)
+
+
+def setup(args):
+    """-> (model_conf of the ValidationPipeline, loader() = a fresh feeder over the split, view_key or None, the
+    function that prints a result) for the parsed `data_arguments`."""
     torch.set_num_threads(max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 16)))
     from .registry import get_dataset
 
@@ -364,13 +363,10 @@ def main(argv=None):
         dataset = get_dataset("endomapper")({"data_dir": data_dir.name, "max_num_features": args.max_num_features,
                                              "reseed": True, args.split + "_split": _endomapper_split(data_dir, args.split)},
                                             data_dir.parent, split=args.split)
-        pipe = ValidationPipeline(endomapper_model_conf(args.ground_truth, args.th_positive, args.th_negative, args.th_epi,
-                                                        args.matcher_weights),
-                                  pair_batch=args.pair_batch, eval_overlap_bins=args.eval_overlap_bins,
-                                  layer_report=args.layer_report)
-        res = pipe.run(dataset.feeder("cuda", num_workers=args.num_workers, batch=args.pair_batch),
-                       log_metrics=args.log_metrics, view_key=dataset.view_key)
-        return _report(res)
+        conf = endomapper_model_conf(args.ground_truth, args.th_positive, args.th_negative, args.th_epi,
+                                     args.matcher_weights)
+        return (conf, lambda: dataset.feeder("cuda", num_workers=args.num_workers, batch=args.pair_batch),
+                dataset.view_key, _report)
     if args.dataset == "posed_images":
         from .eval_pose_pairs import BENCHMARK_DATA
 
@@ -378,17 +374,29 @@ def main(argv=None):
         if conf.pop("name") != "posed_images":
             raise NotImplementedError(f"{args.benchmark}: not a posed_images directory")
         dataset = get_dataset("posed_images")(conf, args.data_dir)
-        pipe = ValidationPipeline({**model_conf, "ground_truth": {**DEPTH_GROUND_TRUTH, "th_epi": args.th_epi}},
-                                  pair_batch=args.pair_batch, layer_report=args.layer_report)
-        res = pipe.run(dataset.feeder("cuda", num_workers=args.num_workers), log_metrics=args.log_metrics)
-        return _print(res)
+        return ({**model_conf, "ground_truth": {**DEPTH_GROUND_TRUTH, "th_epi": args.th_epi}},
+                lambda: dataset.feeder("cuda", num_workers=args.num_workers), None, _print)
     data_dir = Path(args.data_dir).resolve()
     dataset = get_dataset("homographies")({"data_dir": data_dir.name, "photometric": {"name": "identity"},
                                            "reseed": True}, data_dir.parent, split=args.split)
-    pipe = ValidationPipeline(model_conf, pair_batch=args.pair_batch, layer_report=args.layer_report)
-    res = pipe.run(dataset.feeder(batch=args.pair_batch, num_workers=args.num_workers), log_metrics=args.log_metrics,
-                   view_key=dataset.view_key)
-    return _print(res)
+    return (model_conf, lambda: dataset.feeder(batch=args.pair_batch, num_workers=args.num_workers), dataset.view_key,
+            _print)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    data_arguments(ap)
+    ap.add_argument("--log_metrics", default=None, help="append the per-pair TSV to this file")
+    ap.add_argument("--eval_overlap_bins", default=None, help='overlap bins "low:high,low:high" (reported under bins)')
+    ap.add_argument("--layer_report", action="store_true",
+                    help="score every LightGlue layer (forward_layers + layer_loss): loss/confidence, loss/total_deep, "
+                         "a per-layer table and the same columns in the TSV")
+    args = ap.parse_args(argv)
+    model_conf, loader, view_key, report = setup(args)
+    # (the overlap bins belong to the Endomapper pairs, the only ones that carry an overlap)
+    pipe = ValidationPipeline(model_conf, pair_batch=args.pair_batch, layer_report=args.layer_report,
+                              eval_overlap_bins=args.eval_overlap_bins if args.dataset == "endomapper" else None)
+    return report(pipe.run(loader(), log_metrics=args.log_metrics, view_key=view_key))
 
 
 if __name__ == "__main__":
