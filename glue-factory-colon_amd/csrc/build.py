@@ -20,7 +20,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 SOURCES = ["runtime.hip", "conv.hip", "conv_wino.hip", "conv_wino43.hip", "gemm.hip", "attention.hip", "lg_fp16.hip", "sp_detect.hip", "sp_heads.hip", "disk_detect.hip", "disk_unet.hip", "lg_misc.hip", "lg_adaptive.hip", "eval_metrics.hip", "eval_pose.hip", "gt_matches.hip", "gt_sparse_map.hip", "gt_dense_warp.hip", "lg_validation.hip", "lg_layer_scores.hip", "lg_head_backward.hip", "ransac.hip", "relpose.hip", "preprocess.hip", "warp.hip", "superglue.hip", "sift.hip", "api.hip"]
-HEADERS = ["common.h", "block_select.h", "runtime.h", "eval_common.h", "ransac_common.h", "relpose_solver.h", "lg_rowdot.h", os.path.join(PKG, "..", "include", "gfc_amd.h"),
+HEADERS = ["common.h", "block_select.h", "runtime.h", "eval_common.h", "gt_sweep.h", "ransac_common.h", "relpose_solver.h", "lg_rowdot.h", os.path.join(PKG, "..", "include", "gfc_amd.h"),
            os.path.join(PKG, "..", "include", "gfc_amd_validation.h"),
            os.path.join(PKG, "..", "include", "gfc_amd_sparse_map.h"),
            os.path.join(PKG, "..", "include", "gfc_amd_dense_warp.h"),

@@ -2,17 +2,13 @@
 // and the label part of gt_matches_from_roma (gluefactory/geometry/gt_generation.py:127-134, 149-269).  The sampling
 // rule, the order of decisions and the launch plan are stated in include/gfc_amd_dense_warp.h.
 //
-// The sweep is that of gt_sparse_map.hip (a pair split over workgroups, SM_OWN key points x SM_LANES lanes, the other
-// side through LDS in tiles, (distance, index) reduction with the lower index winning) written anew for another tile
-// element and other minima: gfc_gt_matches_sparse_map keeps its code.  fminf / '<' on the running minima skip a NaN
-// distance where torch.min would propagate it: the known difference stated in the header.
-#include "eval_common.h"
+// A pair is split over workgroups by the sweep of gt_sweep.h, which also states the arg-min rule (ties, a row of +inf,
+// NaN) and the known difference from the reference.  Here: the samplers, what a RoMa key point brings to that sweep (one
+// flag, `valid_pos`, for the masked distance and the one-way minimum alike), the verdicts and the dense outputs.
+#include "gt_sweep.h"
 #include "../../include/gfc_amd_dense_warp.h"
 
-#define DW_THREADS 256
-#define DW_LANES 16                      // lanes per owned key point
-#define DW_OWN (DW_THREADS / DW_LANES)   // 16 key points per workgroup
-#define DW_TILE 256                      // elements of the other side per LDS tile: one per thread
+#define DW_THREADS 256  // every kernel here but the sweep, which has gt_sweep.h's shape
 
 // ---- F.grid_sample(bilinear, zeros, align_corners=False) --------------------------------------------------------------
 struct DwTaps {
@@ -140,73 +136,20 @@ __device__ __forceinline__ bool dw_valid_pos(const DwSide& s, const DwTh& th, si
   return v;
 }
 
-// (r, c) as in gt_sparse_map.hip: r = (kp0 projected into image 1, kp0), c = (kp1, kp1 projected into image 0)
-__device__ __forceinline__ float4 dw_coords(const DwSide& s, int side, size_t g) {
-  const float x = s.kp[2 * g], y = s.kp[2 * g + 1], px = s.proj[2 * g], py = s.proj[2 * g + 1];
-  return side == 0 ? make_float4(px, py, x, y) : make_float4(x, y, px, py);
-}
-
-__device__ __forceinline__ void dw_dists(const float4& r, const float4& c, float& d0, float& d1) {
-  const float dx0 = r.x - c.x, dy0 = r.y - c.y;
-  const float dx1 = r.z - c.z, dy1 = r.w - c.w;
-  d0 = dx0 * dx0 + dy0 * dy0;
-  d1 = dx1 * dx1 + dy1 * dy1;
-}
-
-// SIDE is the side of the OWNED key points
-template <int SIDE>
-__device__ __forceinline__ void dw_sweep(const DwSide& own, const DwSide& oth, const DwTh& th, int blk, int b,
-                                         float4* t_xy, unsigned char* t_flag, float* __restrict__ w_best,
-                                         int* __restrict__ w_arg, float* __restrict__ w_own) {
-  const int tid = threadIdx.x, lane = tid % DW_LANES;
-  const int k = blk * DW_OWN + tid / DW_LANES;  // the owned key point
-  const bool live = k < own.n;
-  const size_t g = (size_t)b * own.n + (live ? k : 0);
-  const float4 me = dw_coords(own, SIDE, g);
-  const bool vp = live && dw_valid_pos(own, th, g);
-  float best = INFINITY, best_own = INFINITY;
-  int bi = 0;
-  for (int base = 0; base < oth.n; base += DW_TILE) {
-    const int cnt = min(DW_TILE, oth.n - base);
-    __syncthreads();  // the previous tile has been read
-    if (tid < cnt) {
-      const size_t q = (size_t)b * oth.n + base + tid;
-      t_xy[tid] = dw_coords(oth, 1 - SIDE, q);
-      t_flag[tid] = dw_valid_pos(oth, th, q);
-    }
-    __syncthreads();
-    for (int e = lane; e < cnt; e += DW_LANES) {
-      const float4 r = SIDE == 0 ? me : t_xy[e];
-      const float4 c = SIDE == 0 ? t_xy[e] : me;
-      const bool f = t_flag[e] != 0;
-      float d0, d1;
-      dw_dists(r, c, d0, d1);
-      const float d = (vp && f) ? fmaxf(d0, d1) : INFINITY;
-      if (d < best) { best = d; bi = base + e; }
-      if (f) best_own = fminf(best_own, SIDE == 0 ? d0 : d1);
-    }
+struct DwLabeller {  // for gt_sweep: valid_pos masks the distance and admits a key point to the one-way minimum
+  using Side = DwSide;
+  const DwTh& th;
+  __device__ __forceinline__ unsigned char flags(const DwSide& s, size_t g) const {
+    return dw_valid_pos(s, th, g) ? GTS_MASKED : 0;
   }
-#pragma unroll
-  for (int o = DW_LANES / 2; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, DW_LANES);
-    const int oi = __shfl_xor(bi, o, DW_LANES);
-    if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    best_own = fminf(best_own, __shfl_xor(best_own, o, DW_LANES));
-  }
-  if (live && lane == 0) { w_best[g] = best; w_arg[g] = bi; w_own[g] = best_own; }
-}
+  static __device__ __forceinline__ bool own_min(unsigned char f) { return f & GTS_MASKED; }
+};
 
-__global__ __launch_bounds__(DW_THREADS) void dw_sweep_kernel(DwSide s0, DwSide s1, DwTh th, int row_blocks, size_t side1,
-                                                              float* __restrict__ w_best, int* __restrict__ w_arg,
-                                                              float* __restrict__ w_own) {
-  // one tile for both instantiations: 256 x (16 + 1) = 4352 bytes of static LDS
-  __shared__ __attribute__((aligned(16))) float4 t_xy[DW_TILE];
-  __shared__ unsigned char t_flag[DW_TILE];
-  const int b = blockIdx.y;
-  if ((int)blockIdx.x < row_blocks)
-    dw_sweep<0>(s0, s1, th, blockIdx.x, b, t_xy, t_flag, w_best, w_arg, w_own);
-  else
-    dw_sweep<1>(s1, s0, th, blockIdx.x - row_blocks, b, t_xy, t_flag, w_best + side1, w_arg + side1, w_own + side1);
+__global__ __launch_bounds__(GTS_THREADS) void dw_sweep_kernel(DwSide s0, DwSide s1, DwTh th, int row_blocks, size_t side1,
+                                                               GtsOut w) {
+  __shared__ __attribute__((aligned(16))) GtsTile tile;
+  GtsNoExtra none;
+  gt_sweep_pair(DwLabeller{th}, s0, s1, row_blocks, side1, tile, w, none);
 }
 
 // Steps 3-8 per key point.  grid (ceil((M + N) / DW_THREADS), B): threads 0..M-1 of a pair are its rows, then its columns.
@@ -229,7 +172,7 @@ __global__ __launch_bounds__(DW_THREADS) void dw_finish_kernel(DwSide s0, DwSide
   const size_t w = (side ? side1 : 0) + g;                  // in the workspace
   const size_t wo = (side ? 0 : side1) + (size_t)b * ot.n;  // the other side's key points of this pair in the workspace
   const int a = w_arg[w];
-  const int p = (w_best[w] < th.pos2 && w_arg[wo + a] == k) ? a : -1;
+  const int p = gt_mutual_positive(w_best[w] < th.pos2, w_arg + wo, a, k) ? a : -1;
   const bool vp = dw_valid_pos(me, th, g);
   const bool valid = me.valid[g] != 0;
   const float c = me.cert[g], e = me.cyc[g];
@@ -265,21 +208,19 @@ __global__ __launch_bounds__(DW_THREADS) void dw_dense_kernel(DwSide s0, DwSide 
   if (assignment) assignment[o] = pos;
   if (!reward) return;
   float d0, d1;
-  dw_dists(dw_coords(s0, 0, r), dw_coords(s1, 1, c), d0, d1);
+  gt_pair_dists(gt_coords(s0.kp, s0.proj, 0, r), gt_coords(s1.kp, s1.proj, 1, c), d0, d1);
   const bool pair = w_vp[r] && w_vp[side1 + c];
   const float d = pair ? fmaxf(d0, d1) : INFINITY;
   const float gain = fmaxf((pair && d < th.pos2) ? 1.f : 0.f, pos ? 1.f : 0.f);
   reward[o] = gain - ((pair && d > th.neg2) ? 1.f : 0.f);
 }
 
-// Workspace: one description, used by gfc_gt_matches_roma_workspace_bytes and by the launcher.  K = B (M + N) key points,
-// side 0 of every pair first ([B,M]), then side 1 ([B,N]) inside each array.
-struct DwWs { size_t best, arg, own, vp, pos0, total; };
+// Workspace: one description, used by gfc_gt_matches_roma_workspace_bytes and by the launcher: the head every split
+// labeller has (gt_sweep.h), then vp over the same K = B (M + N) key points, and pos0 [B,M].
+struct DwWs { GtsSlots sweep; size_t vp, pos0, total; };
 static DwWs dw_ws(int B, int M, int N) {
-  const size_t K = (size_t)B * ((size_t)M + N);
   gfc_slots s;
-  return {s.take(K * sizeof(float)), s.take(K * sizeof(int)), s.take(K * sizeof(float)), s.take(K),
-          s.take((size_t)B * M * sizeof(int)), s.off};
+  return {gts_slots(s, B, M, N), s.take(gts_points(B, M, N)), s.take((size_t)B * M * sizeof(int)), s.off};
 }
 
 static bool dw_aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
@@ -339,16 +280,9 @@ extern "C" int gfc_gt_matches_roma(const float* kp0, const float* kp1, const flo
                                    float* reward, void* workspace, size_t workspace_bytes, void* stream) {
   if (!dw_sizes_ok(B, M, N) || !(pos_th >= 0.0) || !(neg_th >= 0.0)) return GFC_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  if (M == 0 || N == 0) {  // gt_generation.py:62-94: every key point of the other side unmatched, nothing positive
-    if ((M > 0 && (!matches0 || !scores0)) || (N > 0 && (!matches1 || !scores1))) return GFC_ERR_INVALID;
-    hipError_t e = hipSuccess;
-    if (M > 0) e = hipMemsetAsync(matches0, 0xFF, (size_t)B * M * sizeof(int64_t), s);
-    if (e == hipSuccess && N > 0) e = hipMemsetAsync(matches1, 0xFF, (size_t)B * N * sizeof(int64_t), s);
-    if (e == hipSuccess && M > 0) e = hipMemsetAsync(scores0, 0, (size_t)B * M * sizeof(float), s);
-    if (e == hipSuccess && N > 0) e = hipMemsetAsync(scores1, 0, (size_t)B * N * sizeof(float), s);
-    if (e == hipSuccess && M > 0 && masks0) e = hipMemsetAsync(masks0, 0, (size_t)B * 4 * M, s);
-    if (e == hipSuccess && N > 0 && masks1) e = hipMemsetAsync(masks1, 0, (size_t)B * 4 * N, s);
-    return e == hipSuccess ? GFC_OK : GFC_ERR_LAUNCH;
+  if (M == 0 || N == 0) {
+    if ((M > 0 && !scores0) || (N > 0 && !scores1)) return GFC_ERR_INVALID;
+    return gt_empty_side(B, M, N, matches0, matches1, nullptr, scores0, scores1, masks0, masks1, nullptr, s);
   }
   if (!kp0 || !kp1 || !proj_0to1 || !proj_1to0 || !certainty_kp0 || !certainty_kp1 || !cycle_kp0 || !cycle_kp1 ||
       !valid0 || !valid1 || !matches0 || !matches1 || !scores0 || !scores1)
@@ -356,9 +290,7 @@ extern "C" int gfc_gt_matches_roma(const float* kp0, const float* kp1, const flo
   const DwWs L = dw_ws(B, M, N);
   if (!workspace || workspace_bytes < L.total) return GFC_ERR_WORKSPACE;
   char* ws = (char*)workspace;
-  float* w_best = (float*)(ws + L.best);
-  int* w_arg = (int*)(ws + L.arg);
-  float* w_own = (float*)(ws + L.own);
+  const GtsOut w = gts_out(workspace, L.sweep);
   unsigned char* w_vp = (unsigned char*)(ws + L.vp);
   int* w_pos0 = (int*)(ws + L.pos0);
   const size_t side1 = (size_t)B * M;  // where the [B,N] part of a workspace array starts
@@ -375,12 +307,12 @@ extern "C" int gfc_gt_matches_roma(const float* kp0, const float* kp1, const flo
   th.pos_cyc = (float)pos_cycle_error_th;
   th.neg_cert = (float)neg_cert_th;
   th.neg_cyc = (float)neg_cycle_error_th;
-  const int row_blocks = (M + DW_OWN - 1) / DW_OWN, col_blocks = (N + DW_OWN - 1) / DW_OWN;
-  hipLaunchKernelGGL(dw_sweep_kernel, dim3(row_blocks + col_blocks, B), dim3(DW_THREADS), 0, s, s0, s1, th, row_blocks,
-                     side1, w_best, w_arg, w_own);
+  const int row_blocks = gts_blocks(M), col_blocks = gts_blocks(N);
+  hipLaunchKernelGGL(dw_sweep_kernel, dim3(row_blocks + col_blocks, B), dim3(GTS_THREADS), 0, s, s0, s1, th, row_blocks,
+                     side1, w);
   GFC_LAUNCH_CHECK();
   hipLaunchKernelGGL(dw_finish_kernel, dim3((M + N + DW_THREADS - 1) / DW_THREADS, B), dim3(DW_THREADS), 0, s, s0, s1, th,
-                     side1, w_best, w_arg, w_own, w_vp, w_pos0, (long long*)matches0, (long long*)matches1, scores0,
+                     side1, w.best, w.arg, w.own, w_vp, w_pos0, (long long*)matches0, (long long*)matches1, scores0,
                      scores1, masks0, masks1);
   GFC_LAUNCH_CHECK();
   if (assignment || reward) {

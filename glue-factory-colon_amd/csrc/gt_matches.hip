@@ -4,14 +4,14 @@
 //
 // gt_matches_kernel: one workgroup per pair, every key point of the pair in LDS, the M x N distance matrix never stored.
 // A row sweep and a column sweep keep (min, argmin) of the MASKED distance and the min of the UNMASKED one-way distance
-// per key point in registers ('<' on a running minimum that starts at +inf: the first index wins a tie and a row of +inf
-// keeps arg-min 0, like torch.min); a third pass gives the verdicts.  With a fundamental matrix a fourth pass is the
+// per key point in registers (the arg-min rule of gt_sweep.h, one thread walking the whole row); a third pass gives the
+// verdicts.  With a fundamental matrix a fourth pass is the
 // epi_th rule: a row / column minimum of the symmetric epipolar distance over ignore x ignore, again never stored.
 // The two projections come from a homography (computed here) or from pose and depth (given: gfc_eval_pose_project or
 // gt_project_kernel).  No static LDS: the dynamic region is all there is.
 // LDS = 21 (M + N) bytes <= 160 KB: M + N <= 7801 is admitted, 3901 x 3901 is the first square shape refused.
 // gt_dense_kernel: plain writes of assignment / reward, one thread per element, gridded over (column blocks, rows, B).
-#include "eval_common.h"
+#include "gt_sweep.h"
 #include "../../include/gfc_amd_validation.h"
 
 #define GT_THREADS 1024  // 16 waves on the one CU a pair occupies: four per SIMD to hide the LDS latency of the sweeps
@@ -24,14 +24,6 @@ inline size_t gt_dynamic_lds(int M, int N) { return (size_t)21 * M + (size_t)21 
 // its smallest masked distance is below pos_th^2 / it may be negative (the same mask for a homography, `valid` depth
 // for the depth matcher) / its match is `ignore` before the epi_th rule
 enum : unsigned char { GT_VALID = 1, GT_NEGATIVE = 2, GT_BELOW_POS = 4, GT_MAY_NEG = 8, GT_IGNORE = 16 };
-
-// sym_epipolar_distance_all (gluefactory/geometry/epipolar.py:59-72) of one pair of pixels: l0 = F p0, l1 = F^T p1
-__device__ __forceinline__ float gt_epi_dist(const float* F, float x0, float y0, float x1, float y1) {
-  const float a0 = F[0] * x0 + F[1] * y0 + F[2], b0 = F[3] * x0 + F[4] * y0 + F[5], c0 = F[6] * x0 + F[7] * y0 + F[8];
-  const float a1 = F[0] * x1 + F[3] * y1 + F[6], b1 = F[1] * x1 + F[4] * y1 + F[7];
-  const float num = fabsf(x1 * a0 + y1 * b0 + c0);
-  return (num / sqrtf(a0 * a0 + b0 * b0 + 1e-15f) + num / sqrtf(a1 * a1 + b1 * b1 + 1e-15f)) / 2.f;
-}
 
 __global__ __launch_bounds__(GT_THREADS) void gt_matches_kernel(
     const float* __restrict__ kp0, const float* __restrict__ kp1, const float* __restrict__ H,
@@ -96,10 +88,9 @@ __global__ __launch_bounds__(GT_THREADS) void gt_matches_kernel(
     int bi = 0;
     for (int i = 0; i < M; ++i) {
       const float4 r = r0[i];
-      const float dx0 = r.x - c.x, dy0 = r.y - c.y;
-      const float dx1 = r.z - c.z, dy1 = r.w - c.w;
-      const float d1 = dx1 * dx1 + dy1 * dy1;
-      const float d = (vj && (v0[i] & GT_VALID)) ? fmaxf(dx0 * dx0 + dy0 * dy0, d1) : INFINITY;
+      float d0, d1;
+      gt_pair_dists(r, c, d0, d1);
+      const float d = (vj && (v0[i] & GT_VALID)) ? fmaxf(d0, d1) : INFINITY;
       if (d < best) { best = d; bi = i; }
       best_d1 = fminf(best_d1, d1);
     }
@@ -115,10 +106,9 @@ __global__ __launch_bounds__(GT_THREADS) void gt_matches_kernel(
     int bj = 0;
     for (int j = 0; j < N; ++j) {
       const float4 c = c1[j];
-      const float dx0 = r.x - c.x, dy0 = r.y - c.y;
-      const float dx1 = r.z - c.z, dy1 = r.w - c.w;
-      const float d0 = dx0 * dx0 + dy0 * dy0;
-      const float d = (vi && (v1[j] & GT_VALID)) ? fmaxf(d0, dx1 * dx1 + dy1 * dy1) : INFINITY;
+      float d0, d1;
+      gt_pair_dists(r, c, d0, d1);
+      const float d = (vi && (v1[j] & GT_VALID)) ? fmaxf(d0, d1) : INFINITY;
       if (d < best) { best = d; bj = j; }
       best_d0 = fminf(best_d0, d0);
     }
@@ -130,7 +120,7 @@ __global__ __launch_bounds__(GT_THREADS) void gt_matches_kernel(
   // dist[i, min0[i]] -- the row minimum -- is below pos_th^2.  negative overrides positive in matches.
   for (int i = tid; i < M; i += GT_THREADS) {
     const int bj = min0[i];
-    const bool positive = (v0[i] & GT_BELOW_POS) && min1[bj] == i;
+    const bool positive = gt_mutual_positive(v0[i] & GT_BELOW_POS, min1, bj, i);
     const long long m = (v0[i] & GT_NEGATIVE) ? -1 : (positive ? bj : -2);
     m0_out[(size_t)b * M + i] = m;
     if (positive0) positive0[(size_t)b * M + i] = positive ? bj : -1;
@@ -138,7 +128,7 @@ __global__ __launch_bounds__(GT_THREADS) void gt_matches_kernel(
   }
   for (int j = tid; j < N; j += GT_THREADS) {
     const int bi = min1[j];
-    const bool positive = (v1[j] & GT_BELOW_POS) && min0[bi] == j;
+    const bool positive = gt_mutual_positive(v1[j] & GT_BELOW_POS, min0, bi, j);
     const long long m = (v1[j] & GT_NEGATIVE) ? -1 : (positive ? bi : -2);
     m1_out[(size_t)b * N + j] = m;
     if (m == -2) v1[j] |= GT_IGNORE;
@@ -188,10 +178,10 @@ __global__ __launch_bounds__(EM_THREADS) void gt_dense_kernel(
   const size_t o = r * N + j;
   if (assignment) assignment[o] = positive0[r] == j;
   if (!reward) return;
-  const float dx0 = proj01[2 * r] - kp1[2 * c], dy0 = proj01[2 * r + 1] - kp1[2 * c + 1];
-  const float dx1 = kp0[2 * r] - proj10[2 * c], dy1 = kp0[2 * r + 1] - proj10[2 * c + 1];
+  float d0, d1;
+  gt_pair_dists(gt_coords(kp0, proj01, 0, r), gt_coords(kp1, proj10, 1, c), d0, d1);
   const bool vis = (!mask0 || mask0[r]) && (!mask1 || mask1[c]);
-  const float d = vis ? fmaxf(dx0 * dx0 + dy0 * dy0, dx1 * dx1 + dy1 * dy1) : INFINITY;
+  const float d = vis ? fmaxf(d0, d1) : INFINITY;
   float penalty;
   if (!Fm) {
     penalty = d > neg2 ? 1.f : 0.f;
@@ -239,17 +229,6 @@ extern "C" size_t gfc_gt_matches_homography_lds_bytes(int M, int N) {
   return (M < 0 || N < 0) ? 0 : gt_dynamic_lds(M, N);
 }
 
-// the early return of the reference (gt_generation.py:598-634, 735-753): every key point of the other side unmatched,
-// no projection written, no dense element exists.  No kernel: -1 is all bits set in int64 and int32 alike.
-static int gt_empty_side(int B, int M, int N, int64_t* matches0, int64_t* matches1, int32_t* positive0, hipStream_t s) {
-  if ((M > 0 && !matches0) || (N > 0 && !matches1)) return GFC_ERR_INVALID;
-  if (M > 0 && hipMemsetAsync(matches0, 0xFF, (size_t)B * M * sizeof(int64_t), s) != hipSuccess) return GFC_ERR_LAUNCH;
-  if (N > 0 && hipMemsetAsync(matches1, 0xFF, (size_t)B * N * sizeof(int64_t), s) != hipSuccess) return GFC_ERR_LAUNCH;
-  if (M > 0 && positive0 && hipMemsetAsync(positive0, 0xFF, (size_t)B * M * sizeof(int32_t), s) != hipSuccess)
-    return GFC_ERR_LAUNCH;
-  return GFC_OK;
-}
-
 static int gt_launch(const float* kp0, const float* kp1, const float* H, const float* Hinv, const float* in01,
                      const float* in10, const uint8_t* mask0, const uint8_t* mask1, const uint8_t* mayneg0,
                      const uint8_t* mayneg1, const float* F, int use_epi, double epi_th, int B, int M, int N,
@@ -284,7 +263,9 @@ extern "C" int gfc_gt_matches_homography(const float* kp0, const float* kp1, con
                                          float* proj_0to1, float* proj_1to0, int32_t* positive0, uint8_t* assignment,
                                          float* reward, void* stream) {
   if (B <= 0 || M < 0 || N < 0 || B > 65535 || M > 65535) return GFC_ERR_INVALID;
-  if (M == 0 || N == 0) return gt_empty_side(B, M, N, matches0, matches1, positive0, (hipStream_t)stream);
+  if (M == 0 || N == 0)
+    return gt_empty_side(B, M, N, matches0, matches1, positive0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         (hipStream_t)stream);
   if (!kp0 || !kp1 || !H || !Hinv || !matches0 || !matches1 || !proj_0to1 || !proj_1to0) return GFC_ERR_INVALID;
   if (assignment && !positive0) return GFC_ERR_INVALID;
   return gt_launch(kp0, kp1, H, Hinv, nullptr, nullptr, valid0, valid1, nullptr, nullptr, nullptr, 0, 0.0, B, M, N,
@@ -298,7 +279,9 @@ extern "C" int gfc_gt_matches_depth(const float* kp0, const float* kp1, const fl
                                     double neg_th, double epi_th, int64_t* matches0, int64_t* matches1,
                                     int32_t* positive0, uint8_t* assignment, float* reward, void* stream) {
   if (B <= 0 || M < 0 || N < 0 || B > 65535 || M > 65535) return GFC_ERR_INVALID;
-  if (M == 0 || N == 0) return gt_empty_side(B, M, N, matches0, matches1, positive0, (hipStream_t)stream);
+  if (M == 0 || N == 0)
+    return gt_empty_side(B, M, N, matches0, matches1, positive0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         (hipStream_t)stream);
   if (!kp0 || !kp1 || !proj_0to1 || !proj_1to0 || !visible0 || !visible1 || !valid0 || !valid1 || !matches0 || !matches1)
     return GFC_ERR_INVALID;
   const int use_epi = epi_th >= 0.0;

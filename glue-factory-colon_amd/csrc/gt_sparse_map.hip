@@ -2,35 +2,23 @@
 // gt_matches_from_pose_sparse_dense_map (reference gluefactory/geometry/gt_generation.py:441-591, 271-438).  The order
 // of decisions and the launch plan are stated in include/gfc_amd_sparse_map.h.
 //
-// Unlike gt_matches_kernel (gt_matches.hip: one workgroup per pair, every key point in LDS) a pair is SPLIT over
-// workgroups: a workgroup owns SM_OWN key points of one side, SM_LANES lanes each, and streams the other side through
-// LDS in tiles of SM_TILE elements.  A lane sees its elements in ascending order and keeps the first of equal distances
-// ('<' on a running minimum that starts at +inf with index 0, as torch.min); the lanes of a key point are then reduced
-// on (distance, index) with the lower index winning, so the result does not depend on the split.  Per-key-point results
-// go to the workspace, a short second launch gives the verdicts; no workgroup waits for another.
-// The per-distance expressions are those of gt_matches_kernel and gt_epi_dist, operand for operand -- fminf / '<' on the
-// running minima included, which skip a NaN distance where torch.min would propagate it (then `NaN > neg_th^2` is false
-// and the point stays `ignore`, while here, as in gt_matches_kernel, it can become `negative`): the one
-// known difference from the reference, for a key point with valid depth whose projection is NaN.
-#include "eval_common.h"
+// A pair is split over workgroups by the sweep of gt_sweep.h, which also states the arg-min rule (ties, a row of +inf,
+// NaN) and the one known difference from the reference.  Here: what a sparse-map key point brings to that sweep (its
+// flags and the seeding by 3D-point identity), the verdicts, the th_epi rule and the dense outputs.
+#include "gt_sweep.h"
 #include "../../include/gfc_amd_sparse_map.h"
 
-#define SM_THREADS 256
-#define SM_LANES 16                      // lanes per owned key point: a quarter of a wave, reduced with __shfl_xor
-#define SM_OWN (SM_THREADS / SM_LANES)   // 16 key points per workgroup
-#define SM_TILE 256                      // elements of the other side per LDS tile: one per thread
+enum : unsigned char { SM_VISIBLE = GTS_MASKED, SM_VALID3D = 2 };  // flag byte of a key point in the sweep
+enum : unsigned char { SM_IGNORE = 1 };                             // state byte: the match is -2 BEFORE the epi_th rule
 
-enum : unsigned char { SM_VISIBLE = 1, SM_VALID3D = 2 };  // flag byte of a tile element in the sweep
-enum : unsigned char { SM_IGNORE = 1 };                   // state byte: the match is -2 BEFORE the epi_th rule
-
-// Workspace: one description, used by gfc_gt_matches_sparse_map_workspace_bytes and by the launcher.  K = B (M + N) key
-// points, side 0 of every pair first ([B,M]), then side 1 ([B,N]) inside each array.
-struct SmWs { size_t best, arg, own, first, count, state, pos0, total; };
+// Workspace: one description, used by gfc_gt_matches_sparse_map_workspace_bytes and by the launcher: the head every
+// split labeller has (gt_sweep.h), then first, count and state over the same K = B (M + N) key points, and pos0 [B,M].
+struct SmWs { GtsSlots sweep; size_t first, count, state, pos0, total; };
 static SmWs sm_ws(int B, int M, int N) {
-  const size_t K = (size_t)B * ((size_t)M + N);
+  const size_t K = gts_points(B, M, N);
   gfc_slots s;
-  return {s.take(K * sizeof(float)), s.take(K * sizeof(int)), s.take(K * sizeof(float)), s.take(K * sizeof(int)),
-          s.take(K * sizeof(int)),   s.take(K),               s.take((size_t)B * M * sizeof(int)), s.off};
+  return {gts_slots(s, B, M, N), s.take(K * sizeof(int)), s.take(K * sizeof(int)), s.take(K),
+          s.take((size_t)B * M * sizeof(int)), s.off};
 }
 
 struct SmSide {  // one image of the batch
@@ -43,106 +31,64 @@ struct SmSide {  // one image of the batch
   int n;
 };
 
-// sym_epipolar_distance_all (gluefactory/geometry/epipolar.py:59-72) of one pair of pixels, as gt_epi_dist of
-// gt_matches.hip writes it: l0 = F p0, l1 = F^T p1
-__device__ __forceinline__ float sm_epi_dist(const float* F, float x0, float y0, float x1, float y1) {
-  const float a0 = F[0] * x0 + F[1] * y0 + F[2], b0 = F[3] * x0 + F[4] * y0 + F[5], c0 = F[6] * x0 + F[7] * y0 + F[8];
-  const float a1 = F[0] * x1 + F[3] * y1 + F[6], b1 = F[1] * x1 + F[4] * y1 + F[7];
-  const float num = fabsf(x1 * a0 + y1 * b0 + c0);
-  return (num / sqrtf(a0 * a0 + b0 * b0 + 1e-15f) + num / sqrtf(a1 * a1 + b1 * b1 + 1e-15f)) / 2.f;
-}
+__device__ __forceinline__ bool sm_valid3d(const SmSide& s, size_t g) { return s.valid3d ? s.valid3d[g] != 0 : true; }
 
-// (r, c) of gt_matches_kernel: r = (kp0 projected into image 1, kp0), c = (kp1, kp1 projected into image 0)
-__device__ __forceinline__ float4 sm_coords(const SmSide& s, int side, size_t g) {
-  const float x = s.kp[2 * g], y = s.kp[2 * g + 1], px = s.proj[2 * g], py = s.proj[2 * g + 1];
-  return side == 0 ? make_float4(px, py, x, y) : make_float4(x, y, px, py);
-}
+struct SmLabeller {  // for gt_sweep: `visible` masks the distance, every key point counts in the one-way minimum
+  using Side = SmSide;
+  __device__ __forceinline__ unsigned char flags(const SmSide& s, size_t g) const {
+    return (s.visible[g] ? SM_VISIBLE : 0) | (sm_valid3d(s, g) ? SM_VALID3D : 0);
+  }
+  static __device__ __forceinline__ bool own_min(unsigned char) { return true; }
+};
 
-// Sweep.  blockIdx.x < row_blocks: SM_OWN rows of image 0 against every column; otherwise SM_OWN columns against every
-// row.  blockIdx.y = pair.  SIDE is the side of the OWNED key points.
-template <int SIDE>
-__device__ __forceinline__ void sm_sweep(const SmSide& own, const SmSide& oth, int blk, int b, float4* t_xy,
-                                         long long* t_id, unsigned char* t_flag, float* __restrict__ w_best,
-                                         int* __restrict__ w_arg, float* __restrict__ w_own, int* __restrict__ w_first,
-                                         int* __restrict__ w_count) {
-  const int tid = threadIdx.x, lane = tid % SM_LANES;
-  const int k = blk * SM_OWN + tid / SM_LANES;  // the owned key point
-  const bool live = k < own.n;
-  const size_t g = (size_t)b * own.n + (live ? k : 0);
-  const float4 me = sm_coords(own, SIDE, g);
-  const bool vis = live && own.visible[g] != 0;
-  const bool use_ids = own.ids != nullptr;
-  const bool id_ok = live && use_ids && (own.valid3d ? own.valid3d[g] != 0 : true);
-  const long long my_id = use_ids ? own.ids[g] : 0;
-  float best = INFINITY, best_own = INFINITY;
-  int bi = 0, first = INT_MAX, count = 0;
-  for (int base = 0; base < oth.n; base += SM_TILE) {
-    const int cnt = min(SM_TILE, oth.n - base);
-    __syncthreads();  // the previous tile has been read
-    if (tid < cnt) {
-      const size_t q = (size_t)b * oth.n + base + tid;
-      t_xy[tid] = sm_coords(oth, 1 - SIDE, q);
-      t_flag[tid] = (oth.visible[q] ? SM_VISIBLE : 0) | ((oth.valid3d ? oth.valid3d[q] != 0 : true) ? SM_VALID3D : 0);
-      t_id[tid] = use_ids ? oth.ids[q] : 0;
-    }
-    __syncthreads();
-    for (int e = lane; e < cnt; e += SM_LANES) {
-      const float4 r = SIDE == 0 ? me : t_xy[e];
-      const float4 c = SIDE == 0 ? t_xy[e] : me;
-      const unsigned char f = t_flag[e];
-      const float dx0 = r.x - c.x, dy0 = r.y - c.y;
-      const float dx1 = r.z - c.z, dy1 = r.w - c.w;
-      const float d0 = dx0 * dx0 + dy0 * dy0, d1 = dx1 * dx1 + dy1 * dy1;
-      const float d = (vis && (f & SM_VISIBLE)) ? fmaxf(d0, d1) : INFINITY;
-      if (d < best) { best = d; bi = base + e; }
-      best_own = fminf(best_own, SIDE == 0 ? d0 : d1);
-      if (id_ok && (f & SM_VALID3D) && t_id[e] == my_id) {
-        first = min(first, base + e);
-        ++count;
-      }
+// The seeding by identity as gt_sweep's further accumulator: the first key point of the other side with the owned point's
+// id, both of them valid 3D points, and how many there are.  Without ids nothing is found.
+struct SmSeeds {
+  long long* t_id;  // [GTS_TILE] in LDS
+  int* w_first;
+  int* w_count;
+  bool use_ids, id_ok;
+  long long my_id;
+  int first, count;
+  __device__ __forceinline__ void begin(const SmSide& own, size_t g, unsigned char mine) {
+    use_ids = own.ids != nullptr;
+    id_ok = use_ids && (mine & SM_VALID3D);
+    my_id = use_ids ? own.ids[g] : 0;
+    first = INT_MAX;
+    count = 0;
+  }
+  __device__ __forceinline__ void stage(const SmSide& oth, size_t q, int slot) { t_id[slot] = use_ids ? oth.ids[q] : 0; }
+  __device__ __forceinline__ void visit(unsigned char f, int slot, int index) {
+    if (id_ok && (f & SM_VALID3D) && t_id[slot] == my_id) {
+      first = min(first, index);
+      ++count;
     }
   }
-  // the SM_LANES lanes of a key point: (distance, index) with the lower index winning equal distances
-#pragma unroll
-  for (int o = SM_LANES / 2; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, SM_LANES);
-    const int oi = __shfl_xor(bi, o, SM_LANES);
-    if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    best_own = fminf(best_own, __shfl_xor(best_own, o, SM_LANES));
-    first = min(first, __shfl_xor(first, o, SM_LANES));
-    count += __shfl_xor(count, o, SM_LANES);
+  __device__ __forceinline__ void reduce(int o) {
+    first = min(first, __shfl_xor(first, o, GTS_LANES));
+    count += __shfl_xor(count, o, GTS_LANES);
   }
-  if (live && lane == 0) {
-    w_best[g] = best; w_arg[g] = bi; w_own[g] = best_own; w_first[g] = first; w_count[g] = count;
-  }
+  __device__ __forceinline__ void store(size_t w) { w_first[w] = first; w_count[w] = count; }
+};
+
+__global__ __launch_bounds__(GTS_THREADS) void sm_sweep_kernel(SmSide s0, SmSide s1, int row_blocks, size_t side1, GtsOut w,
+                                                               int* __restrict__ w_first, int* __restrict__ w_count) {
+  __shared__ __attribute__((aligned(16))) GtsTile tile;  // with the ids 256 x (16 + 1 + 8) = 6400 bytes of static LDS
+  __shared__ long long t_id[GTS_TILE];
+  SmSeeds seeds{t_id, w_first, w_count};
+  gt_sweep_pair(SmLabeller{}, s0, s1, row_blocks, side1, tile, w, seeds);
 }
 
-__global__ __launch_bounds__(SM_THREADS) void sm_sweep_kernel(SmSide s0, SmSide s1, int row_blocks, size_t side1,
-                                                              float* __restrict__ w_best, int* __restrict__ w_arg,
-                                                              float* __restrict__ w_own, int* __restrict__ w_first,
-                                                              int* __restrict__ w_count) {
-  // one tile for both instantiations: 256 x (16 + 8 + 1) = 6400 bytes of static LDS
-  __shared__ __attribute__((aligned(16))) float4 t_xy[SM_TILE];
-  __shared__ long long t_id[SM_TILE];
-  __shared__ unsigned char t_flag[SM_TILE];
-  const int b = blockIdx.y;
-  if ((int)blockIdx.x < row_blocks)
-    sm_sweep<0>(s0, s1, blockIdx.x, b, t_xy, t_id, t_flag, w_best, w_arg, w_own, w_first, w_count);
-  else
-    sm_sweep<1>(s1, s0, blockIdx.x - row_blocks, b, t_xy, t_id, t_flag, w_best + side1, w_arg + side1, w_own + side1, w_first + side1,
-                w_count + side1);
-}
-
-// Steps 2-5 per key point.  grid (ceil((M + N) / SM_THREADS), B): threads 0..M-1 of a pair are its rows, then its columns.
+// Steps 2-5 per key point.  grid (ceil((M + N) / GTS_THREADS), B): threads 0..M-1 of a pair are its rows, then its columns.
 // extra_positives is zeroed by the launcher.
-__global__ __launch_bounds__(SM_THREADS) void sm_finish_kernel(
+__global__ __launch_bounds__(GTS_THREADS) void sm_finish_kernel(
     SmSide s0, SmSide s1, size_t side1, const float* __restrict__ w_best, const int* __restrict__ w_arg,
     const float* __restrict__ w_own, const int* __restrict__ w_first, const int* __restrict__ w_count,
     unsigned char* __restrict__ w_state, int* __restrict__ w_pos0, int has_pos, float pos2, int has_neg, float neg2,
     long long* __restrict__ m0_out, long long* __restrict__ m1_out, unsigned char* __restrict__ masks0,
     unsigned char* __restrict__ masks1, int* __restrict__ positive0, int* __restrict__ extra_positives) {
   const int b = blockIdx.y, M = s0.n, N = s1.n;
-  const int t = blockIdx.x * SM_THREADS + threadIdx.x;
+  const int t = blockIdx.x * GTS_THREADS + threadIdx.x;
   if (t >= M + N) return;
   const int side = t >= M, k = side ? t - M : t;
   const SmSide& me = side ? s1 : s0;
@@ -156,7 +102,7 @@ __global__ __launch_bounds__(SM_THREADS) void sm_finish_kernel(
   int p = -1;  // the distance positive
   if (has_pos) {
     const int a = w_arg[w];
-    if (w_best[w] < pos2 && w_arg[wo + a] == k) p = a;
+    if (gt_mutual_positive(w_best[w] < pos2, w_arg + wo, a, k)) p = a;
   }
   if (m == -2 && p >= 0) m = p;
   const bool negative = has_neg && w_own[w] > neg2 && me.valid[g] != 0;
@@ -179,8 +125,7 @@ __global__ __launch_bounds__(SM_THREADS) void sm_finish_kernel(
     int set = seeds;
     if (p >= 0) {
       const size_t q = (size_t)b * N + p;
-      const bool in_s = me.ids && me.ids[g] == ot.ids[q] && (me.valid3d ? me.valid3d[g] != 0 : true) &&
-                        (ot.valid3d ? ot.valid3d[q] != 0 : true);
+      const bool in_s = me.ids && me.ids[g] == ot.ids[q] && sm_valid3d(me, g) && sm_valid3d(ot, q);
       set += in_s ? 0 : 1;
     }
     if (set > 1) atomicAdd(extra_positives + b, set - 1);
@@ -195,8 +140,8 @@ __device__ __forceinline__ void sm_epi(const SmSide& own, const SmSide& oth, int
                                        const unsigned char* __restrict__ st_oth,
                                        const float* __restrict__ Fm, float epi_th, long long* __restrict__ m_out,
                                        unsigned char* __restrict__ masks) {
-  const int tid = threadIdx.x, lane = tid % SM_LANES;
-  const int k = blk * SM_OWN + tid / SM_LANES;
+  const int tid = threadIdx.x, lane = tid % GTS_LANES;
+  const int k = blk * GTS_OWN + tid / GTS_LANES;
   const bool live = k < own.n;
   const size_t g = (size_t)b * own.n + (live ? k : 0);
   const float mx = own.kp[2 * g], my = own.kp[2 * g + 1];
@@ -205,8 +150,8 @@ __device__ __forceinline__ void sm_epi(const SmSide& own, const SmSide& oth, int
 #pragma unroll
   for (int q = 0; q < 9; ++q) Ff[q] = Fm[b * 9 + q];
   float best = INFINITY;
-  for (int base = 0; base < oth.n; base += SM_TILE) {
-    const int cnt = min(SM_TILE, oth.n - base);
+  for (int base = 0; base < oth.n; base += GTS_TILE) {
+    const int cnt = min(GTS_TILE, oth.n - base);
     __syncthreads();
     if (tid < cnt) {
       const size_t q = (size_t)b * oth.n + base + tid;
@@ -215,14 +160,14 @@ __device__ __forceinline__ void sm_epi(const SmSide& own, const SmSide& oth, int
     }
     __syncthreads();
     if (ign)
-      for (int e = lane; e < cnt; e += SM_LANES)
+      for (int e = lane; e < cnt; e += GTS_LANES)
         if (t_ign[e]) {
           const float2 o = t_xy[e];
-          best = fminf(best, SIDE == 0 ? sm_epi_dist(Ff, mx, my, o.x, o.y) : sm_epi_dist(Ff, o.x, o.y, mx, my));
+          best = fminf(best, SIDE == 0 ? gt_epi_dist(Ff, mx, my, o.x, o.y) : gt_epi_dist(Ff, o.x, o.y, mx, my));
         }
   }
 #pragma unroll
-  for (int o = SM_LANES / 2; o > 0; o >>= 1) best = fminf(best, __shfl_xor(best, o, SM_LANES));
+  for (int o = GTS_LANES / 2; o > 0; o >>= 1) best = fminf(best, __shfl_xor(best, o, GTS_LANES));
   if (live && lane == 0) {
     const bool exclude = best > epi_th;
     if (masks) masks[(size_t)b * 4 * own.n + (size_t)3 * own.n + k] = exclude;
@@ -230,15 +175,15 @@ __device__ __forceinline__ void sm_epi(const SmSide& own, const SmSide& oth, int
   }
 }
 
-__global__ __launch_bounds__(SM_THREADS) void sm_epi_kernel(SmSide s0, SmSide s1, int row_blocks, size_t side1,
+__global__ __launch_bounds__(GTS_THREADS) void sm_epi_kernel(SmSide s0, SmSide s1, int row_blocks, size_t side1,
                                                             const unsigned char* __restrict__ w_state,
                                                             const float* __restrict__ Fm, float epi_th,
                                                             long long* __restrict__ m0_out,
                                                             long long* __restrict__ m1_out,
                                                             unsigned char* __restrict__ masks0,
                                                             unsigned char* __restrict__ masks1) {
-  __shared__ float2 t_xy[SM_TILE];  // one tile for both instantiations: 256 x (8 + 1) = 2304 bytes
-  __shared__ unsigned char t_ign[SM_TILE];
+  __shared__ float2 t_xy[GTS_TILE];  // one tile for both instantiations: 256 x (8 + 1) = 2304 bytes
+  __shared__ unsigned char t_ign[GTS_TILE];
   const int b = blockIdx.y;
   if ((int)blockIdx.x < row_blocks)
     sm_epi<0>(s0, s1, blockIdx.x, b, t_xy, t_ign, w_state, w_state + side1, Fm, epi_th, m0_out, masks0);
@@ -248,30 +193,29 @@ __global__ __launch_bounds__(SM_THREADS) void sm_epi_kernel(SmSide s0, SmSide s1
 
 // Step 7: plain writes, one thread per element, blockIdx = (column block, row, pair).  epi_mode 0: no penalty;
 // 1: epi > epi_val on the unmasked epi (neg_th); 2: epi +inf outside ignore x ignore of the state before step 6 (epi_th).
-__global__ __launch_bounds__(SM_THREADS) void sm_dense_kernel(SmSide s0, SmSide s1, size_t side1,
+__global__ __launch_bounds__(GTS_THREADS) void sm_dense_kernel(SmSide s0, SmSide s1, size_t side1,
                                                               const unsigned char* __restrict__ w_state,
                                                               const int* __restrict__ w_pos0,
                                                               const float* __restrict__ Fm, float epi_val, int epi_mode,
                                                               int has_pos, float pos2,
                                                               unsigned char* __restrict__ assignment,
                                                               float* __restrict__ reward) {
-  const int j = blockIdx.x * SM_THREADS + threadIdx.x, i = blockIdx.y, b = blockIdx.z;
+  const int j = blockIdx.x * GTS_THREADS + threadIdx.x, i = blockIdx.y, b = blockIdx.z;
   const int M = s0.n, N = s1.n;
   if (j >= N) return;
   const size_t r = (size_t)b * M + i, c = (size_t)b * N + j;
   const size_t o = r * N + j;
   bool pos = w_pos0[r] == j;
   if (s0.ids)
-    pos = pos || (s0.ids[r] == s1.ids[c] && (s0.valid3d ? s0.valid3d[r] != 0 : true) &&
-                  (s1.valid3d ? s1.valid3d[c] != 0 : true));
+    pos = pos || (s0.ids[r] == s1.ids[c] && sm_valid3d(s0, r) && sm_valid3d(s1, c));
   if (assignment) assignment[o] = pos;
   if (!reward) return;
   float gain = pos ? 1.f : 0.f;
   if (has_pos) {
-    const float dx0 = s0.proj[2 * r] - s1.kp[2 * c], dy0 = s0.proj[2 * r + 1] - s1.kp[2 * c + 1];
-    const float dx1 = s0.kp[2 * r] - s1.proj[2 * c], dy1 = s0.kp[2 * r + 1] - s1.proj[2 * c + 1];
+    float d0, d1;
+    gt_pair_dists(gt_coords(s0.kp, s0.proj, 0, r), gt_coords(s1.kp, s1.proj, 1, c), d0, d1);
     const bool vis = s0.visible[r] && s1.visible[c];
-    const float d = vis ? fmaxf(dx0 * dx0 + dy0 * dy0, dx1 * dx1 + dy1 * dy1) : INFINITY;
+    const float d = vis ? fmaxf(d0, d1) : INFINITY;
     gain = fmaxf(d < pos2 ? 1.f : 0.f, gain);
   }
   float penalty = 0.f;
@@ -279,7 +223,7 @@ __global__ __launch_bounds__(SM_THREADS) void sm_dense_kernel(SmSide s0, SmSide 
     float Ff[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) Ff[q] = Fm[b * 9 + q];
-    float e = sm_epi_dist(Ff, s0.kp[2 * r], s0.kp[2 * r + 1], s1.kp[2 * c], s1.kp[2 * c + 1]);
+    float e = gt_epi_dist(Ff, s0.kp[2 * r], s0.kp[2 * r + 1], s1.kp[2 * c], s1.kp[2 * c + 1]);
     if (epi_mode == 2 && !((w_state[r] & SM_IGNORE) && (w_state[side1 + c] & SM_IGNORE))) e = INFINITY;
     penalty = e > epi_val ? 1.f : 0.f;
   }
@@ -303,17 +247,8 @@ extern "C" int gfc_gt_matches_sparse_map(const float* kp0, const float* kp1, con
                                          float* reward, void* workspace, size_t workspace_bytes, void* stream) {
   if (!sm_sizes_ok(B, M, N)) return GFC_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  if (M == 0 || N == 0) {  // gt_generation.py:282-314: every key point of the other side unmatched, nothing positive
-    if ((M > 0 && !matches0) || (N > 0 && !matches1)) return GFC_ERR_INVALID;
-    hipError_t e = hipSuccess;
-    if (M > 0) e = hipMemsetAsync(matches0, 0xFF, (size_t)B * M * sizeof(int64_t), s);
-    if (e == hipSuccess && N > 0) e = hipMemsetAsync(matches1, 0xFF, (size_t)B * N * sizeof(int64_t), s);
-    if (e == hipSuccess && M > 0 && positive0) e = hipMemsetAsync(positive0, 0xFF, (size_t)B * M * sizeof(int32_t), s);
-    if (e == hipSuccess && M > 0 && masks0) e = hipMemsetAsync(masks0, 0, (size_t)B * 4 * M, s);
-    if (e == hipSuccess && N > 0 && masks1) e = hipMemsetAsync(masks1, 0, (size_t)B * 4 * N, s);
-    if (e == hipSuccess && extra_positives) e = hipMemsetAsync(extra_positives, 0, (size_t)B * sizeof(int32_t), s);
-    return e == hipSuccess ? GFC_OK : GFC_ERR_LAUNCH;
-  }
+  if (M == 0 || N == 0)
+    return gt_empty_side(B, M, N, matches0, matches1, positive0, nullptr, nullptr, masks0, masks1, extra_positives, s);
   if (!kp0 || !kp1 || !proj_0to1 || !proj_1to0 || !visible0 || !visible1 || !valid0 || !valid1 || !matches0 || !matches1)
     return GFC_ERR_INVALID;
   if ((ids0 == nullptr) != (ids1 == nullptr)) return GFC_ERR_INVALID;
@@ -323,9 +258,7 @@ extern "C" int gfc_gt_matches_sparse_map(const float* kp0, const float* kp1, con
   const SmWs L = sm_ws(B, M, N);
   if (!workspace || workspace_bytes < L.total) return GFC_ERR_WORKSPACE;
   char* ws = (char*)workspace;
-  float* w_best = (float*)(ws + L.best);
-  int* w_arg = (int*)(ws + L.arg);
-  float* w_own = (float*)(ws + L.own);
+  const GtsOut w = gts_out(workspace, L.sweep);
   int* w_first = (int*)(ws + L.first);
   int* w_count = (int*)(ws + L.count);
   unsigned char* w_state = (unsigned char*)(ws + L.state);
@@ -335,23 +268,23 @@ extern "C" int gfc_gt_matches_sparse_map(const float* kp0, const float* kp1, con
   const SmSide s1{kp1, proj_1to0, visible1, valid1, (const long long*)ids1, ids1 ? valid3d1 : nullptr, N};
   // the reference squares the Python double and compares the float32 tensor with it: the double square, rounded once
   const float pos2 = (float)(pos_th * pos_th), neg2 = (float)(neg_th * neg_th);
-  const int row_blocks = (M + SM_OWN - 1) / SM_OWN, col_blocks = (N + SM_OWN - 1) / SM_OWN;
+  const int row_blocks = gts_blocks(M), col_blocks = gts_blocks(N);
   if (extra_positives && hipMemsetAsync(extra_positives, 0, (size_t)B * sizeof(int32_t), s) != hipSuccess)
     return GFC_ERR_LAUNCH;
-  hipLaunchKernelGGL(sm_sweep_kernel, dim3(row_blocks + col_blocks, B), dim3(SM_THREADS), 0, s, s0, s1, row_blocks,
-                     side1, w_best, w_arg, w_own, w_first, w_count);
+  hipLaunchKernelGGL(sm_sweep_kernel, dim3(row_blocks + col_blocks, B), dim3(GTS_THREADS), 0, s, s0, s1, row_blocks,
+                     side1, w, w_first, w_count);
   GFC_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sm_finish_kernel, dim3((M + N + SM_THREADS - 1) / SM_THREADS, B), dim3(SM_THREADS), 0, s, s0, s1,
-                     side1, w_best, w_arg, w_own, w_first, w_count, w_state, w_pos0, has_pos, pos2, has_neg, neg2,
+  hipLaunchKernelGGL(sm_finish_kernel, dim3((M + N + GTS_THREADS - 1) / GTS_THREADS, B), dim3(GTS_THREADS), 0, s, s0, s1,
+                     side1, w.best, w.arg, w.own, w_first, w_count, w_state, w_pos0, has_pos, pos2, has_neg, neg2,
                      (long long*)matches0, (long long*)matches1, masks0, masks1, positive0, extra_positives);
   GFC_LAUNCH_CHECK();
   if (has_epi) {
-    hipLaunchKernelGGL(sm_epi_kernel, dim3(row_blocks + col_blocks, B), dim3(SM_THREADS), 0, s, s0, s1, row_blocks,
+    hipLaunchKernelGGL(sm_epi_kernel, dim3(row_blocks + col_blocks, B), dim3(GTS_THREADS), 0, s, s0, s1, row_blocks,
                        side1, w_state, F, (float)epi_th, (long long*)matches0, (long long*)matches1, masks0, masks1);
     GFC_LAUNCH_CHECK();
   }
   if (assignment || reward) {
-    hipLaunchKernelGGL(sm_dense_kernel, dim3((N + SM_THREADS - 1) / SM_THREADS, M, B), dim3(SM_THREADS), 0, s, s0, s1,
+    hipLaunchKernelGGL(sm_dense_kernel, dim3((N + GTS_THREADS - 1) / GTS_THREADS, M, B), dim3(GTS_THREADS), 0, s, s0, s1,
                        side1, w_state, w_pos0, F, (float)(has_epi ? epi_th : neg_th), epi_mode, has_pos, pos2,
                        assignment, reward);
     GFC_LAUNCH_CHECK();

@@ -29,6 +29,24 @@ def fundamental_matrix(cam0, cam1, T01):
     return (K(cam1).inverse().transpose(-1, -2) @ (skew @ R) @ K(cam0).inverse()).contiguous()
 
 
+def mask(v, b, k, dev):
+    """Any mask of a side as contiguous bool [B,K] on the device."""
+    return v.to(device=dev).reshape(b, k).ne(0).contiguous()
+
+
+def project_given_depth(k, d, valid, ci, mi, cj, mj, T, project=True):
+    """Key points k [B,K,2] of view i whose depth d is GIVEN (cached, or from a sparse map) into view j: (depth float32
+    [B,K], valid bool, the projection, visible = valid depth and a valid projection).  project False is the reference's
+    early return for an empty side: nothing is projected and nothing is visible."""
+    dev, (b, cnt) = k.device, k.shape[:2]
+    d, valid = d.to(device=dev, dtype=torch.float32).reshape(b, cnt).contiguous(), mask(valid, b, cnt, dev)
+    proj = torch.empty((b, cnt, 2), dtype=torch.float32, device=dev)
+    vis = torch.zeros((b, cnt), dtype=torch.bool, device=dev)
+    if project:
+        nat.call("gfc_gt_project_depth", k, d, valid, ci, mi, cj, mj, T, b, cnt, proj, vis, device=dev)
+    return d, valid, proj, vis
+
+
 def gt_matches_from_pose_depth(kp0, kp1, data, pos_th=3, neg_th=5, epi_th=None, cc_th=None, dense=True, **kw):
     """The reference's function for batched device key points kp0 [B,M,2], kp1 [B,N,2] and its data dict (`view0/1` =
     {camera, depth}, `T_0to1`); kw: `depth_keypoints0/1` + `valid_depth_keypoints0/1` (cached depth), or
@@ -44,21 +62,12 @@ def gt_matches_from_pose_depth(kp0, kp1, data, pos_th=3, neg_th=5, epi_th=None, 
     T01, T10 = geometry.pose_args(data["T_0to1"], b, dev)
     k0, k1 = kp0.float().contiguous(), kp1.float().contiguous()
 
-    def mask(v, k):
-        return v.to(device=dev).reshape(b, k).ne(0).contiguous()
-
     if "depth_keypoints0" in kw and "depth_keypoints1" in kw:
-        def given(k, d, valid, ci, mi, cj, mj, T, cnt):
-            d, valid = d.to(device=dev, dtype=torch.float32).reshape(b, cnt).contiguous(), mask(valid, cnt)
-            proj = torch.empty((b, cnt, 2), dtype=torch.float32, device=dev)
-            vis = torch.empty((b, cnt), dtype=torch.bool, device=dev)
-            nat.call("gfc_gt_project_depth", k, d, valid, ci, mi, cj, mj, T, b, cnt, proj, vis, device=dev)
-            return d, valid, proj, vis
-
-        d0, valid0, p01, vis0 = given(k0, kw["depth_keypoints0"], kw["valid_depth_keypoints0"], cam0, model0, cam1,
-                                      model1, T01, m)
-        d1, valid1, p10, vis1 = given(k1, kw["depth_keypoints1"], kw["valid_depth_keypoints1"], cam1, model1, cam0,
-                                      model0, T10, n)
+        both = m > 0 and n > 0
+        d0, valid0, p01, vis0 = project_given_depth(k0, kw["depth_keypoints0"], kw["valid_depth_keypoints0"], cam0,
+                                                    model0, cam1, model1, T01, both)
+        d1, valid1, p10, vis1 = project_given_depth(k1, kw["depth_keypoints1"], kw["valid_depth_keypoints1"], cam1,
+                                                    model1, cam0, model0, T10, both)
     else:
         depth0, depth1 = data["view0"].get("depth"), data["view1"].get("depth")
         assert depth0 is not None and depth1 is not None
@@ -67,7 +76,7 @@ def gt_matches_from_pose_depth(kp0, kp1, data, pos_th=3, neg_th=5, epi_th=None, 
         d1, valid1, p10, vis1 = eval_utils.pose_project(k1, depth1, data["view1"]["camera"], data["view0"]["camera"],
                                                         geometry.Pose(T10))
         if "valid_depth_keypoints0" in kw:  # visible = valid & a valid projection: the AND carries over
-            g0, g1 = mask(kw["valid_depth_keypoints0"], m), mask(kw["valid_depth_keypoints1"], n)
+            g0, g1 = mask(kw["valid_depth_keypoints0"], b, m, dev), mask(kw["valid_depth_keypoints1"], b, n, dev)
             valid0, valid1, vis0, vis1 = valid0 & g0, valid1 & g1, vis0 & g0, vis1 & g1
     m0 = torch.empty((b, m), dtype=torch.long, device=dev)
     m1 = torch.empty((b, n), dtype=torch.long, device=dev)

@@ -21,7 +21,7 @@ import torch
 from . import _native as nat
 from . import geometry
 from .base_model import BaseModel
-from .depth_matcher import fundamental_matrix
+from .depth_matcher import fundamental_matrix, mask, project_given_depth
 
 logger = logging.getLogger(__name__)
 MASK_KEYS = ("mask_pos_3d_map", "mask_pos_reproj", "mask_neg_reproj", "mask_neg_epi")  # the rows of masks0 / masks1
@@ -44,24 +44,14 @@ def gt_matches_from_sparse_map(kp0, kp1, data, depth0, valid0, depth1, valid1, i
     T01, T10 = geometry.pose_args(data["T_0to1"], b, dev)
     k0, k1 = kp0.float().contiguous(), kp1.float().contiguous()
 
-    def mask(v, k):
-        return v.to(device=dev).reshape(b, k).ne(0).contiguous()
-
-    def given(k, d, valid, ci, mi, cj, mj, T, cnt):
-        d32, valid = d.to(device=dev, dtype=torch.float32).reshape(b, cnt).contiguous(), mask(valid, cnt)
-        proj = torch.empty((b, cnt, 2), dtype=torch.float32, device=dev)
-        vis = torch.zeros((b, cnt), dtype=torch.bool, device=dev)
-        if m > 0 and n > 0:  # the early return projects nothing: nothing visible
-            nat.call("gfc_gt_project_depth", k, d32, valid, ci, mi, cj, mj, T, b, cnt, proj, vis, device=dev)
-        return valid, proj, vis
-
-    valid0, p01, vis0 = given(k0, depth0, valid0, cam0, model0, cam1, model1, T01, m)
-    valid1, p10, vis1 = given(k1, depth1, valid1, cam1, model1, cam0, model0, T10, n)
+    both = m > 0 and n > 0  # the early return projects nothing: nothing visible
+    _, valid0, p01, vis0 = project_given_depth(k0, depth0, valid0, cam0, model0, cam1, model1, T01, both)
+    _, valid1, p10, vis1 = project_given_depth(k1, depth1, valid1, cam1, model1, cam0, model0, T10, both)
     seeded = ids0 is not None
     if seeded:
         ids0 = ids0.to(device=dev, dtype=torch.long).reshape(b, m).contiguous()
         ids1 = ids1.to(device=dev, dtype=torch.long).reshape(b, n).contiguous()
-        valid3d0, valid3d1 = mask(valid3d0, m), mask(valid3d1, n)
+        valid3d0, valid3d1 = mask(valid3d0, b, m, dev), mask(valid3d1, b, n, dev)
     else:
         valid3d0 = valid3d1 = None
     m0 = torch.empty((b, m), dtype=torch.long, device=dev)

@@ -250,6 +250,67 @@ def test_without_ids_equals_the_one_workgroup_kernel(epi):
     assert (m0 > -1).any() and (m0 == -1).any() and (m0 == -2).any()
 
 
+def run_depth(case):
+    """gfc_gt_matches_depth (one workgroup per pair) at pos_th 3, neg_th 5, no epi_th -> CPU tensors."""
+    c = {k: v.cuda().contiguous() for k, v in case.items()}
+    b, m, n = case["kp0"].shape[0], case["kp0"].shape[1], case["kp1"].shape[1]
+    out = {"matches0": torch.full((b, m), 7, dtype=torch.long, device="cuda"),
+           "matches1": torch.full((b, n), 7, dtype=torch.long, device="cuda"),
+           "positive0": torch.full((b, m), 7, dtype=torch.int32, device="cuda")}
+    nat.call("gfc_gt_matches_depth", c["kp0"], c["kp1"], c["p01"], c["p10"], c["vis0"], c["vis1"], c["valid0"],
+             c["valid1"], None, b, m, n, 3.0, 5.0, -1.0, out["matches0"], out["matches1"], out["positive0"], None, None,
+             device=c["kp0"].device)
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def run_roma(case):
+    """gfc_gt_matches_roma on the projections of an entry_case: every key point valid with certainty 1 and cycle error 0,
+    pos_th 3, neg_th 5, none of the four optional thresholds -> CPU tensors."""
+    c = {k: v.cuda().contiguous() for k, v in case.items()}
+    b, m, n = case["kp0"].shape[0], case["kp0"].shape[1], case["kp1"].shape[1]
+    dev = c["kp0"].device
+    side = lambda k, fill, dtype: torch.full((b, k), fill, dtype=dtype, device=dev)  # noqa: E731
+    out = {"matches0": side(m, 7, torch.long), "matches1": side(n, 7, torch.long)}
+    nbytes = nat.call("gfc_gt_matches_roma_workspace_bytes", b, m, n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    nat.call("gfc_gt_matches_roma", c["kp0"], c["kp1"], c["p01"], c["p10"], side(m, 1.0, torch.float32),
+             side(n, 1.0, torch.float32), side(m, 0.0, torch.float32), side(n, 0.0, torch.float32),
+             side(m, 1, torch.uint8), side(n, 1, torch.uint8), b, m, n, 3.0, 5.0, -1.0, -1.0, -1.0, -1.0, out["matches0"],
+             out["matches1"], side(m, 7.0, torch.float32), side(n, 7.0, torch.float32), None, None, None, None, ws, nbytes,
+             device=dev)
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def test_the_three_labellers_agree_where_their_rules_coincide():
+    """No ids, pos_th 3 <= neg_th 5, no th_epi: the split sparse-map labeller and the one-workgroup depth labeller state
+    one rule, and with every key point visible and valid the RoMa labeller (certainty 1, cycle error 0, no optional
+    threshold) states it too.  The three evaluate the same float32 expressions, so the labels are EQUAL.  Shapes one off
+    the 16 owned key points, the tile of 256 and the stride of 16 x 256, on either side."""
+    cases = [sr.entry_case(seed, b, m, n) for seed, b, m, n in
+             ((11, 2, 17, 255), (12, 2, 257, 16), (13, 1, 300, 513), (14, 1, 1, 1), (15, 2, 15, 4097))]
+    ones = [{**c, **{k: torch.ones_like(c[k]) for k in ("vis0", "vis1", "valid0", "valid1")}} for c in cases]
+    for name, group in (("own", cases), ("all-visible", ones)):  # before any kernel's answer is looked at
+        kinds = {"0": set(), "1": set()}
+        for c in group:
+            for i in range(c["kp0"].shape[0]):
+                r = sr.labels_of(c, i, 3.0, 5.0, None, use_ids=False)
+                assert not bool(r["undecided0"].any()) and not bool(r["undecided1"].any()), ("bad input", name)
+                for s in "01":
+                    kinds[s] |= set(r["matches" + s].clamp(max=0).tolist())
+        print(name, kinds)
+        assert kinds["0"] == kinds["1"] == {0, -1, -2}, ("bad input: a label kind is missing", name, kinds)
+    for c, o in zip(cases, ones):
+        split, one_wg = run_entry(c, 3.0, 5.0, None, use_ids=False), run_depth(c)
+        for k in ("matches0", "matches1", "positive0"):
+            assert torch.equal(split[k], one_wg[k]), (c["kp0"].shape, c["kp1"].shape, k)
+        split, one_wg, roma = run_entry(o, 3.0, 5.0, None, use_ids=False), run_depth(o), run_roma(o)
+        for k in ("matches0", "matches1"):
+            assert torch.equal(split[k], one_wg[k]) and torch.equal(split[k], roma[k]), (c["kp0"].shape, c["kp1"].shape, k)
+        assert torch.equal(split["positive0"], one_wg["positive0"])
+
+
 def test_a_pair_alone_equals_the_pair_in_a_batch_of_six():
     case = sr.entry_case(9, 6, 300, 257, twins=True)
     both = run_entry(case, 3.0, 5.0, 5.0, dense=True)

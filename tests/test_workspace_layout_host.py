@@ -102,6 +102,19 @@ SIZES = {
         ((7, 2048, 2048), 227542016), ((0, 4, 4), 0), ((1, 0, 4), 0), ((1, 4, 0), 0), ((-1, 4, 4), 0),
         ((1, 2796202, 1), 0),
     ],
+    # the two split ground-truth labellers; recorded from a build of the commit before they shared the head of their
+    # layouts (csrc/gt_sweep.h; source hash dd50ec4fbcab).  Slots of B (M + N) * 4, B (M + N) and B M * 4 bytes that are
+    # no multiple of 256, the evaluation size, an empty side, and every argument error (B, M, N <= 65535)
+    "gfc_gt_matches_sparse_map_workspace_bytes": [
+        ((1, 1, 1), 1792), ((2, 17, 255), 12544), ((3, 257, 16), 20992), ((2, 65, 130), 10240),
+        ((32, 2048, 2048), 3014656), ((1, 65535, 65535), 3014656), ((1, 0, 4), 0), ((1, 4, 0), 0), ((0, 4, 4), 0),
+        ((-1, 4, 4), 0), ((1, -1, 4), 0), ((1, 65536, 4), 0), ((1, 4, 65536), 0), ((65536, 4, 4), 0),
+    ],
+    "gfc_gt_matches_roma_workspace_bytes": [
+        ((1, 1, 1), 1280), ((2, 17, 255), 7936), ((3, 257, 16), 14336), ((2, 65, 130), 6656),
+        ((32, 2048, 2048), 1966080), ((1, 65535, 65535), 1966080), ((1, 0, 4), 0), ((1, 4, 0), 0), ((0, 4, 4), 0),
+        ((-1, 4, 4), 0), ((1, -1, 4), 0), ((1, 65536, 4), 0), ((1, 4, 65536), 0), ((65536, 4, 4), 0),
+    ],
 }
 RAGGED_SIZES = [
     (([65], [130]), 3195392),
@@ -222,6 +235,14 @@ def _short_calls():
         f(1), f(2), f(3), B, M, N, f(4), f(5), ws, None))
     calls["lg_filter_matches"] = (B * (M + N) * 8, lambda ws: lib.gfc_lg_filter_matches(
         f(1), B, M, N, 0.1, f(2), f(3), f(4), f(5), f(6), ws, None))
+    calls["gt_matches_sparse_map"] = (
+        lib.gfc_gt_matches_sparse_map_workspace_bytes(B, M, N), lambda ws: lib.gfc_gt_matches_sparse_map(
+            f(1), f(2), f(3), f(4), f(5), f(6), f(7), f(8), f(9), f(10), None, None, f(11), B, M, N, 3.0, 5.0, 5.0, f(12),
+            f(13), None, None, None, None, None, None, f(14), ws, None))
+    calls["gt_matches_roma"] = (
+        lib.gfc_gt_matches_roma_workspace_bytes(B, M, N), lambda ws: lib.gfc_gt_matches_roma(
+            f(1), f(2), f(3), f(4), f(5), f(6), f(7), f(8), f(9), f(10), B, M, N, 3.0, 5.0, 0.05, 2.0, 5e-4, 20.0, f(11),
+            f(12), f(13), f(14), None, None, None, None, f(15), ws, None))
     step = _lg_params()
     calls["lg_adaptive_step"] = (lib.gfc_lg_adaptive_step_workspace_bytes(B, R), lambda ws: lib.gfc_lg_adaptive_step(
         ctypes.byref(step), 0, f(1), f(2), f(3), f(4), R, f(5), f(6), f(7), B, B, N, 0.9, 0.05, 0.95, 1, 1,
@@ -248,7 +269,8 @@ def _short_calls():
 
 
 _SHORT = ["sp_dense_c1", "sp_dense_c3", "sp_select", "sp_nms_select", "disk_nms_select", "disk_instnorm_stats",
-          "eval_homography_ransac", "eval_relative_pose_ransac", "nn_match", "lg_log_assignment", "lg_filter_matches", "lg_adaptive_step"] + [
+          "eval_homography_ransac", "eval_relative_pose_ransac", "nn_match", "lg_log_assignment", "lg_filter_matches", "lg_adaptive_step",
+          "gt_matches_sparse_map", "gt_matches_roma"] + [
     f"lg_{e}_{t}" for t in ("fp32", "fp16") for e in ("layer", "assign", "forward", "forward_packed", "forward_ragged")]
 
 
