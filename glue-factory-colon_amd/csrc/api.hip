@@ -6,6 +6,7 @@
 
 #include "../../include/gfc_amd_cross_attention.h"
 #include "../../include/gfc_amd_layer_scores.h"
+#include "../../include/gfc_amd_ffn_backward.h"
 #include "common.h"
 #include "lg_rowdot.h"
 
@@ -383,7 +384,7 @@ struct LgCrossStored { int B, M, N, chunk; void* sim; size_t sim_bytes; };
 static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, const float* csb,
                          int R, const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
                          size_t ws_bytes, void* stream, const float* x_in = nullptr, gfc_trace* tr = nullptr,
-                         const LgCrossStored* xst = nullptr);
+                         const LgCrossStored* xst = nullptr, float* keep_mid = nullptr, float* keep_ctx = nullptr);
 
 extern "C" int gfc_lg_layer(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, int R,
                             const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
@@ -433,10 +434,13 @@ static bool lg_f16_layer_ok(const gfc_lg_params* p, int l) {
 // x_in (optional): the rows the SELF block reads (QKV operand, first half of the ffn[0] operand, residual); its result
 // and everything after it live in x.  gfc_lg_forward_packed passes the caller's descriptors for layer 0, so that they
 // are never copied into the row buffer.  tr (optional): event pairs around the two attention launches.  xst (optional,
-// fp32 only): the cross block evaluates sim once; still one event pair around all of its launches.
+// fp32 only): the cross block evaluates sim once; still one event pair around all of its launches.  keep_mid / keep_ctx
+// (optional, fp32 only, [R,256]): copies of the rows the cross block reads and of the cross attention's context.
 static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, const float* csb,
                          int R, const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
-                         size_t ws_bytes, void* stream, const float* x_in, gfc_trace* tr, const LgCrossStored* xst) {
+                         size_t ws_bytes, void* stream, const float* x_in, gfc_trace* tr, const LgCrossStored* xst,
+                         float* keep_mid, float* keep_ctx) {
+  if ((keep_mid || keep_ctx) && (!p || p->precision != GFC_LG_FP32)) return GFC_ERR_INVALID;
   if (!p || !x || !cosb || !sinb || !self_p || !cross_p || !ws || R <= 0 || n_problems <= 0 || maxn <= 0)
     return GFC_ERR_INVALID;
   if (l < 0 || l >= p->n_layers) return GFC_ERR_INVALID;
@@ -501,6 +505,8 @@ static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* c
     }
     GFC_TRY(ffn(xs, a1s, P::w(p->s_ffn0_w[l], p->s_ffn0_w16[l]), p->s_ffn0_b[l], p->s_ln_g[l], p->s_ln_b[l],
                 P::w(p->s_ffn3_w[l], p->s_ffn3_w16[l]), p->s_ffn3_b[l], xs));
+    if (keep_mid && hipMemcpyAsync(keep_mid, x, (size_t)R * D * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return GFC_ERR_LAUNCH;
     // ---- cross block (lightglue.py:193-222) ----
     GFC_TRY(proj(x, false, P::w(p->c_qkv_w[l], p->c_qkv_w16[l]), p->c_qkv_b[l], nullptr, nullptr, nullptr, 0, qkv, 512));
     bool stored = false;
@@ -519,6 +525,8 @@ static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* c
       }
     }
     if (!stored) GFC_TRY(attn(qkv, 512, qkv, 512, qkv + 256, 512, cross_p));
+    if (keep_ctx && hipMemcpyAsync(keep_ctx, ctx, (size_t)R * D * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return GFC_ERR_LAUNCH;
     const T* a1c = ctx;
     if (p->c_out_w[l]) {
       GFC_TRY(proj(ctx, true, P::w(p->c_out_w[l], p->c_out_w16[l]), p->c_out_b[l], nullptr, nullptr, nullptr, 0, msg, D));
@@ -551,9 +559,9 @@ extern "C" size_t gfc_lg_layer_pairs_workspace_bytes(int B, int M, int N) {
   return lg_layer_pairs_ws(B, M, N, L) ? L.total : 0;
 }
 
-extern "C" int gfc_lg_layer_pairs(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, int B,
-                                  int M, int N, const int32_t* self_p, const int32_t* cross_p, void* ws, size_t ws_bytes,
-                                  void* stream) {
+static int lg_layer_pairs_impl(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, int B, int M,
+                               int N, const int32_t* self_p, const int32_t* cross_p, float* keep_mid, float* keep_ctx,
+                               void* ws, size_t ws_bytes, void* stream) {
   LgLayerPairsWs L;
   if (!p || !ws || !lg_layer_pairs_ws(B, M, N, L)) return GFC_ERR_INVALID;
   if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
@@ -561,7 +569,21 @@ extern "C" int gfc_lg_layer_pairs(const gfc_lg_params* p, int l, float* x, const
   const LgCrossStored xst = {B, M, N, L.chunk, base + L.sim, L.sim_bytes};
   const bool stored = L.chunk > 0 && p->precision == GFC_LG_FP32 && gfc_knobs().cross_stored != 0;
   return lg_layer_impl(p, l, x, cosb, sinb, nullptr, B * (M + N), self_p, cross_p, 2 * B, M > N ? M : N, base + L.layer,
-                       L.layer_bytes, stream, nullptr, nullptr, stored ? &xst : nullptr);
+                       L.layer_bytes, stream, nullptr, nullptr, stored ? &xst : nullptr, keep_mid, keep_ctx);
+}
+
+extern "C" int gfc_lg_layer_pairs(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, int B,
+                                  int M, int N, const int32_t* self_p, const int32_t* cross_p, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  return lg_layer_pairs_impl(p, l, x, cosb, sinb, B, M, N, self_p, cross_p, nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+// ... with the rows the cross block reads and the cross attention's context kept (include/gfc_amd_ffn_backward.h)
+extern "C" int gfc_lg_layer_pairs_keep(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb,
+                                       int B, int M, int N, const int32_t* self_p, const int32_t* cross_p, float* x_mid,
+                                       float* ctx, void* ws, size_t ws_bytes, void* stream) {
+  if (!x_mid || !ctx) return GFC_ERR_INVALID;
+  return lg_layer_pairs_impl(p, l, x, cosb, sinb, B, M, N, self_p, cross_p, x_mid, ctx, ws, ws_bytes, stream);
 }
 
 // token confidence / matchability logits: out[row] = (sigmoid?)(x[row,:256] . w + b)   (lightglue.py:69-80,290-291)

@@ -82,11 +82,12 @@ __device__ __forceinline__ float gfc_erff(float x) {
 // 5.6e-7 evaluated in fp32; on the GELU: 4.7e-7 absolute over [-9, 9] against 4.5e-7 for an exactly rounded fp32 erf --
 // both are the fp32 rounding of the product): ~14 instructions instead of the ~45 of gfc_erff.  GFC_EXACT_ERF = 1
 // builds the library with gfc_erff (bit-identical to the device library's erff) in the GELU instead.
-__device__ __forceinline__ float gfc_gelu(float x) {
+// gfc_gelu_erf(z): the erf of this build, which the GELU's derivative (lg_ffn_backward.hip) takes its Phi from as well.
+__device__ __forceinline__ float gfc_gelu_erf(float z) {
 #if defined(GFC_EXACT_ERF) && GFC_EXACT_ERF
-  return 0.5f * x * (1.f + gfc_erff(x * 0.70710678118654752440f));
+  return gfc_erff(z);
 #else
-  const float z = x * 0.70710678118654752440f, a = fabsf(z);
+  const float a = fabsf(z);
   const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, a, 1.f));
   float p = fmaf(t, 1.061405429f, -1.453152027f);
   p = fmaf(t, p, 1.421413741f);
@@ -95,8 +96,11 @@ __device__ __forceinline__ float gfc_gelu(float x) {
   p *= t;
   const float e = __builtin_amdgcn_exp2f(-(a * a) * 1.4426950408889634f);  // exp(-z^2)
   const float r = fmaf(-p, e, 1.f);                                         // erf(|z|)
-  return 0.5f * x * (1.f + copysignf(r, z));
+  return copysignf(r, z);
 #endif
+}
+__device__ __forceinline__ float gfc_gelu(float x) {
+  return 0.5f * x * (1.f + gfc_gelu_erf(x * 0.70710678118654752440f));
 }
 
 #define GFC_LAUNCH_CHECK()                                   \

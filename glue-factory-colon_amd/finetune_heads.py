@@ -4,13 +4,16 @@ reference's training loss (`LightGlue.layer_loss_backward`); the trunk, `input_p
 never touched.
 
     python -m glue_factory_colon_amd.finetune_heads --data_dir D --dataset {homographies,posed_images,endomapper}
-        [--params {tokens,heads,all}] [--lr 1e-3] [--optimizer {adam,sgd}] [--clip_grad G] [--epochs E]
+        [--params {tokens,heads,all,output_stage,all+output_stage}] [--lr 1e-3] [--optimizer {adam,sgd}] [--clip_grad G] [--epochs E]
         [--max_steps S] [--pair_batch N] --out FILE
 
 The pairs come from `validate`'s feeders, with its ground-truth options and its grouping: inside a `--pair_batch` chunk
 the pairs of equal (M, N) form one group, which goes through `forward_layers`, `layer_loss` and `layer_loss_backward`
 with grad_total = 1 / (pairs in the chunk); ONE optimizer step is taken per chunk, then `heads_updated()`.  `--params
-tokens` / `heads` hand only those parameters to the optimizer; the others are not passed to it.  `loss/total_deep`,
+tokens` / `heads` hand only those parameters to the optimizer; the others are not passed to it.  `--params output_stage`
+re-fits `to_out` and `ffn` of the last layer's cross block (eight tensors, about 460 k parameters, whose exact gradients
+`layer_loss_backward(output_stage=True)` gives), `all+output_stage` those with the heads and tokens; the rest of the trunk
+stays frozen, and every step also ends with `output_stage_updated()`.  `loss/total_deep`,
 `loss/confidence` and the per-layer table of `validate --layer_report` are printed before and after, and the matcher's
 `state_dict()` is written to `--out`, which `conf.weights = FILE` loads.  No schedules, no checkpoint resume, no mixed
 precision.
@@ -25,6 +28,8 @@ from . import validate
 
 PREFIXES = {"tokens": ("token_confidence.",), "heads": ("log_assignment.",),
             "all": ("token_confidence.", "log_assignment.")}
+# choices that also train the last layer's output stage -> the prefixes of the heads and tokens trained with it
+OUTPUT_STAGE = {"output_stage": (), "all+output_stage": PREFIXES["all"]}
 
 
 class HeadTuner(validate.ValidationPipeline):
@@ -35,8 +40,15 @@ class HeadTuner(validate.ValidationPipeline):
                  clip_grad=None):
         super().__init__(model_conf, pair_batch=pair_batch, device=device, layer_report=True)
         matcher = self.model.matcher
-        self.trained = {n: p for n, p in matcher.named_parameters() if n.startswith(PREFIXES[params])}
-        self.touched = [p for n, p in matcher.named_parameters() if n.startswith(PREFIXES["all"])]
+        self.output_stage = params in OUTPUT_STAGE
+        prefixes = OUTPUT_STAGE[params] if self.output_stage else PREFIXES[params]
+        touched = PREFIXES["all"]
+        if self.output_stage:
+            stage = f"transformers.{int(matcher.conf.n_layers) - 1}.cross_attn."
+            prefixes += (stage + "to_out.", stage + "ffn.")
+            touched += (stage + "to_out.", stage + "ffn.")
+        self.trained = {n: p for n, p in matcher.named_parameters() if n.startswith(prefixes)}
+        self.touched = [p for n, p in matcher.named_parameters() if n.startswith(touched)]
         cls = {"adam": torch.optim.Adam, "sgd": torch.optim.SGD}[optimizer]
         self.optimizer = cls(list(self.trained.values()), lr=lr)
         self.clip_grad = clip_grad
@@ -44,11 +56,15 @@ class HeadTuner(validate.ValidationPipeline):
         self.steps = 0
         self._chunk_pairs = 1
 
+    def _forward_layers(self, stacked):
+        # the rows and context the output stage's backward starts from are kept only while a step needs them
+        return self.model.matcher.forward_layers(stacked, keep_output_stage=self.tuning and self.output_stage)
+
     def _layer_numbers(self, datas, preds, pred, data):
         numbers = super()._layer_numbers(datas, preds, pred, data)
         if self.tuning:
             g = torch.full((len(datas),), 1.0 / self._chunk_pairs, device=self.device)
-            self.model.layer_loss_backward(pred, data, grad_total=g)
+            self.model.layer_loss_backward(pred, data, grad_total=g, output_stage=self.output_stage)
         return numbers
 
     def _run_chunk(self, chunk, first, results, log_file, step, view_key):
@@ -62,6 +78,8 @@ class HeadTuner(validate.ValidationPipeline):
             torch.nn.utils.clip_grad_norm_(list(self.trained.values()), self.clip_grad)
         self.optimizer.step()
         self.model.matcher.heads_updated()
+        if self.output_stage:
+            self.model.matcher.output_stage_updated()
         self.steps += 1
         return n
 
@@ -85,7 +103,7 @@ def _summary(tag, res):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     validate.data_arguments(ap)
-    ap.add_argument("--params", default="all", choices=sorted(PREFIXES))
+    ap.add_argument("--params", default="all", choices=sorted(PREFIXES) + sorted(OUTPUT_STAGE))
     ap.add_argument("--lr", type=float, default=1e-3, help="the reference's default learning rate")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "sgd"])
     ap.add_argument("--clip_grad", type=float, default=None, help="clip the gradient norm of the trained parameters")

@@ -166,6 +166,7 @@ class LightGlue(nn.Module):
         self._graphs = {}  # (b, m, n, device, has scale/ori) -> captured launch sequence + its static buffers
         self._report_host = None  # pinned [GFC_LG_MAX_RAGGED_PAIRS, 4] int32: the adaptive step's report lands here
         self._thresholds_host = None  # (the packed weights they were read with, confidence_thresholds as a list)
+        self._stage = None  # (the packed weights they belong to, the output stage's unfolded fp32 device copies)
         self.are_weights_initialized = False
 
         w = conf.weights
@@ -209,7 +210,7 @@ class LightGlue(nn.Module):
         for k, v in self.__dict__.items():
             if k == "_graphs":
                 new.__dict__[k] = {}
-            elif k in ("_packed", "_report_host", "_thresholds_host"):
+            elif k in ("_packed", "_report_host", "_thresholds_host", "_stage"):
                 new.__dict__[k] = None
             else:
                 new.__dict__[k] = copy.deepcopy(v, memo)
@@ -305,15 +306,7 @@ class LightGlue(nn.Module):
         head, dd = rem // dh, rem % dh
         src = head * (3 * dh) + dd * 3 + s_
         fold = bool(conf.fold_out_proj)
-
-        def ffn0(lin0, out):
-            """ffn[0] weights with `out` (out_proj / to_out) folded into the message half when enabled."""
-            if not fold:
-                return lin0.weight, lin0.bias
-            w0, b0 = lin0.weight.detach().double(), lin0.bias.detach().double()
-            wo, bo = out.weight.detach().double(), out.bias.detach().double()
-            w = torch.cat([w0[:, :d], w0[:, d:] @ wo], 1)
-            return w.float(), (b0 + w0[:, d:] @ bo).float()
+        ffn0 = self._fold_ffn0
 
         for i, layer in enumerate(self.transformers):
             sa, ca = layer.self_attn, layer.cross_attn
@@ -354,6 +347,16 @@ class LightGlue(nn.Module):
         for i, tc in enumerate(self.token_confidence):
             p.token_w[i], p.token_b[i] = head(tc.token[0].weight, flat=True)[0], head(tc.token[0].bias)[0]
         return p, keep, device, heads
+
+    def _fold_ffn0(self, lin0, out):
+        """ffn[0] weights with `out` (out_proj / to_out) folded into the message half when enabled."""
+        if not bool(self.conf.fold_out_proj):
+            return lin0.weight, lin0.bias
+        d = self.conf.descriptor_dim
+        w0, b0 = lin0.weight.detach().double(), lin0.bias.detach().double()
+        wo, bo = out.weight.detach().double(), out.bias.detach().double()
+        w = torch.cat([w0[:, :d], w0[:, d:] @ wo], 1)
+        return w.float(), (b0 + w0[:, d:] @ bo).float()
 
     def _check_ready(self, data=None):
         if data is not None:
@@ -824,7 +827,7 @@ class LightGlue(nn.Module):
         return losses, {k: d[k] for k in KEYS}
 
     # -- every layer kept: the training-mode forward and loss of the reference, forward only ---------------
-    def forward_layers(self, data: dict) -> dict:
+    def forward_layers(self, data: dict, keep_output_stage: bool = False) -> dict:
         """The reference's forward under `model.train()` (lightglue.py:495-498,546-547): full depth, every layer's
         descriptors kept -- `ref_descriptors0` [B,L,M,256], `ref_descriptors1` [B,L,N,256], index l the output of
         transformer l; every other key as `forward` returns it.  LightGlue has no dropout and no batch norm, so this is
@@ -833,7 +836,12 @@ class LightGlue(nn.Module):
         The host drives the layers one by one (`gfc_lg_layer_pairs`: `gfc_lg_layer` with the cross attention
         gfc_lg_forward_packed takes for the batch) and ends with `gfc_lg_assign` on the last head: the launch
         sequence of gfc_lg_forward_packed.  Layer l works in place on slot l of one stack buffer [L, B*M + B*N, 256],
-        which it enters by one device-to-device copy of slot l - 1; the returned descriptors are permuted views of it."""
+        which it enters by one device-to-device copy of slot l - 1; the returned descriptors are permuted views of it.
+        With `keep_output_stage` the last layer runs through gfc_lg_layer_pairs_keep (the same launches and two copies)
+        and the prediction also holds what the backward of that layer's output stage starts from
+        (`layer_loss_backward(output_stage=True)`): `output_stage_rows0` [B,M,256] / `output_stage_rows1` [B,N,256], the
+        rows the last cross block reads, and `output_stage_context0/1`, its attention context before `to_out`: views of
+        two [B*M + B*N, 256] buffers.  Every other key is the default call's, bit for bit."""
         self._check_ready(data)
         conf = self.conf
         if conf.depth_confidence > 0 or conf.width_confidence > 0:
@@ -847,13 +855,19 @@ class LightGlue(nn.Module):
         device = kpts0.device
         kp, de, so, s0, s1 = self._uniform_rows(data)
         d, nl = conf.descriptor_dim, conf.n_layers
+        if keep_output_stage and conf.matmul_precision != "fp32":
+            raise NotImplementedError("matmul_precision 'fp16': the output stage is kept for the fp32 matcher")
         if m == 0 or n == 0:  # the early return of `forward`
             zeros = torch.zeros
-            return self._result(torch.full((b, m), -1, device=device, dtype=torch.long),
+            pred = self._result(torch.full((b, m), -1, device=device, dtype=torch.long),
                                 torch.full((b, n), -1, device=device, dtype=torch.long),
                                 zeros((b, m), device=device), zeros((b, n), device=device),
                                 zeros((b, nl, m, d), device=device), zeros((b, nl, n, d), device=device),
                                 zeros((b, m + 1, n + 1), device=device))
+            if keep_output_stage:
+                for key in ("output_stage_rows", "output_stage_context"):
+                    pred[key + "0"], pred[key + "1"] = zeros((b, m, d), device=device), zeros((b, n, d), device=device)
+            return pred
         params = self._packed[0]
         rows = b * (m + n)
         stack = torch.empty((nl, rows, d), device=device)
@@ -878,9 +892,14 @@ class LightGlue(nn.Module):
         # on it evaluates sim once), so that the last layer is `forward`'s at every batch size
         ws = self._ws.get(max(nat.call("gfc_lg_layer_pairs_workspace_bytes", b, m, n),
                               nat.call("gfc_lg_assign_workspace_bytes", b, m, n)), device)
+        kept = torch.empty((2, rows, d), device=device) if keep_output_stage else None
         for i in range(nl):
             if i > 0:
                 stack[i].copy_(stack[i - 1])
+            if kept is not None and i == nl - 1:
+                nat.call("gfc_lg_layer_pairs_keep", ctypes.byref(params), i, stack[i], cos, sin, b, m, n, self_p, cross_p,
+                         kept[0], kept[1], ws, ws.numel())
+                continue
             nat.call("gfc_lg_layer_pairs", ctypes.byref(params), i, stack[i], cos, sin, b, m, n, self_p, cross_p, ws,
                      ws.numel())
         m0 = torch.empty((b, m), device=device, dtype=torch.long)
@@ -890,8 +909,12 @@ class LightGlue(nn.Module):
         last = stack[nl - 1]
         nat.call("gfc_lg_assign", ctypes.byref(params), nl - 1, last, last[b * m:], b, m, n,
                  float(conf.filter_threshold), m0, m1, ms0, ms1, scores, ws, ws.numel())
-        return self._result(m0, m1, ms0, ms1, stack[:, :b * m].view(nl, b, m, d).permute(1, 0, 2, 3),
+        pred = self._result(m0, m1, ms0, ms1, stack[:, :b * m].view(nl, b, m, d).permute(1, 0, 2, 3),
                             stack[:, b * m:].view(nl, b, n, d).permute(1, 0, 2, 3), scores)
+        if kept is not None:
+            for key, t in (("output_stage_rows", kept[0]), ("output_stage_context", kept[1])):
+                pred[key + "0"], pred[key + "1"] = t[:b * m].view(b, m, d), t[b * m:].view(b, n, d)
+        return pred
 
     def layer_loss(self, pred, data):
         """The reference's `loss` under `model.train()` (lightglue.py:597-630), forward only, plus a per-layer exit
@@ -1003,7 +1026,8 @@ class LightGlue(nn.Module):
         return losses, report
 
     # -- gradients of the training loss with respect to the heads and exit tokens (the trunk frozen) --------
-    def layer_loss_backward(self, pred, data, grad_total=None, descriptor_grads=False, accumulate=True):
+    def layer_loss_backward(self, pred, data, grad_total=None, descriptor_grads=False, accumulate=True,
+                            output_stage=False):
         """The gradients of `layer_loss`'s `total` with respect to the assignment heads and the exit tokens, what
         `torch.mean(losses["total"]).backward()` (gluefactory/train.py:1114) leaves in their `.grad` in the reference:
         the parameters of log_assignment[l] enter the loss through head l only (lightglue.py:589-616) and the token
@@ -1022,7 +1046,17 @@ class LightGlue(nn.Module):
 
         One layer is alive at a time, with one re-used workspace: gfc_lg_head_backward on the layer's rows; for l < L - 1
         the layer's own assignment (gfc_lg_assign), its token logits, the targets correct0/1 from gfc_lg_layer_scores
-        and gfc_lg_token_backward.  Nothing is read back to the host.  Gradients are built for the fp32 matcher."""
+        and gfc_lg_token_backward.  Nothing is read back to the host.  Gradients are built for the fp32 matcher.
+
+        With `output_stage` (a prediction of `forward_layers(keep_output_stage=True)`, n_layers >= 2) the dict, and
+        `.grad` under `accumulate`, also hold the gradients of the last layer's output stage,
+        `transformers.{L-1}.cross_attn.to_out.weight/.bias` and `.ffn.0/.1/.3.weight/.bias`: these eight tensors reach
+        the loss through head L - 1 only (lightglue.py:219-221,589-616; there is no exit token after the last layer), so
+        head L - 1's direct descriptor gradient, taken for that layer alone, sent through that one FFN block
+        (gfc_lg_ffn_backward on the state-dict weights, not the folded ones) is exactly what the reference's backward
+        leaves in them.  `grad_output_stage_rows0/1` and `grad_output_stage_context0/1` are the kernel's two row outputs:
+        the gradient at the rows the last cross block reads, through the residual and the first half of the
+        concatenation only, and at its attention context -- the operands an attention backward starts from."""
         conf = self.conf
         nl = conf.n_layers
         ref0, ref1 = pred["ref_descriptors0"], pred["ref_descriptors1"]
@@ -1041,6 +1075,14 @@ class LightGlue(nn.Module):
             raise NotImplementedError(f"loss.fn {conf.loss.fn!r}: only 'nll' is built")
         if conf.matmul_precision != "fp32":
             raise NotImplementedError("matmul_precision 'fp16': gradients are built for the fp32 matcher")
+        if output_stage:
+            if nl < 2:
+                raise ValueError("output_stage needs n_layers >= 2")
+            missing = [k for k in ("output_stage_rows0", "output_stage_rows1", "output_stage_context0",
+                                   "output_stage_context1") if k not in pred]
+            if missing:
+                raise ValueError(f"output_stage needs {missing} in the prediction: call "
+                                 "forward_layers(data, keep_output_stage=True)")
         nat.require_cuda(ref0, "pred['ref_descriptors0']")
         device = ref0.device
         params = self.ensure_packed(device)[0]
@@ -1070,7 +1112,10 @@ class LightGlue(nn.Module):
         dwm, dbm = torch.empty((nl, 1, d), device=device), torch.empty((nl, 1), device=device)
         dtw, dtb = torch.empty((max(nl - 1, 0), 1, d), device=device), torch.empty((max(nl - 1, 0), 1), device=device)
         dx = torch.empty((nl, rows, d), device=device) if descriptor_grads else None
-        ws = self._ws.get(max(nat.call("gfc_lg_head_backward_workspace_bytes", b, m, n),
+        # head L - 1's direct gradient, for that layer only when the whole buffer is not asked for
+        dy = None if not output_stage else dx[nl - 1] if dx is not None else torch.empty((rows, d), device=device)
+        ws = self._ws.get(max(nat.call("gfc_lg_ffn_backward_workspace_bytes", rows) if output_stage else 0,
+                              nat.call("gfc_lg_head_backward_workspace_bytes", b, m, n),
                               nat.call("gfc_lg_token_backward_workspace_bytes", b, m, n),
                               nat.call("gfc_lg_assign_workspace_bytes", b, m, n),
                               nat.call("gfc_lg_layer_scores_workspace_bytes", b, m, n)), device)
@@ -1084,7 +1129,8 @@ class LightGlue(nn.Module):
         for i in range(nl):
             x = _pack_sides(ref0[:, i].float().contiguous(), ref1[:, i].float().contiguous())
             nat.call("gfc_lg_head_backward", ctypes.byref(params), i, x, x[b * m:], gt0, gt1, gta, g[i], balancing, b, m,
-                     n, dwf[i], dbf[i], dwm[i], dbm[i], None if dx is None else dx[i], ws, ws.numel())
+                     n, dwf[i], dbf[i], dwm[i], dbm[i], dy if i == nl - 1 and dy is not None else None if dx is None else dx[i],
+                     ws, ws.numel())
             if i == nl - 1:
                 break
             nat.call("gfc_lg_assign", ctypes.byref(params), i, x, x[b * m:], b, m, n, float(conf.filter_threshold),
@@ -1101,6 +1147,24 @@ class LightGlue(nn.Module):
             grads[f"log_assignment.{i}.matchability.bias"] = dbm[i]
         for i in range(nl - 1):
             grads[f"token_confidence.{i}.token.0.weight"], grads[f"token_confidence.{i}.token.0.bias"] = dtw[i], dtb[i]
+        rows_out = None
+        if output_stage:
+            w = self._output_stage_weights(device)
+            x = _pack_sides(pred["output_stage_rows0"].float().contiguous(), pred["output_stage_rows1"].float().contiguous())
+            ctx = _pack_sides(pred["output_stage_context0"].float().contiguous(),
+                              pred["output_stage_context1"].float().contiguous())
+            if tuple(x.shape) != (rows, d) or tuple(ctx.shape) != (rows, d):
+                raise ValueError(f"the kept output stage {tuple(x.shape)} / {tuple(ctx.shape)} does not fit the "
+                                 f"descriptors ({rows} rows)")
+            pre = f"transformers.{nl - 1}.cross_attn."
+            og = {name: torch.empty_like(w[name]) for name in self._OUTPUT_STAGE}
+            rows_out = torch.empty((2, rows, d), device=device)
+            nat.call("gfc_lg_ffn_backward", x, ctx, dy, w["to_out.weight"], w["to_out.bias"], w["ffn.0.weight"],
+                     w["ffn.0.bias"], w["ffn.1.weight"], w["ffn.1.bias"], w["ffn.3.weight"], rows, og["to_out.weight"],
+                     og["to_out.bias"], og["ffn.0.weight"], og["ffn.0.bias"], og["ffn.1.weight"], og["ffn.1.bias"],
+                     og["ffn.3.weight"], og["ffn.3.bias"], rows_out[0], rows_out[1], ws, ws.numel())
+            for name in self._OUTPUT_STAGE:
+                grads[pre + name] = og[name]
         if accumulate:
             for name, grad in grads.items():
                 param = self.get_parameter(name)
@@ -1112,7 +1176,26 @@ class LightGlue(nn.Module):
         if dx is not None:
             grads["grad_ref_descriptors0"] = dx[:, :b * m].view(nl, b, m, d).permute(1, 0, 2, 3)
             grads["grad_ref_descriptors1"] = dx[:, b * m:].view(nl, b, n, d).permute(1, 0, 2, 3)
+        if rows_out is not None:
+            for key, t in (("grad_output_stage_rows", rows_out[0]), ("grad_output_stage_context", rows_out[1])):
+                grads[key + "0"], grads[key + "1"] = t[:b * m].view(b, m, d), t[b * m:].view(b, n, d)
         return grads
+
+    # the last cross block's parameters behind its output stage, by their names under transformers.{L-1}.cross_attn.
+    _OUTPUT_STAGE = ("to_out.weight", "to_out.bias", "ffn.0.weight", "ffn.0.bias", "ffn.1.weight", "ffn.1.bias",
+                     "ffn.3.weight", "ffn.3.bias")
+
+    def _output_stage_params(self):
+        ca = self.transformers[self.conf.n_layers - 1].cross_attn
+        return {name: ca.get_parameter(name) for name in self._OUTPUT_STAGE}
+
+    def _output_stage_weights(self, device):
+        """fp32 device copies of the UNFOLDED parameters of the output stage (a parameter that already lives on the
+        device in fp32 is read where it is), created on first use for the packed weights in force."""
+        if self._stage is None or self._stage[0] is not self._packed:
+            self._stage = (self._packed, {name: p.detach().to(device=device, dtype=torch.float32).contiguous()
+                                          for name, p in self._output_stage_params().items()})
+        return self._stage[1]
 
     def heads_updated(self):
         """Call after parameters of the assignment heads or exit tokens were changed in place (optimizer.step()): the
@@ -1128,6 +1211,37 @@ class LightGlue(nn.Module):
                     t32.copy_(param.detach().reshape(t32.shape))
                 if t16 is not None:
                     t16.copy_(t32)
+
+    def output_stage_updated(self):
+        """Call after the parameters of the last layer's output stage (`to_out` and `ffn` of its cross block) were
+        changed in place (optimizer.step()): `to_out` is folded into `ffn[0]` again by the function `_pack` uses, on the
+        same device, and W0', b0', gamma, beta, W3, b3 (and `to_out` itself without fold_out_proj) are written into the
+        packed device copies IN PLACE, at the addresses captured graphs replay; fp16 copies are rounded again from the
+        fp32 ones and the unfolded copies the backward reads are refreshed.  The result is what a fresh module loaded
+        from `state_dict()` packs, bit for bit; nothing else of the packed weights is touched."""
+        if self._packed is None:
+            return
+        p, l = self._packed[0], self.conf.n_layers - 1
+        by_ptr = {t.data_ptr(): t for t in self._packed[1]}
+        ca = self.transformers[l].cross_attn
+        w0, b0 = self._fold_ffn0(ca.ffn[0], ca.to_out)
+        items = [(w0, p.c_ffn0_w[l], p.c_ffn0_w16[l]), (b0, p.c_ffn0_b[l], None), (ca.ffn[1].weight, p.c_ln_g[l], None),
+                 (ca.ffn[1].bias, p.c_ln_b[l], None), (ca.ffn[3].weight, p.c_ffn3_w[l], p.c_ffn3_w16[l]),
+                 (ca.ffn[3].bias, p.c_ffn3_b[l], None)]
+        if not bool(self.conf.fold_out_proj):
+            items += [(ca.to_out.weight, p.c_out_w[l], p.c_out_w16[l]), (ca.to_out.bias, p.c_out_b[l], None)]
+        with torch.no_grad():
+            for src, ptr, ptr16 in items:
+                t32 = by_ptr[ptr]
+                if t32.data_ptr() != src.data_ptr():
+                    t32.copy_(src.detach().reshape(t32.shape))
+                if ptr16:
+                    by_ptr[ptr16].copy_(t32)
+            if self._stage is not None and self._stage[0] is self._packed:
+                for name, param in self._output_stage_params().items():
+                    t = self._stage[1][name]
+                    if t.data_ptr() != param.data_ptr():
+                        t.copy_(param.detach())
 
 
 __main_model__ = LightGlue

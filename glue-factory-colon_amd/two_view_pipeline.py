@@ -128,11 +128,14 @@ class TwoViewPipeline(BaseModel):
         c0, c1 = out0.pop("extractor_core_time_ms", None), out1.pop("extractor_core_time_ms", None)
         return out0, out1, t_ms, c0, c1, mem
 
-    def forward_layers(self, data):
-        """`forward` with the matcher's `forward_layers`: every layer's descriptors kept, the input of `layer_loss`."""
+    def forward_layers(self, data, keep_output_stage=False):
+        """`forward` with the matcher's `forward_layers`: every layer's descriptors kept, the input of `layer_loss`;
+        with `keep_output_stage` also what `layer_loss_backward(output_stage=True)` starts from."""
         for key in self.required_data_keys:
             assert key in data, f"Missing key {key} in data"
-        return self._forward(data, match=self.matcher.forward_layers)
+        if not keep_output_stage:
+            return self._forward(data, match=self.matcher.forward_layers)
+        return self._forward(data, match=lambda d: self.matcher.forward_layers(d, keep_output_stage=True))
 
     def _forward(self, data, match=None):
         image0, image1 = _image_of(data["view0"]), _image_of(data["view1"])

@@ -156,6 +156,10 @@ class ValidationPipeline:
             self.extra_positives = (self.extra_positives or 0) + int(host[-1].sum())
         return {k: host[i].tolist() for i, k in enumerate(keys)}
 
+    def _forward_layers(self, stacked):
+        """The matcher's `forward_layers` on a group's stacked key points and descriptors (finetune_heads overrides it)."""
+        return self.model.matcher.forward_layers(stacked)
+
     def _layer_numbers(self, datas, preds, pred, data):
         """The numbers of a group with --layer_report: the matcher's `forward_layers` on the stacked key points and
         descriptors, then `layer_loss`.  `loss/total` keeps its meaning (the final layer's NLL, as without the flag); the
@@ -168,7 +172,7 @@ class ValidationPipeline:
             if all(s is not None for s in sizes):
                 stacked[v] = {"image_size": torch.cat([torch.as_tensor(s, dtype=torch.float32).reshape(1, 2)
                                                        for s in sizes], 0).to(self.device)}
-        pred.update(self.model.matcher.forward_layers(stacked))
+        pred.update(self._forward_layers(stacked))
         losses, report = self.model.layer_loss(pred, data)
         numbers = {k: report[k] for k in KEYS}
         numbers.update({"loss/" + k: v for k, v in losses.items() if k not in ("total", "confidence")})
