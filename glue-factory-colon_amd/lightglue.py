@@ -6,10 +6,13 @@ the same state-dict key names (lightglue.py:349-408), including the legacy
 `self_attn.{i}` -> `transformers.{i}.self_attn` rename (lightglue.py:394-401), so the official
 `superpoint_lightglue.pth` / `disk_lightglue.pth` load unchanged.  Like the reference class it
 is a plain nn.Module (not a BaseModel) resolved through `__main_model__`.  The torch
-sub-modules are parameter containers only; the forward pass is one call into libgfc_amd.so.
+sub-modules are parameter containers only; the forward pass is one call into libgfc_amd.so.  The losses, the
+kept-layers forward and the gradients (`loss`, `forward_layers`, `layer_loss`, `layer_loss_backward`, `heads_updated`,
+`output_stage_updated`) are the mix-in of `lightglue_training.py`.
 
     model.matcher.name = glue_factory_colon_amd.lightglue
 """
+import copy
 import ctypes
 import itertools
 import sys
@@ -21,7 +24,9 @@ from torch import nn
 
 from . import _native as nat
 from . import weights as _weights
-from .base_model import Conf, conf_get, merge
+from ._rows import match_outputs, pack_sides, split_sides
+from .base_model import Conf, merge
+from .lightglue_training import LightGlueTraining
 
 
 def _ffn(d):
@@ -75,18 +80,6 @@ class _TokenConfidence(nn.Module):
 _CAPTURE_LOCK = threading.Lock()  # one stream capture at a time per process
 
 
-def _pack_sides(a, b):
-    """[B,M,C] and [B,N,C] -> [B*M + B*N, C] rows (side 0 first).  A view when `b` starts where `a` ends in the same
-    allocation (both views extracted by one call), a concatenation otherwise."""
-    c = a.shape[-1]
-    ra, rb = a.numel() // c, b.numel() // c
-    if (a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype == torch.float32
-            and b.data_ptr() == a.data_ptr() + a.numel() * 4
-            and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()):
-        return a.as_strided((ra + rb, c), (c, 1))
-    return torch.cat([a.reshape(ra, c), b.reshape(rb, c)], 0)
-
-
 def _image_size(data, side):
     """`view{side}.image_size` like the reference (lightglue.py:430-434); a view without one normalises by the extent
     of its own key points (normalize_keypoints, lightglue.py:31-32).  (The reference leaves the size unbound when a
@@ -98,7 +91,16 @@ def _image_size(data, side):
     return size
 
 
-class LightGlue(nn.Module):
+class _Derived:
+    """What is worked out once from one set of packed weights and replaced with them.  Every entry is (the packed
+    weights it was made for, value), so an entry is never used with other weights than its own (`LightGlue._derive`)."""
+
+    def __init__(self):
+        self.thresholds = None  # confidence_thresholds as a host list
+        self.stage = None  # the output stage's unfolded fp32 device copies, by name (lightglue_training.py)
+
+
+class LightGlue(LightGlueTraining, nn.Module):
     default_conf = {
         "name": "lightglue",
         "input_dim": 256,
@@ -160,13 +162,10 @@ class LightGlue(nn.Module):
         self.log_assignment = nn.ModuleList([_Assignment(d) for _ in range(n)])
         self.token_confidence = nn.ModuleList([_TokenConfidence(d) for _ in range(n - 1)])
         self.register_buffer("confidence_thresholds", _weights.confidence_thresholds(n))
-        self._packed = None
+        self._set_packed(None)
         self._ws = nat.Workspace()
         self.trace = None  # optional nat.KernelTrace (bench.py): per-launch events of the attention kernel
-        self._graphs = {}  # (b, m, n, device, has scale/ori) -> captured launch sequence + its static buffers
         self._report_host = None  # pinned [GFC_LG_MAX_RAGGED_PAIRS, 4] int32: the adaptive step's report lands here
-        self._thresholds_host = None  # (the packed weights they were read with, confidence_thresholds as a list)
-        self._stage = None  # (the packed weights they belong to, the output stage's unfolded fp32 device copies)
         self.are_weights_initialized = False
 
         w = conf.weights
@@ -188,14 +187,21 @@ class LightGlue(nn.Module):
             state_dict = {k.replace(f"cross_attn.{i}", f"transformers.{i}.cross_attn"): v
                           for k, v in state_dict.items()}
         ret = super().load_state_dict(state_dict, *args, **kwargs)
-        self._packed = None
+        self._set_packed(None)
         self.are_weights_initialized = True
         return ret
 
     def _apply(self, fn, *args, **kwargs):
-        self._packed = None
-        self._graphs = {}
+        self._set_packed(None)
         return super()._apply(fn, *args, **kwargs)
+
+    def _set_packed(self, packed):
+        """New packed weights (None: they are built on the next use), and with them nothing that was made for the old
+        ones: the captured graphs ((b, m, n, device, has scale/ori) -> launch sequence + its static buffers) and the
+        derived state."""
+        self._packed = packed
+        self._graphs = {}
+        self._derived = _Derived()
 
     def is_initialized(self):
         return self.are_weights_initialized
@@ -203,14 +209,14 @@ class LightGlue(nn.Module):
     def __deepcopy__(self, memo):
         """Replicas (export_predictions workers) get their own parameters and workspaces; captured graphs and packed
         weight pointers belong to the original and are rebuilt by the copy on first use."""
-        import copy
-
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
             if k == "_graphs":
                 new.__dict__[k] = {}
-            elif k in ("_packed", "_report_host", "_thresholds_host", "_stage"):
+            elif k == "_derived":
+                new.__dict__[k] = _Derived()
+            elif k in ("_packed", "_report_host"):
                 new.__dict__[k] = None
             else:
                 new.__dict__[k] = copy.deepcopy(v, memo)
@@ -225,12 +231,10 @@ class LightGlue(nn.Module):
     def _graph_entry(self, key, kp, de, s0, s1, so, b, m, n):
         """Static buffers + the captured launch sequence of gfc_lg_forward_packed for one problem shape."""
         device, d = kp.device, self.conf.descriptor_dim
+        m0, m1, ms0, ms1, scores = match_outputs(b, m, n, device)
         e = {"kp": torch.empty_like(kp), "de": torch.empty_like(de), "s0": torch.empty_like(s0),
              "s1": torch.empty_like(s1), "so": None if so is None else torch.empty_like(so),
-             "m0": torch.empty((b, m), device=device, dtype=torch.long),
-             "m1": torch.empty((b, n), device=device, dtype=torch.long),
-             "ms0": torch.empty((b, m), device=device), "ms1": torch.empty((b, n), device=device),
-             "scores": torch.empty((b, m + 1, n + 1), device=device),
+             "m0": m0, "m1": m1, "ms0": ms0, "ms1": ms1, "scores": scores,
              "rows": torch.empty((b * (m + n), d), device=device),
              "ws": torch.empty(nat.call("gfc_lg_packed_workspace_bytes", b, m, n), dtype=torch.uint8, device=device)}
         for name, src in (("kp", kp), ("de", de), ("s0", s0), ("s1", s1), ("so", so)):
@@ -379,9 +383,35 @@ class LightGlue(nn.Module):
         they do not exist yet (export workers share them: the caller packs before its worker streams start)."""
         self._check_ready()
         if self._packed is None or self._packed[2] != device:
-            self._packed = self._pack(device)
-            self._graphs = {}
+            self._set_packed(self._pack(device))
         return self._packed
+
+    def _host_thresholds(self):
+        """`confidence_thresholds` as a host list, read with the packed weights in force, once: no device-to-host read
+        in the calls that follow."""
+        return self._derive("thresholds", self.confidence_thresholds.tolist)
+
+    def _derive(self, name, make):
+        """Entry `name` of the derived state, made on first use with the packed weights in force."""
+        entry = getattr(self._derived, name)
+        if entry is None or entry[0] is not self._packed:
+            entry = (self._packed, make())
+            setattr(self._derived, name, entry)
+        return entry[1]
+
+    @property
+    def _thresholds_host(self):
+        """The entry behind `_host_thresholds` as it is held (None before the first read)."""
+        return self._derived.thresholds
+
+    def _empty_result(self, ref0, ref1):
+        """The reference's early return for a side without key points (lightglue.py:298-303): all -1 / zeros, around the
+        caller's zero descriptors ref0 [B,L,M,256] and ref1 [B,L,N,256]."""
+        (b, _, m, _), n, device, zeros = ref0.shape, ref1.shape[2], ref0.device, torch.zeros
+        return self._result(torch.full((b, m), -1, device=device, dtype=torch.long),
+                            torch.full((b, n), -1, device=device, dtype=torch.long),
+                            zeros((b, m), device=device), zeros((b, n), device=device), ref0, ref1,
+                            zeros((b, m + 1, n + 1), device=device))
 
     # -- forward ------------------------------------------------------------------------
     def _uniform_rows(self, data):
@@ -413,9 +443,9 @@ class LightGlue(nn.Module):
         s1 = torch.as_tensor(size1, device=device, dtype=torch.float32).expand(b, 2).contiguous()
         # side-0 rows then side-1 rows: zero-copy when both views came out of ONE extractor call (adjacent
         # slices of one tensor), otherwise one concatenation each (tensor plumbing)
-        kp = _pack_sides(kpts0.contiguous().float(), kpts1.contiguous().float())
-        de = _pack_sides(desc0, desc1)
-        so = _pack_sides(so0, so1) if so0 is not None else None
+        kp = pack_sides(kpts0.contiguous().float(), kpts1.contiguous().float())
+        de = pack_sides(desc0, desc1)
+        so = pack_sides(so0, so1) if so0 is not None else None
         return kp, de, so, s0, s1
 
     def forward(self, data: dict) -> dict:
@@ -432,38 +462,32 @@ class LightGlue(nn.Module):
             return self._forward_adaptive(data)
         kp, de, so, s0, s1 = self._uniform_rows(data)
         d = conf.descriptor_dim
-        if m > 0 and n > 0:
-            use_graph = 0 < b * (m + n) <= int(conf.graph_max_rows or 0) and self.trace is None
-            if use_graph:
-                key = (b, m, n, device.index, so is not None, torch.cuda.current_stream(device).cuda_stream)
-                e = self._graphs.get(key) or self._graph_entry(key, kp, de, s0, s1, so, b, m, n)
-                use_graph = e["graph"] is not None
-            if use_graph:
-                for name, src in (("kp", kp), ("de", de), ("s0", s0), ("s1", s1), ("so", so)):
-                    if src is not None:
-                        e[name].copy_(src)
-                e["graph"].replay()
-                # the graph owns its buffers: the caller gets copies (plumbing; 6 MB at 1024 x 1024 points)
-                m0, m1, ms0, ms1 = e["m0"].clone(), e["m1"].clone(), e["ms0"].clone(), e["ms1"].clone()
-                scores, rows = e["scores"].clone(), e["rows"].clone()
-            else:
-                # every element of the outputs is written by gfc_lg_forward_packed: no fills
-                m0 = torch.empty((b, m), device=device, dtype=torch.long)
-                m1 = torch.empty((b, n), device=device, dtype=torch.long)
-                ms0, ms1 = torch.empty((b, m), device=device), torch.empty((b, n), device=device)
-                scores = torch.empty((b, m + 1, n + 1), device=device)
-                # one row buffer [b*m + b*n, 256]: the library's layers work in place on it and leave the last layer's
-                # descriptors there; ref_descriptors0/1 are its two halves (no copy out)
-                rows = torch.empty((b * (m + n), d), device=device)
-                ws = self._ws.get(nat.call("gfc_lg_packed_workspace_bytes", b, m, n), device)
-                self._launch_packed(kp, de, s0, s1, so, b, m, n, m0, m1, ms0, ms1, scores, rows, ws, self.trace)
-        else:  # the reference's early return (lightglue.py:298-303): all -1 / zeros
-            m0 = torch.full((b, m), -1, device=device, dtype=torch.long)
-            m1 = torch.full((b, n), -1, device=device, dtype=torch.long)
-            ms0, ms1 = torch.zeros((b, m), device=device), torch.zeros((b, n), device=device)
-            scores = torch.zeros((b, m + 1, n + 1), device=device)
-            rows = torch.zeros((b * (m + n), d), device=device)
-        return self._result(m0, m1, ms0, ms1, rows[: b * m].view(b, 1, m, d), rows[b * m:].view(b, 1, n, d), scores)
+        if m == 0 or n == 0:  # ref_descriptors0/1 are the two halves of one row buffer, as below
+            ref0, ref1 = split_sides(torch.zeros((b * (m + n), d), device=device), b, m, n)
+            return self._empty_result(ref0.view(b, 1, m, d), ref1.view(b, 1, n, d))
+        use_graph = 0 < b * (m + n) <= int(conf.graph_max_rows or 0) and self.trace is None
+        if use_graph:
+            key = (b, m, n, device.index, so is not None, torch.cuda.current_stream(device).cuda_stream)
+            e = self._graphs.get(key) or self._graph_entry(key, kp, de, s0, s1, so, b, m, n)
+            use_graph = e["graph"] is not None
+        if use_graph:
+            for name, src in (("kp", kp), ("de", de), ("s0", s0), ("s1", s1), ("so", so)):
+                if src is not None:
+                    e[name].copy_(src)
+            e["graph"].replay()
+            # the graph owns its buffers: the caller gets copies (plumbing; 6 MB at 1024 x 1024 points)
+            m0, m1, ms0, ms1 = e["m0"].clone(), e["m1"].clone(), e["ms0"].clone(), e["ms1"].clone()
+            scores, rows = e["scores"].clone(), e["rows"].clone()
+        else:
+            # every element of the outputs is written by gfc_lg_forward_packed: no fills
+            m0, m1, ms0, ms1, scores = match_outputs(b, m, n, device)
+            # one row buffer [b*m + b*n, 256]: the library's layers work in place on it and leave the last layer's
+            # descriptors there; ref_descriptors0/1 are its two halves (no copy out)
+            rows = torch.empty((b * (m + n), d), device=device)
+            ws = self._ws.get(nat.call("gfc_lg_packed_workspace_bytes", b, m, n), device)
+            self._launch_packed(kp, de, s0, s1, so, b, m, n, m0, m1, ms0, ms1, scores, rows, ws, self.trace)
+        ref0, ref1 = split_sides(rows, b, m, n)
+        return self._result(m0, m1, ms0, ms1, ref0.view(b, 1, m, d), ref1.view(b, 1, n, d), scores)
 
     # -- one view of a batch-1 item, rows of several views, the rows' way into the matcher --------
     def _side(self, item, side, device):
@@ -603,7 +627,7 @@ class LightGlue(nn.Module):
         ind1 = torch.arange(n, device=device)
         prune0 = torch.ones((1, m), device=device, dtype=torch.long)
         prune1 = torch.ones((1, n), device=device, dtype=torch.long)
-        thresholds = self.confidence_thresholds.tolist()
+        thresholds = self._host_thresholds()
         cm, cn = m, n
         last = conf.n_layers - 1
         for i in range(conf.n_layers):
@@ -734,7 +758,7 @@ class LightGlue(nn.Module):
         if self._report_host is None:
             self._report_host = torch.empty((nat.GFC_LG_MAX_RAGGED_PAIRS, 4), dtype=torch.int32).pin_memory()
         report_host = self._report_host
-        thresholds = self.confidence_thresholds.tolist()
+        thresholds = self._host_thresholds()
         keep_thr = float(1 - conf.width_confidence)
         step_ws_bytes = nat.call("gfc_lg_adaptive_step_workspace_bytes", nb, total)
         bufs = [(xa, cosa, sina, inda), (xb, cosb, sinb, indb)]
@@ -797,451 +821,6 @@ class LightGlue(nn.Module):
         for slot, r0, cm, cn in live:  # went through every layer: the last layer's head
             finish(slot, conf.n_layers - 1, x, ind, r0, cm, cn)
         return outs
-
-    def loss(self, pred, data):
-        """The reference's `loss` (lightglue.py:588-637) in eval mode: (losses, metrics) of a full-depth prediction and
-        the labels `gt_matches0/1` (and `gt_assignment`, when the ground truth made one) in `data`.  In eval mode the
-        reference keeps the last layer only, so its layer loop runs zero times and total = last = the NLL of the final
-        assignment; it recomputes that assignment from ref_descriptors[:, -1] with the last head, which is
-        pred["log_assignment"] here.  One launch (gfc_lg_validation_metrics) gives the loss terms, row_norm and the
-        four matcher metrics; every value is a [B] tensor."""
-        if self.training:
-            raise NotImplementedError("the training loss (per-layer terms, token confidence, backward) is out of scope")
-        conf = self.conf
-        if conf.depth_confidence > 0 or conf.width_confidence > 0:
-            raise NotImplementedError(
-                "loss of an early-stopped / pruned prediction (depth_confidence / width_confidence > 0): the reference "
-                "applies the LAST head to the stop layer's descriptors there, which this prediction does not hold")
-        if conf_get(conf.loss, "fn", "nll") != "nll":
-            raise NotImplementedError(f"loss.fn {conf.loss.fn!r}: only 'nll' is built")
-        from .losses import OUT_KEYS, as_dict, validation_metrics
-        from .metrics import KEYS
-
-        out = validation_metrics(pred["log_assignment"], data["gt_matches0"], data["gt_matches1"],
-                                 data.get("gt_assignment"), pred["matches0"], pred["matching_scores0"],
-                                 conf_get(conf.loss, "nll_balancing", 0.5))
-        d = as_dict(out, OUT_KEYS)
-        losses = {"total": d["assignment_nll"], "last": d["assignment_nll"].clone(),
-                  **{k: d[k] for k in ("assignment_nll", "nll_pos", "nll_neg", "num_matchable", "num_unmatchable")},
-                  "row_norm": d["row_norm"]}
-        return losses, {k: d[k] for k in KEYS}
-
-    # -- every layer kept: the training-mode forward and loss of the reference, forward only ---------------
-    def forward_layers(self, data: dict, keep_output_stage: bool = False) -> dict:
-        """The reference's forward under `model.train()` (lightglue.py:495-498,546-547): full depth, every layer's
-        descriptors kept -- `ref_descriptors0` [B,L,M,256], `ref_descriptors1` [B,L,N,256], index l the output of
-        transformer l; every other key as `forward` returns it.  LightGlue has no dropout and no batch norm, so this is
-        the eval forward with the layers kept; it does not look at `self.training`.  Early stopping and pruning are
-        refused, as the reference disables both in training mode (lightglue.py:471-472).
-        The host drives the layers one by one (`gfc_lg_layer_pairs`: `gfc_lg_layer` with the cross attention
-        gfc_lg_forward_packed takes for the batch) and ends with `gfc_lg_assign` on the last head: the launch
-        sequence of gfc_lg_forward_packed.  Layer l works in place on slot l of one stack buffer [L, B*M + B*N, 256],
-        which it enters by one device-to-device copy of slot l - 1; the returned descriptors are permuted views of it.
-        With `keep_output_stage` the last layer runs through gfc_lg_layer_pairs_keep (the same launches and two copies)
-        and the prediction also holds what the backward of that layer's output stage starts from
-        (`layer_loss_backward(output_stage=True)`): `output_stage_rows0` [B,M,256] / `output_stage_rows1` [B,N,256], the
-        rows the last cross block reads, and `output_stage_context0/1`, its attention context before `to_out`: views of
-        two [B*M + B*N, 256] buffers.  Every other key is the default call's, bit for bit."""
-        self._check_ready(data)
-        conf = self.conf
-        if conf.depth_confidence > 0 or conf.width_confidence > 0:
-            raise NotImplementedError(
-                "forward_layers keeps every layer of the full-depth pass: depth_confidence / width_confidence > 0 "
-                "(early stopping, pruning) are disabled in the reference's training mode and refused here")
-        kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
-        nat.require_cuda(kpts0, "data['keypoints0']")
-        b, m, _ = kpts0.shape
-        n = kpts1.shape[1]
-        device = kpts0.device
-        kp, de, so, s0, s1 = self._uniform_rows(data)
-        d, nl = conf.descriptor_dim, conf.n_layers
-        if keep_output_stage and conf.matmul_precision != "fp32":
-            raise NotImplementedError("matmul_precision 'fp16': the output stage is kept for the fp32 matcher")
-        if m == 0 or n == 0:  # the early return of `forward`
-            zeros = torch.zeros
-            pred = self._result(torch.full((b, m), -1, device=device, dtype=torch.long),
-                                torch.full((b, n), -1, device=device, dtype=torch.long),
-                                zeros((b, m), device=device), zeros((b, n), device=device),
-                                zeros((b, nl, m, d), device=device), zeros((b, nl, n, d), device=device),
-                                zeros((b, m + 1, n + 1), device=device))
-            if keep_output_stage:
-                for key in ("output_stage_rows", "output_stage_context"):
-                    pred[key + "0"], pred[key + "1"] = zeros((b, m, d), device=device), zeros((b, n, d), device=device)
-            return pred
-        params = self._packed[0]
-        rows = b * (m + n)
-        stack = torch.empty((nl, rows, d), device=device)
-        if conf.input_dim != d:
-            self._input_proj(params, de, stack[0], rows)
-        else:
-            stack[0].copy_(de)
-        # problem b = side 0 of pair b, b + B = side 1 (the tables of gfc_lg_forward_packed), one upload
-        r0 = torch.arange(b, dtype=torch.int32) * m
-        r1 = b * m + torch.arange(b, dtype=torch.int32) * n
-        cm, cn = torch.full_like(r0, m), torch.full_like(r1, n)
-        self_p = torch.cat([torch.stack([r0, cm, r0, cm], 1), torch.stack([r1, cn, r1, cn], 1)], 0)
-        cross_p = torch.cat([torch.stack([r0, cm, r1, cn], 1), torch.stack([r1, cn, r0, cm], 1)], 0)
-        tabs = torch.cat([self_p.reshape(-1), cross_p.reshape(-1), r0, r1, cm, cn]).to(device)
-        self_p, cross_p = tabs[:8 * b].view(2 * b, 4), tabs[8 * b:16 * b].view(2 * b, 4)
-        row0, cnt = tabs[16 * b:18 * b], tabs[18 * b:20 * b]
-        sizes = torch.cat([s0, s1], 0).contiguous()
-        cos, sin = torch.empty((rows, 64), device=device), torch.empty((rows, 64), device=device)
-        nat.call("gfc_lg_posenc", kp, so, sizes, row0, cnt, 2 * b, max(m, n), params.posenc_wr,
-                 4 if so is not None else 2, cos, sin)
-        # gfc_lg_layer_pairs: gfc_lg_layer with the cross attention `forward` takes for this batch (from 8 large pairs
-        # on it evaluates sim once), so that the last layer is `forward`'s at every batch size
-        ws = self._ws.get(max(nat.call("gfc_lg_layer_pairs_workspace_bytes", b, m, n),
-                              nat.call("gfc_lg_assign_workspace_bytes", b, m, n)), device)
-        kept = torch.empty((2, rows, d), device=device) if keep_output_stage else None
-        for i in range(nl):
-            if i > 0:
-                stack[i].copy_(stack[i - 1])
-            if kept is not None and i == nl - 1:
-                nat.call("gfc_lg_layer_pairs_keep", ctypes.byref(params), i, stack[i], cos, sin, b, m, n, self_p, cross_p,
-                         kept[0], kept[1], ws, ws.numel())
-                continue
-            nat.call("gfc_lg_layer_pairs", ctypes.byref(params), i, stack[i], cos, sin, b, m, n, self_p, cross_p, ws,
-                     ws.numel())
-        m0 = torch.empty((b, m), device=device, dtype=torch.long)
-        m1 = torch.empty((b, n), device=device, dtype=torch.long)
-        ms0, ms1 = torch.empty((b, m), device=device), torch.empty((b, n), device=device)
-        scores = torch.empty((b, m + 1, n + 1), device=device)
-        last = stack[nl - 1]
-        nat.call("gfc_lg_assign", ctypes.byref(params), nl - 1, last, last[b * m:], b, m, n,
-                 float(conf.filter_threshold), m0, m1, ms0, ms1, scores, ws, ws.numel())
-        pred = self._result(m0, m1, ms0, ms1, stack[:, :b * m].view(nl, b, m, d).permute(1, 0, 2, 3),
-                            stack[:, b * m:].view(nl, b, n, d).permute(1, 0, 2, 3), scores)
-        if kept is not None:
-            for key, t in (("output_stage_rows", kept[0]), ("output_stage_context", kept[1])):
-                pred[key + "0"], pred[key + "1"] = t[:b * m].view(b, m, d), t[b * m:].view(b, n, d)
-        return pred
-
-    def layer_loss(self, pred, data):
-        """The reference's `loss` under `model.train()` (lightglue.py:597-630), forward only, plus a per-layer exit
-        report: (losses, report) of a `forward_layers` prediction and the labels `gt_matches0/1` (and `gt_assignment`,
-        when the ground truth made one) in `data`.  It does not look at `self.training`.
-
-        Every layer l < L - 1 goes through its own head (gfc_lg_assign into ONE re-used log-assignment buffer, so only
-        the final assignment and one layer's are alive), gfc_lg_validation_metrics on that assignment with that
-        layer's own mutual matches, the token logits (gfc_lg_rowdot without the sigmoid) and gfc_lg_layer_scores.  The
-        reference re-uses the weight matrix of the last layer for every layer (`weights=gt_weights`,
-        lightglue.py:598,609); that matrix depends on the labels only, so gfc_lg_validation_metrics on each layer with
-        the same labels is the same arithmetic.
-
-        losses, each [B]: `last`, `assignment_nll`, `nll_pos`, `nll_neg`, `num_matchable`, `num_unmatchable`,
-        `row_norm` of the final layer (what `loss` returns), `confidence` = sum_l (bce0_l + bce1_l) / 2 / (L - 1) and
-        `total` = (nll_{L-1} + sum_l w_l nll_l) / (1 + sum_l w_l) + confidence with w_l = gamma^(L-l-1) for
-        loss.gamma > 0, else l + 1, added in the reference's order.
-        report (MI355X addition), [B,L]: `layer_nll`, `layer_nll_pos`, `layer_nll_neg`, `layer_recall`,
-        `layer_precision` (the matcher metrics of layer l's own mutual matches); [B,L-1]: `layer_agree` = the share of
-        points whose arg-max (dustbin included) is that of the final layer -- the token-confidence target --,
-        `layer_token_bce`, `layer_ratio_confident` = the share of points with !(token < confidence_threshold(l)), the
-        number check_if_stop (lightglue.py:569-580) compares with depth_confidence; [B]: the four matcher metrics of the
-        final layer under the names `loss` gives them."""
-        conf = self.conf
-        nl = conf.n_layers
-        ref0, ref1 = pred["ref_descriptors0"], pred["ref_descriptors1"]
-        if ref0.dim() != 4 or ref0.shape[1] != nl or ref1.shape[1] != nl:
-            raise ValueError(f"layer_loss needs the descriptors of all {nl} layers, ref_descriptors0 is "
-                             f"{tuple(ref0.shape)}: the prediction must come from forward_layers, not forward")
-        b, _, m, d = ref0.shape
-        n = ref1.shape[2]
-        if m == 0 or n == 0:
-            raise ValueError(f"layer_loss of a pair without key points in one view ({m} x {n})")
-        if conf.depth_confidence > 0 or conf.width_confidence > 0:
-            raise NotImplementedError("layer_loss scores the full-depth pass: depth_confidence / width_confidence > 0 "
-                                      "are disabled in the reference's training mode and refused here")
-        if conf_get(conf.loss, "fn", "nll") != "nll":
-            raise NotImplementedError(f"loss.fn {conf.loss.fn!r}: only 'nll' is built")
-        nat.require_cuda(ref0, "pred['ref_descriptors0']")
-        from .losses import OUT_KEYS
-        from .metrics import KEYS
-
-        device = ref0.device
-        packed = self.ensure_packed(device)
-        params = packed[0]
-        if self._thresholds_host is None or self._thresholds_host[0] is not packed:
-            # read with the weights they belong to, once: no device-to-host read in the calls that follow
-            self._thresholds_host = (packed, self.confidence_thresholds.tolist())
-        thresholds = self._thresholds_host[1]
-        la_final = pred["log_assignment"].float().contiguous()
-        gt0 = data["gt_matches0"].to(device=device, dtype=torch.long).contiguous()
-        gt1 = data["gt_matches1"].to(device=device, dtype=torch.long).contiguous()
-        gta = data.get("gt_assignment")
-        if tuple(la_final.shape) != (b, m + 1, n + 1) or tuple(gt0.shape) != (b, m) or tuple(gt1.shape) != (b, n) or (
-                gta is not None and tuple(gta.shape) != (b, m, n)):
-            raise ValueError(f"ref_descriptors {tuple(ref0.shape)} / {tuple(ref1.shape)} do not fit log_assignment "
-                             f"{tuple(la_final.shape)}, gt_matches0 {tuple(gt0.shape)}, gt_matches1 {tuple(gt1.shape)}")
-        if gta is not None:
-            gta = gta.to(device=device).ne(0).contiguous()
-        balancing = float(conf_get(conf.loss, "nll_balancing", 0.5))
-        vm = torch.empty((nl, b, len(OUT_KEYS)), device=device)       # gfc_lg_validation_metrics of every layer
-        sc = torch.empty((max(nl - 1, 0), b, 6), device=device)        # gfc_lg_layer_scores of every layer but the last
-        nat.call("gfc_lg_validation_metrics", la_final, gt0, gt1, gta,
-                 pred["matches0"].to(device=device, dtype=torch.long).contiguous(),
-                 pred["matching_scores0"].to(device=device, dtype=torch.float32).contiguous(), b, m, n, balancing,
-                 vm[nl - 1])
-        rows = b * (m + n)
-        ws_assign = nat.call("gfc_lg_assign_workspace_bytes", b, m, n)
-        ws_scores = nat.call("gfc_lg_layer_scores_workspace_bytes", b, m, n)
-        ws = self._ws.get(max(ws_assign, ws_scores), device)
-        la = torch.empty_like(la_final)  # ONE buffer for every layer's own assignment
-        pm0 = torch.empty((b, m), device=device, dtype=torch.long)
-        pm1 = torch.empty((b, n), device=device, dtype=torch.long)
-        ps0, ps1 = torch.empty((b, m), device=device), torch.empty((b, n), device=device)
-        logits = torch.empty((rows,), device=device)
-        for i in range(nl - 1):
-            # [B*M + B*N, 256], side 0 first: slot i of the stack of forward_layers as it is, else one concatenation
-            x = _pack_sides(ref0[:, i].float().contiguous(), ref1[:, i].float().contiguous())
-            nat.call("gfc_lg_assign", ctypes.byref(params), i, x, x[b * m:], b, m, n, float(conf.filter_threshold),
-                     pm0, pm1, ps0, ps1, la, ws, ws.numel())
-            nat.call("gfc_lg_validation_metrics", la, gt0, gt1, gta, pm0, ps0, b, m, n, balancing, vm[i])
-            nat.call("gfc_lg_rowdot", x, d, rows, params.token_w[i], params.token_b[i], 0, logits)
-            nat.call("gfc_lg_layer_scores", la, la_final, logits, logits[b * m:], float(thresholds[i]), b, m, n, sc[i],
-                     None, None, ws, ws.numel())
-        col = OUT_KEYS.index
-        nll = vm[:, :, col("assignment_nll")]  # [L,B]
-        # lightglue.py:597-630 in its order of additions
-        gamma = float(conf_get(conf.loss, "gamma", 1.0))
-        total, sum_weights = nll[nl - 1], 1.0
-        confidence = torch.zeros((b,), device=device)
-        for i in range(nl - 1):
-            weight = gamma ** (nl - i - 1) if gamma > 0.0 else i + 1
-            sum_weights += weight
-            total = total + nll[i] * weight
-            confidence = confidence + (sc[i, :, 2] + sc[i, :, 3]) / 2.0 / (nl - 1)
-        total = total / sum_weights + confidence
-        final = vm[nl - 1]
-        losses = {"total": total, "last": final[:, col("assignment_nll")].clone(),
-                  **{k: final[:, col(k)] for k in ("assignment_nll", "nll_pos", "nll_neg", "num_matchable",
-                                                   "num_unmatchable")},
-                  "row_norm": final[:, col("row_norm")], "confidence": confidence}
-        report = {"layer_nll": nll.t(), "layer_nll_pos": vm[:, :, col("nll_pos")].t(),
-                  "layer_nll_neg": vm[:, :, col("nll_neg")].t(), "layer_recall": vm[:, :, col("match_recall")].t(),
-                  "layer_precision": vm[:, :, col("match_precision")].t(),
-                  "layer_agree": ((sc[:, :, 0] + sc[:, :, 1]) / (m + n)).t(),
-                  "layer_token_bce": ((sc[:, :, 2] + sc[:, :, 3]) / 2.0).t(),
-                  "layer_ratio_confident": ((sc[:, :, 4] + sc[:, :, 5]) / (m + n)).t(),
-                  **{k: final[:, col(k)] for k in KEYS}}
-        return losses, report
-
-    # -- gradients of the training loss with respect to the heads and exit tokens (the trunk frozen) --------
-    def layer_loss_backward(self, pred, data, grad_total=None, descriptor_grads=False, accumulate=True,
-                            output_stage=False):
-        """The gradients of `layer_loss`'s `total` with respect to the assignment heads and the exit tokens, what
-        `torch.mean(losses["total"]).backward()` (gluefactory/train.py:1114) leaves in their `.grad` in the reference:
-        the parameters of log_assignment[l] enter the loss through head l only (lightglue.py:589-616) and the token
-        reads detached descriptors (lightglue.py:83-85).  The trunk is not followed; `row_norm` and `last` carry no
-        gradient.
-
-        pred: a `forward_layers` prediction; data: the labels, as `layer_loss` takes them; grad_total [B]: the weight of
-        each pair's `total` in the differentiated scalar (default 1 / B each: the mean).  Returns a dict keyed by the
-        reference's state-dict names: `log_assignment.{l}.final_proj.weight` [256,256] / `.bias` [256],
-        `log_assignment.{l}.matchability.weight` [1,256] / `.bias` [1], `token_confidence.{l}.token.0.weight` [1,256] /
-        `.bias` [1].  With `accumulate` the same tensors are added into `.grad` of the module's parameters (created when
-        absent, as Tensor.backward does), so a torch optimizer works unchanged.  With `descriptor_grads` the dict also
-        holds `grad_ref_descriptors0` [B,L,M,256] and `grad_ref_descriptors1` [B,L,N,256], permuted views of one
-        [L, B*M + B*N, 256] buffer (the layout of forward_layers' stack): the DIRECT gradient at every layer's
-        descriptors, where a trunk backward would start.  Without the flag that buffer is never allocated.
-
-        One layer is alive at a time, with one re-used workspace: gfc_lg_head_backward on the layer's rows; for l < L - 1
-        the layer's own assignment (gfc_lg_assign), its token logits, the targets correct0/1 from gfc_lg_layer_scores
-        and gfc_lg_token_backward.  Nothing is read back to the host.  Gradients are built for the fp32 matcher.
-
-        With `output_stage` (a prediction of `forward_layers(keep_output_stage=True)`, n_layers >= 2) the dict, and
-        `.grad` under `accumulate`, also hold the gradients of the last layer's output stage,
-        `transformers.{L-1}.cross_attn.to_out.weight/.bias` and `.ffn.0/.1/.3.weight/.bias`: these eight tensors reach
-        the loss through head L - 1 only (lightglue.py:219-221,589-616; there is no exit token after the last layer), so
-        head L - 1's direct descriptor gradient, taken for that layer alone, sent through that one FFN block
-        (gfc_lg_ffn_backward on the state-dict weights, not the folded ones) is exactly what the reference's backward
-        leaves in them.  `grad_output_stage_rows0/1` and `grad_output_stage_context0/1` are the kernel's two row outputs:
-        the gradient at the rows the last cross block reads, through the residual and the first half of the
-        concatenation only, and at its attention context -- the operands an attention backward starts from."""
-        conf = self.conf
-        nl = conf.n_layers
-        ref0, ref1 = pred["ref_descriptors0"], pred["ref_descriptors1"]
-        if ref0.dim() != 4 or ref0.shape[1] != nl or ref1.shape[1] != nl:
-            raise ValueError(f"layer_loss_backward needs the descriptors of all {nl} layers, ref_descriptors0 is "
-                             f"{tuple(ref0.shape)}: the prediction must come from forward_layers, not forward")
-        b, _, m, d = ref0.shape
-        n = ref1.shape[2]
-        if m == 0 or n == 0:
-            raise ValueError(f"layer_loss_backward of a pair without key points in one view ({m} x {n})")
-        if conf.depth_confidence > 0 or conf.width_confidence > 0:
-            raise NotImplementedError("layer_loss_backward differentiates the full-depth pass: depth_confidence / "
-                                      "width_confidence > 0 are disabled in the reference's training mode and refused "
-                                      "here")
-        if conf_get(conf.loss, "fn", "nll") != "nll":
-            raise NotImplementedError(f"loss.fn {conf.loss.fn!r}: only 'nll' is built")
-        if conf.matmul_precision != "fp32":
-            raise NotImplementedError("matmul_precision 'fp16': gradients are built for the fp32 matcher")
-        if output_stage:
-            if nl < 2:
-                raise ValueError("output_stage needs n_layers >= 2")
-            missing = [k for k in ("output_stage_rows0", "output_stage_rows1", "output_stage_context0",
-                                   "output_stage_context1") if k not in pred]
-            if missing:
-                raise ValueError(f"output_stage needs {missing} in the prediction: call "
-                                 "forward_layers(data, keep_output_stage=True)")
-        nat.require_cuda(ref0, "pred['ref_descriptors0']")
-        device = ref0.device
-        params = self.ensure_packed(device)[0]
-        la_final = pred["log_assignment"].float().contiguous()
-        gt0 = data["gt_matches0"].to(device=device, dtype=torch.long).contiguous()
-        gt1 = data["gt_matches1"].to(device=device, dtype=torch.long).contiguous()
-        gta = data.get("gt_assignment")
-        if tuple(la_final.shape) != (b, m + 1, n + 1) or tuple(gt0.shape) != (b, m) or tuple(gt1.shape) != (b, n) or (
-                gta is not None and tuple(gta.shape) != (b, m, n)):
-            raise ValueError(f"ref_descriptors {tuple(ref0.shape)} / {tuple(ref1.shape)} do not fit log_assignment "
-                             f"{tuple(la_final.shape)}, gt_matches0 {tuple(gt0.shape)}, gt_matches1 {tuple(gt1.shape)}")
-        if gta is not None:
-            gta = gta.to(device=device).ne(0).contiguous()
-        if grad_total is None:
-            gtot = torch.full((b,), 1.0 / b, device=device)
-        else:
-            gtot = grad_total.to(device=device, dtype=torch.float32).contiguous()
-            if tuple(gtot.shape) != (b,):
-                raise ValueError(f"grad_total must be [{b}], got {tuple(gtot.shape)}")
-        balancing = float(conf_get(conf.loss, "nll_balancing", 0.5))
-        gamma = float(conf_get(conf.loss, "gamma", 1.0))
-        # lightglue.py:597,611-626: the last layer has weight 1; every nll is divided by the sum of the weights
-        weights = [gamma ** (nl - i - 1) if gamma > 0.0 else float(i + 1) for i in range(nl - 1)] + [1.0]
-        g = (torch.tensor(weights, dtype=torch.float64) / sum(weights)).float().to(device)[:, None] * gtot[None]  # [L,B]
-        rows = b * (m + n)
-        dwf, dbf = torch.empty((nl, d, d), device=device), torch.empty((nl, d), device=device)
-        dwm, dbm = torch.empty((nl, 1, d), device=device), torch.empty((nl, 1), device=device)
-        dtw, dtb = torch.empty((max(nl - 1, 0), 1, d), device=device), torch.empty((max(nl - 1, 0), 1), device=device)
-        dx = torch.empty((nl, rows, d), device=device) if descriptor_grads else None
-        # head L - 1's direct gradient, for that layer only when the whole buffer is not asked for
-        dy = None if not output_stage else dx[nl - 1] if dx is not None else torch.empty((rows, d), device=device)
-        ws = self._ws.get(max(nat.call("gfc_lg_ffn_backward_workspace_bytes", rows) if output_stage else 0,
-                              nat.call("gfc_lg_head_backward_workspace_bytes", b, m, n),
-                              nat.call("gfc_lg_token_backward_workspace_bytes", b, m, n),
-                              nat.call("gfc_lg_assign_workspace_bytes", b, m, n),
-                              nat.call("gfc_lg_layer_scores_workspace_bytes", b, m, n)), device)
-        la = torch.empty_like(la_final)  # ONE buffer for every layer's own assignment
-        pm0 = torch.empty((b, m), device=device, dtype=torch.long)
-        pm1 = torch.empty((b, n), device=device, dtype=torch.long)
-        ps0, ps1 = torch.empty((b, m), device=device), torch.empty((b, n), device=device)
-        logits = torch.empty((rows,), device=device)
-        correct = torch.empty((rows,), device=device, dtype=torch.uint8)
-        sc = torch.empty((b, 6), device=device)
-        for i in range(nl):
-            x = _pack_sides(ref0[:, i].float().contiguous(), ref1[:, i].float().contiguous())
-            nat.call("gfc_lg_head_backward", ctypes.byref(params), i, x, x[b * m:], gt0, gt1, gta, g[i], balancing, b, m,
-                     n, dwf[i], dbf[i], dwm[i], dbm[i], dy if i == nl - 1 and dy is not None else None if dx is None else dx[i],
-                     ws, ws.numel())
-            if i == nl - 1:
-                break
-            nat.call("gfc_lg_assign", ctypes.byref(params), i, x, x[b * m:], b, m, n, float(conf.filter_threshold),
-                     pm0, pm1, ps0, ps1, la, ws, ws.numel())
-            nat.call("gfc_lg_rowdot", x, d, rows, params.token_w[i], params.token_b[i], 0, logits)
-            nat.call("gfc_lg_layer_scores", la, la_final, logits, logits[b * m:], 0.5, b, m, n, sc, correct,
-                     correct[b * m:], ws, ws.numel())
-            nat.call("gfc_lg_token_backward", x, x[b * m:], logits, logits[b * m:], correct, correct[b * m:], gtot, nl,
-                     b, m, n, dtw[i], dtb[i], ws, ws.numel())
-        grads = {}
-        for i in range(nl):
-            grads[f"log_assignment.{i}.final_proj.weight"], grads[f"log_assignment.{i}.final_proj.bias"] = dwf[i], dbf[i]
-            grads[f"log_assignment.{i}.matchability.weight"] = dwm[i]
-            grads[f"log_assignment.{i}.matchability.bias"] = dbm[i]
-        for i in range(nl - 1):
-            grads[f"token_confidence.{i}.token.0.weight"], grads[f"token_confidence.{i}.token.0.bias"] = dtw[i], dtb[i]
-        rows_out = None
-        if output_stage:
-            w = self._output_stage_weights(device)
-            x = _pack_sides(pred["output_stage_rows0"].float().contiguous(), pred["output_stage_rows1"].float().contiguous())
-            ctx = _pack_sides(pred["output_stage_context0"].float().contiguous(),
-                              pred["output_stage_context1"].float().contiguous())
-            if tuple(x.shape) != (rows, d) or tuple(ctx.shape) != (rows, d):
-                raise ValueError(f"the kept output stage {tuple(x.shape)} / {tuple(ctx.shape)} does not fit the "
-                                 f"descriptors ({rows} rows)")
-            pre = f"transformers.{nl - 1}.cross_attn."
-            og = {name: torch.empty_like(w[name]) for name in self._OUTPUT_STAGE}
-            rows_out = torch.empty((2, rows, d), device=device)
-            nat.call("gfc_lg_ffn_backward", x, ctx, dy, w["to_out.weight"], w["to_out.bias"], w["ffn.0.weight"],
-                     w["ffn.0.bias"], w["ffn.1.weight"], w["ffn.1.bias"], w["ffn.3.weight"], rows, og["to_out.weight"],
-                     og["to_out.bias"], og["ffn.0.weight"], og["ffn.0.bias"], og["ffn.1.weight"], og["ffn.1.bias"],
-                     og["ffn.3.weight"], og["ffn.3.bias"], rows_out[0], rows_out[1], ws, ws.numel())
-            for name in self._OUTPUT_STAGE:
-                grads[pre + name] = og[name]
-        if accumulate:
-            for name, grad in grads.items():
-                param = self.get_parameter(name)
-                grad = grad.to(device=param.device, dtype=param.dtype)
-                if param.grad is None:
-                    param.grad = grad.clone()
-                else:
-                    param.grad += grad
-        if dx is not None:
-            grads["grad_ref_descriptors0"] = dx[:, :b * m].view(nl, b, m, d).permute(1, 0, 2, 3)
-            grads["grad_ref_descriptors1"] = dx[:, b * m:].view(nl, b, n, d).permute(1, 0, 2, 3)
-        if rows_out is not None:
-            for key, t in (("grad_output_stage_rows", rows_out[0]), ("grad_output_stage_context", rows_out[1])):
-                grads[key + "0"], grads[key + "1"] = t[:b * m].view(b, m, d), t[b * m:].view(b, n, d)
-        return grads
-
-    # the last cross block's parameters behind its output stage, by their names under transformers.{L-1}.cross_attn.
-    _OUTPUT_STAGE = ("to_out.weight", "to_out.bias", "ffn.0.weight", "ffn.0.bias", "ffn.1.weight", "ffn.1.bias",
-                     "ffn.3.weight", "ffn.3.bias")
-
-    def _output_stage_params(self):
-        ca = self.transformers[self.conf.n_layers - 1].cross_attn
-        return {name: ca.get_parameter(name) for name in self._OUTPUT_STAGE}
-
-    def _output_stage_weights(self, device):
-        """fp32 device copies of the UNFOLDED parameters of the output stage (a parameter that already lives on the
-        device in fp32 is read where it is), created on first use for the packed weights in force."""
-        if self._stage is None or self._stage[0] is not self._packed:
-            self._stage = (self._packed, {name: p.detach().to(device=device, dtype=torch.float32).contiguous()
-                                          for name, p in self._output_stage_params().items()})
-        return self._stage[1]
-
-    def heads_updated(self):
-        """Call after parameters of the assignment heads or exit tokens were changed in place (optimizer.step()): the
-        device copies the kernels read are refreshed IN PLACE, at the addresses captured graphs replay, so `forward`,
-        `forward_pairs` and `forward_layers` give what a fresh module loaded from `state_dict()` gives.  The trunk's
-        packed weights are not rebuilt.  (A parameter that already lives on the device in fp32 is read by the kernels
-        where it is: only its fp16 copy needs the refresh.)"""
-        if self._packed is None:
-            return
-        with torch.no_grad():
-            for param, t32, t16 in self._packed[3]:
-                if t32.data_ptr() != param.data_ptr():
-                    t32.copy_(param.detach().reshape(t32.shape))
-                if t16 is not None:
-                    t16.copy_(t32)
-
-    def output_stage_updated(self):
-        """Call after the parameters of the last layer's output stage (`to_out` and `ffn` of its cross block) were
-        changed in place (optimizer.step()): `to_out` is folded into `ffn[0]` again by the function `_pack` uses, on the
-        same device, and W0', b0', gamma, beta, W3, b3 (and `to_out` itself without fold_out_proj) are written into the
-        packed device copies IN PLACE, at the addresses captured graphs replay; fp16 copies are rounded again from the
-        fp32 ones and the unfolded copies the backward reads are refreshed.  The result is what a fresh module loaded
-        from `state_dict()` packs, bit for bit; nothing else of the packed weights is touched."""
-        if self._packed is None:
-            return
-        p, l = self._packed[0], self.conf.n_layers - 1
-        by_ptr = {t.data_ptr(): t for t in self._packed[1]}
-        ca = self.transformers[l].cross_attn
-        w0, b0 = self._fold_ffn0(ca.ffn[0], ca.to_out)
-        items = [(w0, p.c_ffn0_w[l], p.c_ffn0_w16[l]), (b0, p.c_ffn0_b[l], None), (ca.ffn[1].weight, p.c_ln_g[l], None),
-                 (ca.ffn[1].bias, p.c_ln_b[l], None), (ca.ffn[3].weight, p.c_ffn3_w[l], p.c_ffn3_w16[l]),
-                 (ca.ffn[3].bias, p.c_ffn3_b[l], None)]
-        if not bool(self.conf.fold_out_proj):
-            items += [(ca.to_out.weight, p.c_out_w[l], p.c_out_w16[l]), (ca.to_out.bias, p.c_out_b[l], None)]
-        with torch.no_grad():
-            for src, ptr, ptr16 in items:
-                t32 = by_ptr[ptr]
-                if t32.data_ptr() != src.data_ptr():
-                    t32.copy_(src.detach().reshape(t32.shape))
-                if ptr16:
-                    by_ptr[ptr16].copy_(t32)
-            if self._stage is not None and self._stage[0] is self._packed:
-                for name, param in self._output_stage_params().items():
-                    t = self._stage[1][name]
-                    if t.data_ptr() != param.data_ptr():
-                        t.copy_(param.detach())
 
 
 __main_model__ = LightGlue

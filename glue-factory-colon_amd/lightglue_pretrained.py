@@ -49,7 +49,7 @@ class LightGlue(BaseModel):
             self.set_initialized()
             return ret
         ret = super().load_state_dict(state_dict, *args, **kwargs)
-        self.net._packed = None
+        self.net._set_packed(None)
         self.net.are_weights_initialized = True
         self.set_initialized()
         return ret

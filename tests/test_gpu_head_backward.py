@@ -485,6 +485,51 @@ def test_finetune_heads_on_a_generated_directory(tmp_path, capsys):
         assert torch.equal(loaded.state_dict()[k].cpu(), v), k
 
 
+def test_layer_loss_and_backward_in_either_order():
+    """`layer_loss` and `layer_loss_backward` build the same layer pass (one set of per-layer buffers, the module's one
+    workspace): on one prediction, loss then backward on one module and backward then loss on a fresh one give the same
+    bits, and `.grad` after two accumulating calls is the sum of two non-accumulating results added in that order.
+    2 x (130 + 65) points, 3 layers: no multiple of the 64-row tiles, M != N."""
+    b, m, n = 2, 130, 65
+    g = torch.Generator().manual_seed(11)
+    size = torch.tensor([[640.0, 480.0]] * b).cuda()
+    data = {"keypoints0": (torch.rand((b, m, 2), generator=g) * 479).cuda(),
+            "keypoints1": (torch.rand((b, n, 2), generator=g) * 479).cuda(), "descriptors0": rows(b, m, 12).cuda(),
+            "descriptors1": rows(b, n, 13).cuda(), "view0": {"image_size": size}, "view1": {"image_size": size}}
+    gt0, gt1, gta = make_labels(b, m, n, 14, "assignment")
+    lab = {"gt_matches0": gt0.cuda(), "gt_matches1": gt1.cuda(), "gt_assignment": gta.cuda()}
+
+    def run(order):
+        lg = model(n_layers=3)
+        with torch.no_grad():
+            pred = lg.forward_layers(data)
+        out = {}
+        for what in order:
+            if what == "loss":
+                with torch.no_grad():
+                    out["losses"], out["report"] = lg.layer_loss(pred, lab)
+            else:
+                out["grads"] = lg.layer_loss_backward(pred, lab, accumulate=False)
+        return lg, pred, out
+
+    lg, pred, first = run(("loss", "backward"))
+    _, other_pred, second = run(("backward", "loss"))
+    for k in pred:
+        assert torch.equal(pred[k], other_pred[k]), k
+    assert len(first["grads"]) == 4 * 3 + 2 * 2 and any(k.startswith("token_confidence.") for k in first["grads"])
+    for part in ("losses", "report", "grads"):
+        assert set(first[part]) == set(second[part])
+        for k, v in first[part].items():
+            assert bool(torch.isfinite(v).all()) and torch.equal(v, second[part][k]), (part, k)
+    assert all(p.grad is None for p in lg.parameters())
+    lg.layer_loss_backward(pred, lab)
+    lg.layer_loss_backward(pred, lab)
+    for k, v in first["grads"].items():
+        want = v.clone()
+        want += second["grads"][k]
+        assert bool((v != 0).any()) and torch.equal(lg.get_parameter(k).grad, want), k
+
+
 def test_print_the_worst_fractions():
     """Last in the file: the largest fraction of a bound that any test above used, per output."""
     for k in sorted(WORST):
