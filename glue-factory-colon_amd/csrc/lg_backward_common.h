@@ -1,6 +1,6 @@
-// What the backward units share (lg_head_backward.hip, lg_ffn_backward.hip): the strided split-K GEMM on
-// v_mfma_f32_32x32x2_f32, the split of a row count into parts, and the column sums per chunk of rows with their finishing
-// launch.  Nothing here is accumulated by atomics and no sum depends on the order in which workgroups run.
+// What the backward units share (lg_head_backward.hip, lg_ffn_backward.hip, lg_cross_attn_backward.hip): the strided
+// split-K GEMM on v_mfma_f32_32x32x2_f32, the split of a row count into parts, the column sums per chunk of rows with
+// their finishing launch, and the finishing launch of the split-K parts.  Nothing here is accumulated by atomics and no sum depends on the order in which workgroups run.
 #pragma once
 #include "common.h"
 
@@ -168,6 +168,23 @@ static int hb_colsums(const float* dmd, const float* v, const float* x0, const f
   hipLaunchKernelGGL(hb_colsum_kernel, dim3(chunks), dim3(256), 0, st, dmd, v, x0, x1, R0, R, part);
   GFC_LAUNCH_CHECK();
   hipLaunchKernelGGL(hb_colsum_finish_kernel, dim3(3), dim3(256), 0, st, part, chunks, scale, o_d, o_w, o_b);
+  GFC_LAUNCH_CHECK();
+  return GFC_OK;
+}
+
+// out[e] = the sum over `n` records of `stride` floats of rec[e], in ascending order, in fp64, rounded once
+static __global__ __launch_bounds__(256) void hb_finish_kernel(const float* __restrict__ rec, int n, size_t stride, int count,
+                                                        float* __restrict__ out) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= count) return;
+  double s = 0.0;
+#pragma unroll 8  // eight loads in flight; the additions stay in ascending order
+  for (int p = 0; p < n; ++p) s += (double)rec[(size_t)p * stride + e];
+  out[e] = (float)s;
+}
+
+static int hb_finish(const float* rec, int n, size_t stride, int count, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(hb_finish_kernel, dim3((count + 255) / 256), dim3(256), 0, st, rec, n, stride, count, out);
   GFC_LAUNCH_CHECK();
   return GFC_OK;
 }

@@ -101,17 +101,6 @@ __global__ __launch_bounds__(256) void fb_ln_gelu_backward_kernel(float* h, floa
   for (int e = tid; e < FB_ROW_STRIDE; e += 256) out[e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
 }
 
-// out[e] = the sum over `n` records of `stride` floats of rec[e], in ascending order, in fp64, rounded once
-__global__ __launch_bounds__(256) void fb_finish_kernel(const float* __restrict__ rec, int n, size_t stride, int count,
-                                                        float* __restrict__ out) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= count) return;
-  double s = 0.0;
-#pragma unroll 8  // eight loads in flight; the additions stay in ascending order
-  for (int p = 0; p < n; ++p) s += (double)rec[(size_t)p * stride + e];
-  out[e] = (float)s;
-}
-
 // the row kernel's chunk records [dgamma | dbeta | db0] in one launch, the same sums
 __global__ __launch_bounds__(256) void fb_row_finish_kernel(const float* __restrict__ rec, int n,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
@@ -122,12 +111,6 @@ __global__ __launch_bounds__(256) void fb_row_finish_kernel(const float* __restr
   for (int p = 0; p < n; ++p) s += (double)rec[(size_t)p * FB_ROW_STRIDE + e];
   float* out = e < FB_H ? dgamma : e < 2 * FB_H ? dbeta : db0;
   out[e % FB_H] = (float)s;
-}
-
-static int fb_finish(const float* rec, int n, size_t stride, int count, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(fb_finish_kernel, dim3((count + 255) / 256), dim3(256), 0, st, rec, n, stride, count, out);
-  GFC_LAUNCH_CHECK();
-  return GFC_OK;
 }
 
 // dx_in += dy
@@ -196,7 +179,7 @@ extern "C" int gfc_lg_ffn_backward(const float* x, const float* ctx, const float
   w.A = dy; w.a_k = HB_D; w.B = da; w.b_k = FB_H; w.C = wpart; w.c_m = FB_H; w.c_p = (long long)HB_D * FB_H;
   w.M = HB_D; w.N = FB_H;
   HB_TRY(hb_gemm(w, false, sp.parts, 1, st));
-  HB_TRY(fb_finish(wpart, sp.parts, (size_t)HB_D * FB_H, HB_D * FB_H, dW3, st));
+  HB_TRY(hb_finish(wpart, sp.parts, (size_t)HB_D * FB_H, HB_D * FB_H, dW3, st));
   HB_TRY(hb_colsums(dy, nullptr, nullptr, nullptr, 0, rows, cpart, 1.f, db3, nullptr, nullptr, st));
   // dW0 [512,512] = dh^T [x | m], a half of the columns per launch
   w.A = h; w.a_k = FB_H; w.B = x; w.b_k = HB_D; w.C = wpart; w.c_m = FB_H; w.c_p = (long long)FB_H * FB_H;
@@ -204,7 +187,7 @@ extern "C" int gfc_lg_ffn_backward(const float* x, const float* ctx, const float
   HB_TRY(hb_gemm(w, false, sp.parts, 1, st));
   w.B = msg; w.C = wpart + HB_D;
   HB_TRY(hb_gemm(w, false, sp.parts, 1, st));
-  HB_TRY(fb_finish(wpart, sp.parts, (size_t)FB_H * FB_H, FB_H * FB_H, dW0, st));
+  HB_TRY(hb_finish(wpart, sp.parts, (size_t)FB_H * FB_H, FB_H * FB_H, dW0, st));
 
   // dcat = dh W0: the second half is dm, the first one joins the residual
   HbGemm d{};
@@ -230,7 +213,7 @@ extern "C" int gfc_lg_ffn_backward(const float* x, const float* ctx, const float
     w.A = dm; w.a_k = HB_D; w.B = ctx; w.b_k = HB_D; w.C = wpart; w.c_m = HB_D; w.c_p = (long long)HB_D * HB_D;
     w.M = HB_D; w.N = HB_D;
     HB_TRY(hb_gemm(w, false, sp.parts, 1, st));
-    HB_TRY(fb_finish(wpart, sp.parts, (size_t)HB_D * HB_D, HB_D * HB_D, dWout, st));
+    HB_TRY(hb_finish(wpart, sp.parts, (size_t)HB_D * HB_D, HB_D * HB_D, dWout, st));
     HB_TRY(hb_colsums(dm, nullptr, nullptr, nullptr, 0, rows, cpart, 1.f, dbout, nullptr, nullptr, st));
     if (dctx) {
       d.A = dm; d.a_m = HB_D; d.K = HB_D; d.kchunk = HB_D;

@@ -4,7 +4,7 @@ reference's training loss (`LightGlue.layer_loss_backward`); the trunk, `input_p
 never touched.
 
     python -m glue_factory_colon_amd.finetune_heads --data_dir D --dataset {homographies,posed_images,endomapper}
-        [--params {tokens,heads,all,output_stage,all+output_stage}] [--lr 1e-3] [--optimizer {adam,sgd}] [--clip_grad G] [--epochs E]
+        [--params {tokens,heads,all,output_stage,all+output_stage,cross_block,all+cross_block}] [--lr 1e-3] [--optimizer {adam,sgd}] [--clip_grad G] [--epochs E]
         [--max_steps S] [--pair_batch N] --out FILE
 
 The pairs come from `validate`'s feeders, with its ground-truth options and its grouping: inside a `--pair_batch` chunk
@@ -13,7 +13,10 @@ with grad_total = 1 / (pairs in the chunk); ONE optimizer step is taken per chun
 tokens` / `heads` hand only those parameters to the optimizer; the others are not passed to it.  `--params output_stage`
 re-fits `to_out` and `ffn` of the last layer's cross block (eight tensors, about 460 k parameters, whose exact gradients
 `layer_loss_backward(output_stage=True)` gives), `all+output_stage` those with the heads and tokens; the rest of the trunk
-stays frozen, and every step also ends with `output_stage_updated()`.  `loss/total_deep`,
+stays frozen, and every step also ends with `output_stage_updated()`.  `--params cross_block` re-fits the twelve tensors
+of the last cross block (the output stage and `to_qk`, `to_v`, through `layer_loss_backward(output_stage=True,
+cross_attention=True)`), `all+cross_block` those with the heads and tokens; every such step also ends with
+`cross_attention_updated()`.  `loss/total_deep`,
 `loss/confidence` and the per-layer table of `validate --layer_report` are printed before and after, and the matcher's
 `state_dict()` is written to `--out`, which `conf.weights = FILE` loads.  No schedules, no checkpoint resume, no mixed
 precision.
@@ -29,7 +32,9 @@ from . import validate
 PREFIXES = {"tokens": ("token_confidence.",), "heads": ("log_assignment.",),
             "all": ("token_confidence.", "log_assignment.")}
 # choices that also train the last layer's output stage -> the prefixes of the heads and tokens trained with it
-OUTPUT_STAGE = {"output_stage": (), "all+output_stage": PREFIXES["all"]}
+OUTPUT_STAGE = {"output_stage": (), "all+output_stage": PREFIXES["all"], "cross_block": (),
+                "all+cross_block": PREFIXES["all"]}
+CROSS_BLOCK = ("cross_block", "all+cross_block")  # ... and to_qk, to_v in front of its attention
 
 
 class HeadTuner(validate.ValidationPipeline):
@@ -41,12 +46,16 @@ class HeadTuner(validate.ValidationPipeline):
         super().__init__(model_conf, pair_batch=pair_batch, device=device, layer_report=True)
         matcher = self.model.matcher
         self.output_stage = params in OUTPUT_STAGE
+        self.cross_attention = params in CROSS_BLOCK
         prefixes = OUTPUT_STAGE[params] if self.output_stage else PREFIXES[params]
         touched = PREFIXES["all"]
         if self.output_stage:
             stage = f"transformers.{int(matcher.conf.n_layers) - 1}.cross_attn."
             prefixes += (stage + "to_out.", stage + "ffn.")
             touched += (stage + "to_out.", stage + "ffn.")
+            if self.cross_attention:
+                prefixes += (stage + "to_qk.", stage + "to_v.")
+                touched += (stage + "to_qk.", stage + "to_v.")
         self.trained = {n: p for n, p in matcher.named_parameters() if n.startswith(prefixes)}
         self.touched = [p for n, p in matcher.named_parameters() if n.startswith(touched)]
         cls = {"adam": torch.optim.Adam, "sgd": torch.optim.SGD}[optimizer]
@@ -64,7 +73,8 @@ class HeadTuner(validate.ValidationPipeline):
         numbers = super()._layer_numbers(datas, preds, pred, data)
         if self.tuning:
             g = torch.full((len(datas),), 1.0 / self._chunk_pairs, device=self.device)
-            self.model.layer_loss_backward(pred, data, grad_total=g, output_stage=self.output_stage)
+            self.model.layer_loss_backward(pred, data, grad_total=g, output_stage=self.output_stage,
+                                           cross_attention=self.cross_attention)
         return numbers
 
     def _run_chunk(self, chunk, first, results, log_file, step, view_key):
@@ -80,6 +90,8 @@ class HeadTuner(validate.ValidationPipeline):
         self.model.matcher.heads_updated()
         if self.output_stage:
             self.model.matcher.output_stage_updated()
+        if self.cross_attention:
+            self.model.matcher.cross_attention_updated()
         self.steps += 1
         return n
 

@@ -1,6 +1,6 @@
 """The training side of the LightGlue matcher: the validation loss, the kept-layers forward, the deep-supervision loss
-and the gradients of the heads, the exit tokens and the last layer's output stage (reference file
-gluefactory/models/matchers/lightglue.py:495-498,546-547,588-637).  `LightGlueTraining` is a mix-in of
+and the gradients of the heads, the exit tokens and the last layer's cross block -- its output stage and its attention
+(reference file gluefactory/models/matchers/lightglue.py:193-222,495-498,546-547,588-637).  `LightGlueTraining` is a mix-in of
 `lightglue.LightGlue`: it reads the module's configuration, parameters, packed weights and workspace and adds no state
 of its own, so every method is called on the matcher as before.
 """
@@ -272,7 +272,7 @@ class LightGlueTraining:
 
     # -- gradients of the training loss with respect to the heads and exit tokens (the trunk frozen) --------
     def layer_loss_backward(self, pred, data, grad_total=None, descriptor_grads=False, accumulate=True,
-                            output_stage=False):
+                            output_stage=False, cross_attention=False):
         """The gradients of `layer_loss`'s `total` with respect to the assignment heads and the exit tokens, what
         `torch.mean(losses["total"]).backward()` (gluefactory/train.py:1114) leaves in their `.grad` in the reference:
         the parameters of log_assignment[l] enter the loss through head l only (lightglue.py:589-616) and the token
@@ -301,7 +301,15 @@ class LightGlueTraining:
         (gfc_lg_ffn_backward on the state-dict weights, not the folded ones) is exactly what the reference's backward
         leaves in them.  `grad_output_stage_rows0/1` and `grad_output_stage_context0/1` are the kernel's two row outputs:
         the gradient at the rows the last cross block reads, through the residual and the first half of the
-        concatenation only, and at its attention context -- the operands an attention backward starts from."""
+        concatenation only, and at its attention context -- the operands an attention backward starts from.
+
+        With `cross_attention` (needs `output_stage`) those two go through the backward of that block's bidirectional
+        attention (gfc_lg_cross_attn_backward on the state-dict `to_qk` / `to_v`): the dict, and `.grad` under
+        `accumulate`, also hold `transformers.{L-1}.cross_attn.to_qk.weight/.bias` and `.to_v.weight/.bias` -- exact for
+        the same reason: the last cross block reaches the loss through head L - 1 alone (lightglue.py:193-222) -- and
+        the dict `grad_cross_block_rows0` [B,M,256] / `grad_cross_block_rows1` [B,N,256], the COMPLETE gradient at the
+        rows the last cross block reads (`grad_output_stage_rows` plus the attention's share), where the backward of
+        the last self block starts.  Without the keyword every result is what it was, bit for bit."""
         lp = _LayerPass(self, "layer_loss_backward", pred)
         nl, b, m, n, d, rows, device = lp.nl, lp.b, lp.m, lp.n, lp.d, lp.rows, lp.device
         if self.conf.matmul_precision != "fp32":
@@ -314,7 +322,11 @@ class LightGlueTraining:
             if missing:
                 raise ValueError(f"output_stage needs {missing} in the prediction: call "
                                  "forward_layers(data, keep_output_stage=True)")
+        elif cross_attention:
+            raise ValueError("cross_attention needs output_stage=True: the attention backward starts from the output "
+                             "stage's two row gradients")
         lp.open(data, "gfc_lg_head_backward", "gfc_lg_token_backward",
+                *(("gfc_lg_cross_attn_backward",) if cross_attention else ()),
                 by_rows=("gfc_lg_ffn_backward",) if output_stage else ())
         if grad_total is None:
             gtot = torch.full((b,), 1.0 / b, device=device)
@@ -352,7 +364,8 @@ class LightGlueTraining:
             grads[f"log_assignment.{i}.matchability.bias"] = dbm[i]
         for i in range(nl - 1):
             grads[f"token_confidence.{i}.token.0.weight"], grads[f"token_confidence.{i}.token.0.bias"] = dtw[i], dtb[i]
-        rows_out = self._output_stage_backward(lp, dy, grads) if output_stage else None
+        rows_out, x_mid, ctx = self._output_stage_backward(lp, dy, grads) if output_stage else (None, None, None)
+        dx_mid = self._cross_attention_backward(lp, x_mid, ctx, rows_out, grads) if cross_attention else None
         if accumulate:
             for name, grad in grads.items():
                 param = self.get_parameter(name)
@@ -366,6 +379,8 @@ class LightGlueTraining:
         if rows_out is not None:
             put_sides(grads, "grad_output_stage_rows", split_sides(rows_out[0], b, m, n))
             put_sides(grads, "grad_output_stage_context", split_sides(rows_out[1], b, m, n))
+        if dx_mid is not None:
+            put_sides(grads, "grad_cross_block_rows", split_sides(dx_mid, b, m, n))
         return grads
 
     # the last cross block's parameters behind its output stage, by their names under transformers.{L-1}.cross_attn.
@@ -375,7 +390,7 @@ class LightGlueTraining:
     def _output_stage_backward(self, lp, dy, grads):
         """Head L - 1's direct gradient dy [B*M + B*N, 256] through the last layer's output stage (gfc_lg_ffn_backward on
         the rows and the context the prediction kept): the eight parameter gradients into `grads`; returns the kernel's
-        two row outputs [2, B*M + B*N, 256]."""
+        two row outputs [2, B*M + B*N, 256], and the packed rows and context it read."""
         pred, rows, d = lp.pred, lp.rows, lp.d
         w = self._output_stage_weights(lp.device)
         x = pack_sides(pred["output_stage_rows0"].float().contiguous(), pred["output_stage_rows1"].float().contiguous())
@@ -392,7 +407,34 @@ class LightGlueTraining:
                  og["ffn.3.weight"], og["ffn.3.bias"], rows_out[0], rows_out[1], lp.ws, lp.ws.numel())
         for name in self._OUTPUT_STAGE:
             grads[f"transformers.{lp.nl - 1}.cross_attn.{name}"] = og[name]
-        return rows_out
+        return rows_out, x, ctx
+
+    # ... and in front of its attention
+    _CROSS_ATTENTION = ("to_qk.weight", "to_qk.bias", "to_v.weight", "to_v.bias")
+
+    def _cross_attention_backward(self, lp, x, ctx, rows_out, grads):
+        """The output stage's two row gradients (rows_out[0] at the rows through the residual and the concatenation,
+        rows_out[1] at the context) through the last cross block's attention (gfc_lg_cross_attn_backward on the packed
+        rows x and context ctx the prediction kept): the four parameter gradients into `grads`; returns the complete
+        gradient at x [B*M + B*N, 256]."""
+        w = self._cross_attention_weights(lp.device)
+        ag = {name: torch.empty_like(w[name]) for name in self._CROSS_ATTENTION}
+        dx = torch.empty((lp.rows, lp.d), device=lp.device)
+        nat.call("gfc_lg_cross_attn_backward", x, ctx, rows_out[1], rows_out[0], w["to_qk.weight"], w["to_qk.bias"],
+                 w["to_v.weight"], w["to_v.bias"], lp.b, lp.m, lp.n, ag["to_qk.weight"], ag["to_qk.bias"],
+                 ag["to_v.weight"], ag["to_v.bias"], dx, lp.ws, lp.ws.numel())
+        for name in self._CROSS_ATTENTION:
+            grads[f"transformers.{lp.nl - 1}.cross_attn.{name}"] = ag[name]
+        return dx
+
+    def _cross_attention_params(self):
+        ca = self.transformers[self.conf.n_layers - 1].cross_attn
+        return {name: ca.get_parameter(name) for name in self._CROSS_ATTENTION}
+
+    def _cross_attention_weights(self, device):
+        """fp32 device copies of `to_qk` and `to_v` of the last cross block, as `_output_stage_weights` holds its own."""
+        return self._derive("cross", lambda: {name: p.detach().to(device=device, dtype=torch.float32).contiguous()
+                                              for name, p in self._cross_attention_params().items()})
 
     def _output_stage_params(self):
         ca = self.transformers[self.conf.n_layers - 1].cross_attn
@@ -448,5 +490,29 @@ class LightGlueTraining:
             if stage is not None and stage[0] is self._packed:
                 for name, param in self._output_stage_params().items():
                     t = stage[1][name]
+                    if t.data_ptr() != param.data_ptr():
+                        t.copy_(param.detach())
+
+    def cross_attention_updated(self):
+        """Call after `to_qk` / `to_v` of the last layer's cross block were changed in place (optimizer.step()): the
+        packed [to_qk; to_v] weight and bias of that layer are written again IN PLACE, at the addresses captured graphs
+        replay, the fp16 copy is rounded again from the fp32 one and the copies the backward reads are refreshed.  The
+        result is what a fresh module loaded from `state_dict()` packs, bit for bit; nothing else is touched."""
+        if self._packed is None:
+            return
+        p, l, d = self._packed[0], self.conf.n_layers - 1, self.conf.descriptor_dim
+        by_ptr = {t.data_ptr(): t for t in self._packed[1]}
+        ca = self.transformers[l].cross_attn
+        with torch.no_grad():
+            w32, b32 = by_ptr[p.c_qkv_w[l]], by_ptr[p.c_qkv_b[l]]
+            for t32, qk, v in ((w32, ca.to_qk.weight, ca.to_v.weight), (b32, ca.to_qk.bias, ca.to_v.bias)):
+                t32[:d].copy_(qk.detach())
+                t32[d:].copy_(v.detach())
+            if p.c_qkv_w16[l]:
+                by_ptr[p.c_qkv_w16[l]].copy_(w32)
+            cross = self._derived.cross
+            if cross is not None and cross[0] is self._packed:
+                for name, param in self._cross_attention_params().items():
+                    t = cross[1][name]
                     if t.data_ptr() != param.data_ptr():
                         t.copy_(param.detach())

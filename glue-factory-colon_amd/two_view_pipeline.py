@@ -288,7 +288,8 @@ class TwoViewPipeline(BaseModel):
 
     def layer_loss_backward(self, pred, data, **kw):
         """The matcher's `layer_loss_backward` (the gradients of `layer_loss`'s total with respect to the assignment
-        heads and exit tokens) on a `forward_layers` prediction, with the labels built as `layer_loss` builds them."""
+        heads and exit tokens; with `output_stage` / `cross_attention` also the last cross block) on a `forward_layers`
+        prediction, with the labels built as `layer_loss` builds them."""
         if hasattr(self, "ground_truth") and not conf_get(self.conf, "run_gt_in_forward"):
             pred = self._with_gt(pred, data)
         return self.matcher.layer_loss_backward(pred, {**pred, **data}, **kw)
