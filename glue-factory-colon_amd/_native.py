@@ -3,7 +3,8 @@ include/gfc_amd_validation.h, include/gfc_amd_sparse_map.h and include/gfc_amd_d
 the score matrix evaluated once, include/gfc_amd_cross_attention.h; for the per-layer scores of the deep-supervision loss,
 include/gfc_amd_layer_scores.h; for the head and exit-token gradients, include/gfc_amd_head_backward.h; for the FFN-block
 backward and the last layer's kept tensors, include/gfc_amd_ffn_backward.h; for the cross-attention backward,
-include/gfc_amd_cross_attn_backward.h).
+include/gfc_amd_cross_attn_backward.h; for the self-attention backward and the layer that keeps the self attention's
+context, include/gfc_amd_self_attn_backward.h).
 
 The library is the product: if it is missing or a call fails, this module raises --
 there is no PyTorch / CPU fallback for any arithmetic on the path.
@@ -28,6 +29,7 @@ LAYER_SCORES_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_a
 HEAD_BACKWARD_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_head_backward.h")
 FFN_BACKWARD_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_ffn_backward.h")
 CROSS_ATTN_BACKWARD_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_cross_attn_backward.h")
+SELF_ATTN_BACKWARD_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "gfc_amd_self_attn_backward.h")
 
 
 class NativeError(RuntimeError):
@@ -142,6 +144,11 @@ CROSS_ATTN_BACKWARD_FUNCTIONS = _load_functions_header(
     CROSS_ATTN_BACKWARD_HEADER_PATH, {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS, **DENSE_WARP_FUNCTIONS,
                                       **CROSS_ATTENTION_FUNCTIONS, **LAYER_SCORES_FUNCTIONS, **HEAD_BACKWARD_FUNCTIONS,
                                       **FFN_BACKWARD_FUNCTIONS})
+# include/gfc_amd_self_attn_backward.h: the self-attention backward, the Wqkv gradients around it, the kept self context
+SELF_ATTN_BACKWARD_FUNCTIONS = _load_functions_header(
+    SELF_ATTN_BACKWARD_HEADER_PATH, {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS, **DENSE_WARP_FUNCTIONS,
+                                     **CROSS_ATTENTION_FUNCTIONS, **LAYER_SCORES_FUNCTIONS, **HEAD_BACKWARD_FUNCTIONS,
+                                     **FFN_BACKWARD_FUNCTIONS, **CROSS_ATTN_BACKWARD_FUNCTIONS})
 globals().update(CONSTANTS)  # GFC_LG_MAX_LAYERS, GFC_LG_FP16, GFC_CAM_RADIAL, GFC_RS_AREA, ...
 STATUS = {v: k for k, v in ENUMS["gfc_status"].items()}
 
@@ -198,9 +205,10 @@ LAYER_SCORES_SIGNATURES = _signatures(LAYER_SCORES_FUNCTIONS)  # include/gfc_amd
 HEAD_BACKWARD_SIGNATURES = _signatures(HEAD_BACKWARD_FUNCTIONS)  # include/gfc_amd_head_backward.h
 FFN_BACKWARD_SIGNATURES = _signatures(FFN_BACKWARD_FUNCTIONS)  # include/gfc_amd_ffn_backward.h
 CROSS_ATTN_BACKWARD_SIGNATURES = _signatures(CROSS_ATTN_BACKWARD_FUNCTIONS)  # include/gfc_amd_cross_attn_backward.h
+SELF_ATTN_BACKWARD_SIGNATURES = _signatures(SELF_ATTN_BACKWARD_FUNCTIONS)  # include/gfc_amd_self_attn_backward.h
 _ALL_FUNCTIONS = {**FUNCTIONS, **VALIDATION_FUNCTIONS, **SPARSE_MAP_FUNCTIONS, **DENSE_WARP_FUNCTIONS,
                   **CROSS_ATTENTION_FUNCTIONS, **LAYER_SCORES_FUNCTIONS, **HEAD_BACKWARD_FUNCTIONS,
-                  **FFN_BACKWARD_FUNCTIONS, **CROSS_ATTN_BACKWARD_FUNCTIONS}
+                  **FFN_BACKWARD_FUNCTIONS, **CROSS_ATTN_BACKWARD_FUNCTIONS, **SELF_ATTN_BACKWARD_FUNCTIONS}
 
 _DTYPES = {"float": (torch.float32,), "int32_t": (torch.int32,), "int": (torch.int32,), "int64_t": (torch.int64,),
            "double": (torch.float64,), "uint8_t": (torch.uint8, torch.bool), "unsigned char": (torch.uint8, torch.bool),
@@ -274,7 +282,8 @@ def lib():
         for name, (res, args) in {**SIGNATURES, **VALIDATION_SIGNATURES, **SPARSE_MAP_SIGNATURES,
                                   **DENSE_WARP_SIGNATURES, **CROSS_ATTENTION_SIGNATURES,
                                   **LAYER_SCORES_SIGNATURES, **HEAD_BACKWARD_SIGNATURES,
-                                  **FFN_BACKWARD_SIGNATURES, **CROSS_ATTN_BACKWARD_SIGNATURES}.items():
+                                  **FFN_BACKWARD_SIGNATURES, **CROSS_ATTN_BACKWARD_SIGNATURES,
+                                  **SELF_ATTN_BACKWARD_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -384,7 +384,8 @@ struct LgCrossStored { int B, M, N, chunk; void* sim; size_t sim_bytes; };
 static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, const float* csb,
                          int R, const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
                          size_t ws_bytes, void* stream, const float* x_in = nullptr, gfc_trace* tr = nullptr,
-                         const LgCrossStored* xst = nullptr, float* keep_mid = nullptr, float* keep_ctx = nullptr);
+                         const LgCrossStored* xst = nullptr, float* keep_mid = nullptr, float* keep_ctx = nullptr,
+                         float* keep_self = nullptr);
 
 extern "C" int gfc_lg_layer(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, int R,
                             const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
@@ -435,12 +436,13 @@ static bool lg_f16_layer_ok(const gfc_lg_params* p, int l) {
 // and everything after it live in x.  gfc_lg_forward_packed passes the caller's descriptors for layer 0, so that they
 // are never copied into the row buffer.  tr (optional): event pairs around the two attention launches.  xst (optional,
 // fp32 only): the cross block evaluates sim once; still one event pair around all of its launches.  keep_mid / keep_ctx
-// (optional, fp32 only, [R,256]): copies of the rows the cross block reads and of the cross attention's context.
+// (optional, fp32 only, [R,256]): copies of the rows the cross block reads and of the cross attention's context;
+// keep_self (likewise): a copy of the SELF attention's context.
 static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, const float* csb,
                          int R, const int32_t* self_p, const int32_t* cross_p, int n_problems, int maxn, void* ws,
                          size_t ws_bytes, void* stream, const float* x_in, gfc_trace* tr, const LgCrossStored* xst,
-                         float* keep_mid, float* keep_ctx) {
-  if ((keep_mid || keep_ctx) && (!p || p->precision != GFC_LG_FP32)) return GFC_ERR_INVALID;
+                         float* keep_mid, float* keep_ctx, float* keep_self) {
+  if ((keep_mid || keep_ctx || keep_self) && (!p || p->precision != GFC_LG_FP32)) return GFC_ERR_INVALID;
   if (!p || !x || !cosb || !sinb || !self_p || !cross_p || !ws || R <= 0 || n_problems <= 0 || maxn <= 0)
     return GFC_ERR_INVALID;
   if (l < 0 || l >= p->n_layers) return GFC_ERR_INVALID;
@@ -496,6 +498,9 @@ static int lg_layer_impl(const gfc_lg_params* p, int l, float* x, const float* c
       GFC_TRY(proj(xs, false, P::w(p->wqkv[l], p->wqkv16[l]), p->bqkv[l], csb, csb ? nullptr : cosb,
                    csb ? nullptr : sinb, 512, qkv, 768));
     GFC_TRY(attn(qkv, 768, qkv + 256, 768, qkv + 512, 768, self_p));
+    if (keep_self &&
+        hipMemcpyAsync(keep_self, ctx, (size_t)R * D * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return GFC_ERR_LAUNCH;
     // out_proj is either a GEMM of its own, or (s_out_w == NULL) already folded into ffn0's second
     // K block at load time: [x | ctx] . [W0a | W0b.Wo]^T + (b0 + W0b.bo)
     const T* a1s = ctx;
@@ -561,7 +566,7 @@ extern "C" size_t gfc_lg_layer_pairs_workspace_bytes(int B, int M, int N) {
 
 static int lg_layer_pairs_impl(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, int B, int M,
                                int N, const int32_t* self_p, const int32_t* cross_p, float* keep_mid, float* keep_ctx,
-                               void* ws, size_t ws_bytes, void* stream) {
+                               float* keep_self, void* ws, size_t ws_bytes, void* stream) {
   LgLayerPairsWs L;
   if (!p || !ws || !lg_layer_pairs_ws(B, M, N, L)) return GFC_ERR_INVALID;
   if (ws_bytes < L.total) return GFC_ERR_WORKSPACE;
@@ -569,13 +574,14 @@ static int lg_layer_pairs_impl(const gfc_lg_params* p, int l, float* x, const fl
   const LgCrossStored xst = {B, M, N, L.chunk, base + L.sim, L.sim_bytes};
   const bool stored = L.chunk > 0 && p->precision == GFC_LG_FP32 && gfc_knobs().cross_stored != 0;
   return lg_layer_impl(p, l, x, cosb, sinb, nullptr, B * (M + N), self_p, cross_p, 2 * B, M > N ? M : N, base + L.layer,
-                       L.layer_bytes, stream, nullptr, nullptr, stored ? &xst : nullptr, keep_mid, keep_ctx);
+                       L.layer_bytes, stream, nullptr, nullptr, stored ? &xst : nullptr, keep_mid, keep_ctx, keep_self);
 }
 
 extern "C" int gfc_lg_layer_pairs(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb, int B,
                                   int M, int N, const int32_t* self_p, const int32_t* cross_p, void* ws, size_t ws_bytes,
                                   void* stream) {
-  return lg_layer_pairs_impl(p, l, x, cosb, sinb, B, M, N, self_p, cross_p, nullptr, nullptr, ws, ws_bytes, stream);
+  return lg_layer_pairs_impl(p, l, x, cosb, sinb, B, M, N, self_p, cross_p, nullptr, nullptr, nullptr, ws, ws_bytes,
+                             stream);
 }
 
 // ... with the rows the cross block reads and the cross attention's context kept (include/gfc_amd_ffn_backward.h)
@@ -583,7 +589,16 @@ extern "C" int gfc_lg_layer_pairs_keep(const gfc_lg_params* p, int l, float* x, 
                                        int B, int M, int N, const int32_t* self_p, const int32_t* cross_p, float* x_mid,
                                        float* ctx, void* ws, size_t ws_bytes, void* stream) {
   if (!x_mid || !ctx) return GFC_ERR_INVALID;
-  return lg_layer_pairs_impl(p, l, x, cosb, sinb, B, M, N, self_p, cross_p, x_mid, ctx, ws, ws_bytes, stream);
+  return lg_layer_pairs_impl(p, l, x, cosb, sinb, B, M, N, self_p, cross_p, x_mid, ctx, nullptr, ws, ws_bytes, stream);
+}
+
+// ... and the self attention's context too (include/gfc_amd_self_attn_backward.h)
+extern "C" int gfc_lg_layer_pairs_keep_self(const gfc_lg_params* p, int l, float* x, const float* cosb, const float* sinb,
+                                            int B, int M, int N, const int32_t* self_p, const int32_t* cross_p,
+                                            float* x_mid, float* ctx, float* ctx_self, void* ws, size_t ws_bytes,
+                                            void* stream) {
+  if (!x_mid || !ctx || !ctx_self) return GFC_ERR_INVALID;
+  return lg_layer_pairs_impl(p, l, x, cosb, sinb, B, M, N, self_p, cross_p, x_mid, ctx, ctx_self, ws, ws_bytes, stream);
 }
 
 // token confidence / matchability logits: out[row] = (sigmoid?)(x[row,:256] . w + b)   (lightglue.py:69-80,290-291)

@@ -19,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-SOURCES = ["runtime.hip", "conv.hip", "conv_wino.hip", "conv_wino43.hip", "gemm.hip", "attention.hip", "lg_fp16.hip", "sp_detect.hip", "sp_heads.hip", "disk_detect.hip", "disk_unet.hip", "lg_misc.hip", "lg_adaptive.hip", "eval_metrics.hip", "eval_pose.hip", "gt_matches.hip", "gt_sparse_map.hip", "gt_dense_warp.hip", "lg_validation.hip", "lg_layer_scores.hip", "lg_head_backward.hip", "lg_ffn_backward.hip", "lg_cross_attn_backward.hip", "ransac.hip", "relpose.hip", "preprocess.hip", "warp.hip", "superglue.hip", "sift.hip", "api.hip"]
+SOURCES = ["runtime.hip", "conv.hip", "conv_wino.hip", "conv_wino43.hip", "gemm.hip", "attention.hip", "lg_fp16.hip", "sp_detect.hip", "sp_heads.hip", "disk_detect.hip", "disk_unet.hip", "lg_misc.hip", "lg_adaptive.hip", "eval_metrics.hip", "eval_pose.hip", "gt_matches.hip", "gt_sparse_map.hip", "gt_dense_warp.hip", "lg_validation.hip", "lg_layer_scores.hip", "lg_head_backward.hip", "lg_ffn_backward.hip", "lg_cross_attn_backward.hip", "lg_self_attn_backward.hip", "ransac.hip", "relpose.hip", "preprocess.hip", "warp.hip", "superglue.hip", "sift.hip", "api.hip"]
 HEADERS = ["common.h", "block_select.h", "runtime.h", "eval_common.h", "gt_sweep.h", "ransac_common.h", "relpose_solver.h", "lg_rowdot.h", "lg_backward_common.h", os.path.join(PKG, "..", "include", "gfc_amd.h"),
            os.path.join(PKG, "..", "include", "gfc_amd_validation.h"),
            os.path.join(PKG, "..", "include", "gfc_amd_sparse_map.h"),
@@ -28,7 +28,8 @@ HEADERS = ["common.h", "block_select.h", "runtime.h", "eval_common.h", "gt_sweep
            os.path.join(PKG, "..", "include", "gfc_amd_layer_scores.h"),
            os.path.join(PKG, "..", "include", "gfc_amd_head_backward.h"),
            os.path.join(PKG, "..", "include", "gfc_amd_ffn_backward.h"),
-           os.path.join(PKG, "..", "include", "gfc_amd_cross_attn_backward.h")]
+           os.path.join(PKG, "..", "include", "gfc_amd_cross_attn_backward.h"),
+           os.path.join(PKG, "..", "include", "gfc_amd_self_attn_backward.h")]
 LIB = os.path.join(PKG, "libgfc_amd.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 VERSION_UNIT = "api.hip"  # compiled with -DGFC_SOURCE_HASH="<hash>": gfc_version() reports it

@@ -4,7 +4,7 @@ reference's training loss (`LightGlue.layer_loss_backward`); the trunk, `input_p
 never touched.
 
     python -m glue_factory_colon_amd.finetune_heads --data_dir D --dataset {homographies,posed_images,endomapper}
-        [--params {tokens,heads,all,output_stage,all+output_stage,cross_block,all+cross_block}] [--lr 1e-3] [--optimizer {adam,sgd}] [--clip_grad G] [--epochs E]
+        [--params {tokens,heads,all,output_stage,all+output_stage,cross_block,all+cross_block,last_layer,all+last_layer}] [--lr 1e-3] [--optimizer {adam,sgd}] [--clip_grad G] [--epochs E]
         [--max_steps S] [--pair_batch N] --out FILE
 
 The pairs come from `validate`'s feeders, with its ground-truth options and its grouping: inside a `--pair_batch` chunk
@@ -16,7 +16,9 @@ re-fits `to_out` and `ffn` of the last layer's cross block (eight tensors, about
 stays frozen, and every step also ends with `output_stage_updated()`.  `--params cross_block` re-fits the twelve tensors
 of the last cross block (the output stage and `to_qk`, `to_v`, through `layer_loss_backward(output_stage=True,
 cross_attention=True)`), `all+cross_block` those with the heads and tokens; every such step also ends with
-`cross_attention_updated()`.  `loss/total_deep`,
+`cross_attention_updated()`.  `--params last_layer` re-fits all 22 tensors of the last layer (the cross block and the
+self block in front of it, through `layer_loss_backward(..., self_block=True)`), `all+last_layer` those with the heads and
+tokens; every such step also ends with `self_block_updated()`.  `loss/total_deep`,
 `loss/confidence` and the per-layer table of `validate --layer_report` are printed before and after, and the matcher's
 `state_dict()` is written to `--out`, which `conf.weights = FILE` loads.  No schedules, no checkpoint resume, no mixed
 precision.
@@ -33,8 +35,9 @@ PREFIXES = {"tokens": ("token_confidence.",), "heads": ("log_assignment.",),
             "all": ("token_confidence.", "log_assignment.")}
 # choices that also train the last layer's output stage -> the prefixes of the heads and tokens trained with it
 OUTPUT_STAGE = {"output_stage": (), "all+output_stage": PREFIXES["all"], "cross_block": (),
-                "all+cross_block": PREFIXES["all"]}
-CROSS_BLOCK = ("cross_block", "all+cross_block")  # ... and to_qk, to_v in front of its attention
+                "all+cross_block": PREFIXES["all"], "last_layer": (), "all+last_layer": PREFIXES["all"]}
+CROSS_BLOCK = ("cross_block", "all+cross_block", "last_layer", "all+last_layer")  # ... and to_qk, to_v in front of its attention
+LAST_LAYER = ("last_layer", "all+last_layer")  # ... and the self block in front of the cross block
 
 
 class HeadTuner(validate.ValidationPipeline):
@@ -47,6 +50,7 @@ class HeadTuner(validate.ValidationPipeline):
         matcher = self.model.matcher
         self.output_stage = params in OUTPUT_STAGE
         self.cross_attention = params in CROSS_BLOCK
+        self.self_block = params in LAST_LAYER
         prefixes = OUTPUT_STAGE[params] if self.output_stage else PREFIXES[params]
         touched = PREFIXES["all"]
         if self.output_stage:
@@ -56,6 +60,10 @@ class HeadTuner(validate.ValidationPipeline):
             if self.cross_attention:
                 prefixes += (stage + "to_qk.", stage + "to_v.")
                 touched += (stage + "to_qk.", stage + "to_v.")
+            if self.self_block:
+                block = f"transformers.{int(matcher.conf.n_layers) - 1}.self_attn."
+                prefixes += (block,)
+                touched += (block,)
         self.trained = {n: p for n, p in matcher.named_parameters() if n.startswith(prefixes)}
         self.touched = [p for n, p in matcher.named_parameters() if n.startswith(touched)]
         cls = {"adam": torch.optim.Adam, "sgd": torch.optim.SGD}[optimizer]
@@ -67,14 +75,15 @@ class HeadTuner(validate.ValidationPipeline):
 
     def _forward_layers(self, stacked):
         # the rows and context the output stage's backward starts from are kept only while a step needs them
-        return self.model.matcher.forward_layers(stacked, keep_output_stage=self.tuning and self.output_stage)
+        return self.model.matcher.forward_layers(stacked, keep_output_stage=self.tuning and self.output_stage,
+                                                 keep_self_block=self.tuning and self.self_block)
 
     def _layer_numbers(self, datas, preds, pred, data):
         numbers = super()._layer_numbers(datas, preds, pred, data)
         if self.tuning:
             g = torch.full((len(datas),), 1.0 / self._chunk_pairs, device=self.device)
             self.model.layer_loss_backward(pred, data, grad_total=g, output_stage=self.output_stage,
-                                           cross_attention=self.cross_attention)
+                                           cross_attention=self.cross_attention, self_block=self.self_block)
         return numbers
 
     def _run_chunk(self, chunk, first, results, log_file, step, view_key):
@@ -92,6 +101,8 @@ class HeadTuner(validate.ValidationPipeline):
             self.model.matcher.output_stage_updated()
         if self.cross_attention:
             self.model.matcher.cross_attention_updated()
+        if self.self_block:
+            self.model.matcher.self_block_updated()
         self.steps += 1
         return n
 

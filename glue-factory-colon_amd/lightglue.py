@@ -99,6 +99,7 @@ class _Derived:
         self.thresholds = None  # confidence_thresholds as a host list
         self.stage = None  # the output stage's unfolded fp32 device copies, by name (lightglue_training.py)
         self.cross = None  # to_qk / to_v of the last cross block, fp32 device copies, by name (lightglue_training.py)
+        self.selfb = None  # out_proj / ffn of the last self block, fp32 device copies, by name (lightglue_training.py)
 
 
 class LightGlue(LightGlueTraining, nn.Module):

@@ -1,6 +1,7 @@
 """The training side of the LightGlue matcher: the validation loss, the kept-layers forward, the deep-supervision loss
-and the gradients of the heads, the exit tokens and the last layer's cross block -- its output stage and its attention
-(reference file gluefactory/models/matchers/lightglue.py:193-222,495-498,546-547,588-637).  `LightGlueTraining` is a mix-in of
+and the gradients of the heads, the exit tokens and the last layer -- its cross block (output stage and attention) and
+its self block (FFN part, rotary attention and Wqkv)
+(reference file gluefactory/models/matchers/lightglue.py:151-164,193-222,495-498,546-547,588-637).  `LightGlueTraining` is a mix-in of
 `lightglue.LightGlue`: it reads the module's configuration, parameters, packed weights and workspace and adds no state
 of its own, so every method is called on the matcher as before.
 """
@@ -131,7 +132,7 @@ class LightGlueTraining:
         return losses, {k: d[k] for k in KEYS}
 
     # -- every layer kept: the training-mode forward and loss of the reference, forward only ---------------
-    def forward_layers(self, data: dict, keep_output_stage: bool = False) -> dict:
+    def forward_layers(self, data: dict, keep_output_stage: bool = False, keep_self_block: bool = False) -> dict:
         """The reference's forward under `model.train()` (lightglue.py:495-498,546-547): full depth, every layer's
         descriptors kept -- `ref_descriptors0` [B,L,M,256], `ref_descriptors1` [B,L,N,256], index l the output of
         transformer l; every other key as `forward` returns it.  LightGlue has no dropout and no batch norm, so this is
@@ -145,7 +146,16 @@ class LightGlueTraining:
         and the prediction also holds what the backward of that layer's output stage starts from
         (`layer_loss_backward(output_stage=True)`): `output_stage_rows0` [B,M,256] / `output_stage_rows1` [B,N,256], the
         rows the last cross block reads, and `output_stage_context0/1`, its attention context before `to_out`: views of
-        two [B*M + B*N, 256] buffers.  Every other key is the default call's, bit for bit."""
+        two [B*M + B*N, 256] buffers.  Every other key is the default call's, bit for bit.
+        With `keep_self_block` (needs `keep_output_stage`) the last layer runs through gfc_lg_layer_pairs_keep_self (one
+        more copy) and the prediction also holds what `layer_loss_backward(self_block=True)` starts from:
+        `self_block_context0/1`, the last SELF attention's context before `out_proj`, views of a third buffer, and the
+        rotary tables of the packed rows, `self_block_cos` / `self_block_sin` [B*M + B*N, 64] -- they are kept, not
+        recomputed, because the backward sees the labels and not the key points.  The rows the last self block reads
+        are `ref_descriptors0/1[:, L-2]`."""
+        if keep_self_block and not keep_output_stage:
+            raise ValueError("keep_self_block needs keep_output_stage=True: the self block's backward starts from the "
+                             "cross block's")
         self._check_ready(data)
         conf = self.conf
         _refuse_adaptive(conf, "forward_layers")
@@ -163,6 +173,11 @@ class LightGlueTraining:
             if keep_output_stage:
                 for key in ("output_stage_rows", "output_stage_context"):
                     put_sides(pred, key, (torch.zeros((b, m, d), device=device), torch.zeros((b, n, d), device=device)))
+            if keep_self_block:
+                put_sides(pred, "self_block_context", (torch.zeros((b, m, d), device=device),
+                                                       torch.zeros((b, n, d), device=device)))
+                pred["self_block_cos"] = torch.zeros((b * (m + n), 64), device=device)
+                pred["self_block_sin"] = torch.zeros((b * (m + n), 64), device=device)
             return pred
         params = self._packed[0]
         rows = b * (m + n)
@@ -188,13 +203,17 @@ class LightGlueTraining:
         # on it evaluates sim once), so that the last layer is `forward`'s at every batch size
         ws = self._ws.get(max(nat.call("gfc_lg_layer_pairs_workspace_bytes", b, m, n),
                               nat.call("gfc_lg_assign_workspace_bytes", b, m, n)), device)
-        kept = torch.empty((2, rows, d), device=device) if keep_output_stage else None
+        kept = torch.empty((3 if keep_self_block else 2, rows, d), device=device) if keep_output_stage else None
         for i in range(nl):
             if i > 0:
                 stack[i].copy_(stack[i - 1])
             if kept is not None and i == nl - 1:
-                nat.call("gfc_lg_layer_pairs_keep", ctypes.byref(params), i, stack[i], cos, sin, b, m, n, self_p, cross_p,
-                         kept[0], kept[1], ws, ws.numel())
+                if keep_self_block:
+                    nat.call("gfc_lg_layer_pairs_keep_self", ctypes.byref(params), i, stack[i], cos, sin, b, m, n, self_p,
+                             cross_p, kept[0], kept[1], kept[2], ws, ws.numel())
+                else:
+                    nat.call("gfc_lg_layer_pairs_keep", ctypes.byref(params), i, stack[i], cos, sin, b, m, n, self_p,
+                             cross_p, kept[0], kept[1], ws, ws.numel())
                 continue
             nat.call("gfc_lg_layer_pairs", ctypes.byref(params), i, stack[i], cos, sin, b, m, n, self_p, cross_p, ws,
                      ws.numel())
@@ -206,6 +225,9 @@ class LightGlueTraining:
         if kept is not None:
             put_sides(pred, "output_stage_rows", split_sides(kept[0], b, m, n))
             put_sides(pred, "output_stage_context", split_sides(kept[1], b, m, n))
+        if keep_self_block:
+            put_sides(pred, "self_block_context", split_sides(kept[2], b, m, n))
+            pred["self_block_cos"], pred["self_block_sin"] = cos, sin
         return pred
 
     def layer_loss(self, pred, data):
@@ -272,7 +294,7 @@ class LightGlueTraining:
 
     # -- gradients of the training loss with respect to the heads and exit tokens (the trunk frozen) --------
     def layer_loss_backward(self, pred, data, grad_total=None, descriptor_grads=False, accumulate=True,
-                            output_stage=False, cross_attention=False):
+                            output_stage=False, cross_attention=False, self_block=False):
         """The gradients of `layer_loss`'s `total` with respect to the assignment heads and the exit tokens, what
         `torch.mean(losses["total"]).backward()` (gluefactory/train.py:1114) leaves in their `.grad` in the reference:
         the parameters of log_assignment[l] enter the loss through head l only (lightglue.py:589-616) and the token
@@ -309,7 +331,20 @@ class LightGlueTraining:
         the same reason: the last cross block reaches the loss through head L - 1 alone (lightglue.py:193-222) -- and
         the dict `grad_cross_block_rows0` [B,M,256] / `grad_cross_block_rows1` [B,N,256], the COMPLETE gradient at the
         rows the last cross block reads (`grad_output_stage_rows` plus the attention's share), where the backward of
-        the last self block starts.  Without the keyword every result is what it was, bit for bit."""
+        the last self block starts.  Without the keyword every result is what it was, bit for bit.
+
+        With `self_block` (needs `cross_attention` and a prediction of `forward_layers(keep_self_block=True)`) that
+        gradient goes through the last SELF block (lightglue.py:151-164): gfc_lg_ffn_backward on the state-dict
+        `out_proj`, `ffn.0/.1/.3` of `transformers.{L-1}.self_attn` with the rows of layer L - 2 and the kept self
+        context, then gfc_lg_self_attn_backward (rotary attention and `Wqkv`, on the packed row order; the gradients are
+        mapped back to the state dict's by the inverse of `_pack`'s index, which is exact).  The dict, and `.grad` under
+        `accumulate`, also hold the ten tensors of `transformers.{L-1}.self_attn.` -- exact for the same reason: the
+        last self block reaches the loss through the last cross block and head L - 1 alone -- so all 22 tensors of
+        layer L - 1 have their gradients.  The dict also holds `grad_self_block_rows0/1`, the gradient at layer L - 1's
+        input rows through layer L - 1 alone, and `grad_layer_input_rows0/1`, the same plus head L - 2's direct
+        descriptor gradient: the COMPLETE gradient at `ref_descriptors0/1[:, L-2]`, where the backward of layer L - 2
+        would start.  No gradient for `posenc.Wr` is produced: the rotary tables get gradient from every layer.
+        Without the keyword every result is what it was, bit for bit."""
         lp = _LayerPass(self, "layer_loss_backward", pred)
         nl, b, m, n, d, rows, device = lp.nl, lp.b, lp.m, lp.n, lp.d, lp.rows, lp.device
         if self.conf.matmul_precision != "fp32":
@@ -325,8 +360,18 @@ class LightGlueTraining:
         elif cross_attention:
             raise ValueError("cross_attention needs output_stage=True: the attention backward starts from the output "
                              "stage's two row gradients")
+        if self_block:
+            if not cross_attention:
+                raise ValueError("self_block needs cross_attention=True: the self block's backward starts from the "
+                                 "complete gradient at the rows the cross block reads")
+            missing = [k for k in ("self_block_context0", "self_block_context1", "self_block_cos", "self_block_sin")
+                       if k not in pred]
+            if missing:
+                raise ValueError(f"self_block needs {missing} in the prediction: call "
+                                 "forward_layers(data, keep_output_stage=True, keep_self_block=True)")
         lp.open(data, "gfc_lg_head_backward", "gfc_lg_token_backward",
                 *(("gfc_lg_cross_attn_backward",) if cross_attention else ()),
+                *(("gfc_lg_self_attn_backward",) if self_block else ()),
                 by_rows=("gfc_lg_ffn_backward",) if output_stage else ())
         if grad_total is None:
             gtot = torch.full((b,), 1.0 / b, device=device)
@@ -343,13 +388,16 @@ class LightGlueTraining:
         dx = torch.empty((nl, rows, d), device=device) if descriptor_grads else None
         # head L - 1's direct gradient, for that layer only when the whole buffer is not asked for
         dy = None if not output_stage else dx[nl - 1] if dx is not None else torch.empty((rows, d), device=device)
+        # ... and head L - 2's, which completes the gradient at the last layer's input rows
+        dy_in = None if not self_block else dx[nl - 2] if dx is not None else torch.empty((rows, d), device=device)
         correct = torch.empty((rows,), device=device, dtype=torch.uint8)
         sc = torch.empty((b, 6), device=device)
         for i in range(nl):
             x = lp.layer_rows(i)
+            own = dy if i == nl - 1 else dy_in if i == nl - 2 else None
             nat.call("gfc_lg_head_backward", ctypes.byref(lp.params), i, x, x[lp.bm:], lp.gt0, lp.gt1, lp.gta, g[i],
                      lp.balancing, b, m, n, dwf[i], dbf[i], dwm[i], dbm[i],
-                     dy if i == nl - 1 and dy is not None else None if dx is None else dx[i], lp.ws, lp.ws.numel())
+                     own if own is not None else None if dx is None else dx[i], lp.ws, lp.ws.numel())
             if i == nl - 1:
                 break
             lp.assign(i, x)
@@ -366,6 +414,7 @@ class LightGlueTraining:
             grads[f"token_confidence.{i}.token.0.weight"], grads[f"token_confidence.{i}.token.0.bias"] = dtw[i], dtb[i]
         rows_out, x_mid, ctx = self._output_stage_backward(lp, dy, grads) if output_stage else (None, None, None)
         dx_mid = self._cross_attention_backward(lp, x_mid, ctx, rows_out, grads) if cross_attention else None
+        dx_self = self._self_block_backward(lp, dx_mid, grads) if self_block else None
         if accumulate:
             for name, grad in grads.items():
                 param = self.get_parameter(name)
@@ -381,6 +430,9 @@ class LightGlueTraining:
             put_sides(grads, "grad_output_stage_context", split_sides(rows_out[1], b, m, n))
         if dx_mid is not None:
             put_sides(grads, "grad_cross_block_rows", split_sides(dx_mid, b, m, n))
+        if dx_self is not None:
+            put_sides(grads, "grad_self_block_rows", split_sides(dx_self, b, m, n))
+            put_sides(grads, "grad_layer_input_rows", split_sides(dx_self + dy_in, b, m, n))
         return grads
 
     # the last cross block's parameters behind its output stage, by their names under transformers.{L-1}.cross_attn.
@@ -426,6 +478,63 @@ class LightGlueTraining:
         for name in self._CROSS_ATTENTION:
             grads[f"transformers.{lp.nl - 1}.cross_attn.{name}"] = ag[name]
         return dx
+
+    # the last SELF block: its FFN part by the names the output stage has (out_proj in the place of to_out) ...
+    _SELF_STAGE = ("out_proj.weight", "out_proj.bias", "ffn.0.weight", "ffn.0.bias", "ffn.1.weight", "ffn.1.bias",
+                   "ffn.3.weight", "ffn.3.bias")
+
+    def _self_block_backward(self, lp, dy, grads):
+        """The complete gradient dy [B*M + B*N, 256] at the last self block's output through that block: its FFN part
+        (gfc_lg_ffn_backward on the rows of layer L - 2 and the self context the prediction kept), then its rotary
+        attention and Wqkv (gfc_lg_self_attn_backward on the packed Wqkv the forward reads): the ten parameter
+        gradients into `grads`, Wqkv's mapped back to state-dict row order; returns the gradient at the block's input
+        rows [B*M + B*N, 256]."""
+        pred, rows, d, device, l = lp.pred, lp.rows, lp.d, lp.device, lp.nl - 1
+        w = self._self_block_weights(device)
+        x = lp.layer_rows(l - 1)
+        ctx = pack_sides(pred["self_block_context0"].float().contiguous(), pred["self_block_context1"].float().contiguous())
+        cos, sin = pred["self_block_cos"].float().contiguous(), pred["self_block_sin"].float().contiguous()
+        if tuple(ctx.shape) != (rows, d) or tuple(cos.shape) != (rows, 64) or tuple(sin.shape) != (rows, 64):
+            raise ValueError(f"the kept self block {tuple(ctx.shape)} / {tuple(cos.shape)} / {tuple(sin.shape)} does not "
+                             f"fit the descriptors ({rows} rows)")
+        sg = {name: torch.empty_like(w[name]) for name in self._SELF_STAGE}
+        rows_out = torch.empty((2, rows, d), device=device)
+        nat.call("gfc_lg_ffn_backward", x, ctx, dy, w["out_proj.weight"], w["out_proj.bias"], w["ffn.0.weight"],
+                 w["ffn.0.bias"], w["ffn.1.weight"], w["ffn.1.bias"], w["ffn.3.weight"], rows, sg["out_proj.weight"],
+                 sg["out_proj.bias"], sg["ffn.0.weight"], sg["ffn.0.bias"], sg["ffn.1.weight"], sg["ffn.1.bias"],
+                 sg["ffn.3.weight"], sg["ffn.3.bias"], rows_out[0], rows_out[1], lp.ws, lp.ws.numel())
+        # Wqkv in the packed row order, where the forward reads it; its gradient comes out in that order
+        by_ptr = {t.data_ptr(): t for t in self._packed[1]}
+        wqkv, bqkv = by_ptr[lp.params.wqkv[l]], by_ptr[lp.params.bqkv[l]]
+        dw, db = torch.empty_like(wqkv), torch.empty_like(bqkv)
+        dx = torch.empty((rows, d), device=device)
+        nat.call("gfc_lg_self_attn_backward", x, cos, sin, ctx, rows_out[1], rows_out[0], wqkv, bqkv, lp.b, lp.m, lp.n, dw,
+                 db, dx, lp.ws, lp.ws.numel())
+        pre = f"transformers.{l}.self_attn."
+        for name in self._SELF_STAGE:
+            grads[pre + name] = sg[name]
+        src = w["packed_rows"]  # packed row r holds state-dict row src[r]
+        grads[pre + "Wqkv.weight"] = torch.empty_like(dw).index_copy_(0, src, dw)
+        grads[pre + "Wqkv.bias"] = torch.empty_like(db).index_copy_(0, src, db)
+        return dx
+
+    def _wqkv_rows(self):
+        """src[packed row] = state-dict row of Wqkv: packed s*d + head*dh + dd <- head*(3*dh) + dd*3 + s (`_pack`)."""
+        d, dh = self.conf.descriptor_dim, self.conf.descriptor_dim // self.conf.num_heads
+        idx = torch.arange(3 * d)
+        s_, rem = idx // d, idx % d
+        return (rem // dh) * (3 * dh) + (rem % dh) * 3 + s_
+
+    def _self_stage_params(self):
+        sa = self.transformers[self.conf.n_layers - 1].self_attn
+        return {name: sa.get_parameter(name) for name in self._SELF_STAGE}
+
+    def _self_block_weights(self, device):
+        """fp32 device copies of the UNFOLDED `out_proj` / `ffn` parameters of the last self block, as
+        `_output_stage_weights` holds the cross block's, and `packed_rows`, the index of `_wqkv_rows` on the device."""
+        return self._derive("selfb", lambda: {
+            **{name: p.detach().to(device=device, dtype=torch.float32).contiguous()
+               for name, p in self._self_stage_params().items()}, "packed_rows": self._wqkv_rows().to(device)})
 
     def _cross_attention_params(self):
         ca = self.transformers[self.conf.n_layers - 1].cross_attn
@@ -490,6 +599,40 @@ class LightGlueTraining:
             if stage is not None and stage[0] is self._packed:
                 for name, param in self._output_stage_params().items():
                     t = stage[1][name]
+                    if t.data_ptr() != param.data_ptr():
+                        t.copy_(param.detach())
+
+    def self_block_updated(self):
+        """Call after the ten parameters of the last layer's SELF block were changed in place (optimizer.step()): the
+        packed `wqkv` / `bqkv` (rows permuted by `_pack`'s index), `out_proj` folded into `ffn[0]` again by the function
+        `_pack` uses (or `out_proj` itself without fold_out_proj), gamma, beta, W3, b3 are written into the packed device
+        copies IN PLACE, at the addresses captured graphs replay; fp16 copies are rounded again from the fp32 ones and the
+        unfolded copies the backward reads are refreshed.  The result is what a fresh module loaded from `state_dict()`
+        packs, bit for bit; nothing else of the packed weights is touched."""
+        if self._packed is None:
+            return
+        p, l = self._packed[0], self.conf.n_layers - 1
+        by_ptr = {t.data_ptr(): t for t in self._packed[1]}
+        sa = self.transformers[l].self_attn
+        src = self._wqkv_rows()
+        w0, b0 = self._fold_ffn0(sa.ffn[0], sa.out_proj)
+        items = [(sa.Wqkv.weight[src], p.wqkv[l], p.wqkv16[l]), (sa.Wqkv.bias[src], p.bqkv[l], None),
+                 (w0, p.s_ffn0_w[l], p.s_ffn0_w16[l]), (b0, p.s_ffn0_b[l], None), (sa.ffn[1].weight, p.s_ln_g[l], None),
+                 (sa.ffn[1].bias, p.s_ln_b[l], None), (sa.ffn[3].weight, p.s_ffn3_w[l], p.s_ffn3_w16[l]),
+                 (sa.ffn[3].bias, p.s_ffn3_b[l], None)]
+        if not bool(self.conf.fold_out_proj):
+            items += [(sa.out_proj.weight, p.s_out_w[l], p.s_out_w16[l]), (sa.out_proj.bias, p.s_out_b[l], None)]
+        with torch.no_grad():
+            for t, ptr, ptr16 in items:
+                t32 = by_ptr[ptr]
+                if t32.data_ptr() != t.data_ptr():
+                    t32.copy_(t.detach().reshape(t32.shape))
+                if ptr16:
+                    by_ptr[ptr16].copy_(t32)
+            selfb = self._derived.selfb
+            if selfb is not None and selfb[0] is self._packed:
+                for name, param in self._self_stage_params().items():
+                    t = selfb[1][name]
                     if t.data_ptr() != param.data_ptr():
                         t.copy_(param.detach())
 

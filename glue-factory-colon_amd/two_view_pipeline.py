@@ -128,14 +128,16 @@ class TwoViewPipeline(BaseModel):
         c0, c1 = out0.pop("extractor_core_time_ms", None), out1.pop("extractor_core_time_ms", None)
         return out0, out1, t_ms, c0, c1, mem
 
-    def forward_layers(self, data, keep_output_stage=False):
+    def forward_layers(self, data, keep_output_stage=False, keep_self_block=False):
         """`forward` with the matcher's `forward_layers`: every layer's descriptors kept, the input of `layer_loss`;
-        with `keep_output_stage` also what `layer_loss_backward(output_stage=True)` starts from."""
+        with `keep_output_stage` also what `layer_loss_backward(output_stage=True)` starts from, with `keep_self_block`
+        what its `self_block=True` does."""
         for key in self.required_data_keys:
             assert key in data, f"Missing key {key} in data"
-        if not keep_output_stage:
+        if not keep_output_stage and not keep_self_block:
             return self._forward(data, match=self.matcher.forward_layers)
-        return self._forward(data, match=lambda d: self.matcher.forward_layers(d, keep_output_stage=True))
+        return self._forward(data, match=lambda d: self.matcher.forward_layers(
+            d, keep_output_stage=keep_output_stage, keep_self_block=keep_self_block))
 
     def _forward(self, data, match=None):
         image0, image1 = _image_of(data["view0"]), _image_of(data["view1"])
